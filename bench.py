@@ -1,16 +1,22 @@
 #!/usr/bin/env python3
 """Headline benchmark: training img/s at 640x192, RepLKNet-31B Stage-1 (BASELINE.json config 2/3).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One rank per GPU (RCCL).  A "step" = Trainer.process_batch (teacher + multi-frame forward, both
 photometric losses) + backward + gradient all-reduce + Adam step on a synthetic batch of 12 frame
 triplets per GPU already resident in HBM.  Rank 0 prints ONE JSON line.
 
-Extra objects in the line:
+A plain run sets up, warms up, times exactly K steps and prints the line (`ms_per_step` = one timed
+step).  --dump-outputs DIR then writes rank 0's outputs and losses of the last timed step as
+DIR/<name>.npy (float32 / float64; arrays above a size cap as a fixed, seeded sample).
+
+--full adds the measurements of their own, objects in the line:
   roofline      31x31 depthwise-conv kernel (the kernel north_star names): algorithmic bytes per
-                launch / average launch duration measured with HIP events inside the timed steps.
+                launch / average launch duration measured with HIP events inside an eager probe step.
+  roofline_pwconv, sync_bn, rccl   the largest 1x1-conv GEMM alone; SyncBN / RCCL census of the probe step.
+  absrel        AbsRel of a fresh model on a synthetic eigen_zhou-format split (fp32 and bf16).
   cpu_baseline  the CPU oracle (oracle/ref_model.py, a restatement pinned to the reference's golden
                 vectors) timed on this host for one B=2 step (rank 0, N=1 only).
 """
@@ -121,6 +127,40 @@ def cpu_baseline(seconds_budget=40.0, eval_root=None):
     return out
 
 
+def dump_outputs(out_dir, outputs, losses, budget=60 << 20):
+    """Every tensor of the step's `outputs` and `losses` dicts as out_dir/{outputs,losses}.<key>.npy: float64 tensors as
+    float64, the rest as float32 (integers as float64, exact).  Arrays of more than `cap` elements are written as a
+    sample: the flattened array at `cap` sorted positions drawn by a generator seeded with 0, the same for every array
+    of that size, so two builds compare position for position.  `cap` starts at 2^18 and halves until the files fit
+    the budget (64 MB in all with headers)."""
+    import numpy as np
+    arrays = {}
+    for prefix, d in (("outputs", outputs), ("losses", losses)):
+        for k, v in d.items():
+            if not torch.is_tensor(v):
+                continue
+            name = prefix + "." + ("_".join(str(p) for p in k) if isinstance(k, tuple) else str(k)).replace("/", "_")
+            if name in arrays:
+                raise ValueError(f"--dump-outputs: two keys map to {name}")
+            wide = v.dtype == torch.float64 or not (v.is_floating_point() or v.dtype == torch.bool)
+            arrays[name] = v.detach().to(torch.float64 if wide else torch.float32)
+    cap = 1 << 18
+    while sum(min(a.numel(), cap) * a.element_size() + 128 for a in arrays.values()) > budget:
+        cap //= 2
+    os.makedirs(out_dir, exist_ok=True)
+    picks = {}
+    for name, a in arrays.items():
+        n = a.numel()
+        if n > cap:
+            if n not in picks:
+                idx = np.sort(np.random.default_rng(0).choice(n, cap, replace=False))
+                picks[n] = torch.from_numpy(idx).to(a.device)
+            a = a.reshape(-1)[picks[n]]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+    print(f"[bench] --dump-outputs: {len(arrays)} arrays -> {out_dir} (at most {cap} elements each)",
+          file=sys.stderr, flush=True)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` outside a launcher: start the N ranks ourselves, one per GPU, BEFORE anything touches a
     GPU (torch.cuda.device_count() does not initialise HIP on this image), and leave with the worst exit status.  Never
@@ -154,7 +194,12 @@ def main():
     ap.add_argument("--batch", type=int, default=12, help="per-GPU batch (reference --batch_size)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--rep_size", default="b", choices=["b", "l"])
-    ap.add_argument("--no_cpu_baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beside the headline: roofline probes, SyncBN / RCCL census, AbsRel, "
+                         "CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs and losses (rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no_cpu_baseline", action="store_true", help="with --full: skip the CPU baseline and AbsRel")
     ap.add_argument("--eager", action="store_true", help="no hipGraph: launch every kernel from Python")
     ap.add_argument("--height", type=int, default=192)
     ap.add_argument("--width", type=int, default=640)
@@ -166,6 +211,8 @@ def main():
                     help="Stage-2 decoder adapter (BASELINE config 5: --dc after dc_ft_init, Cityscapes intrinsics; the "
                          "reference trains it at 192x512, BASELINE names 512x1024: pass --height/--width)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         spawn_ranks(args.gpus)                # does not return
 
@@ -245,11 +292,15 @@ def main():
     for _ in range(args.warmup):
         engine.step(dict(inputs))
     barrier()
-    # roofline probe: HIP events around every k=31 launch of ONE eager step (events cannot be recorded
+    # roofline probe (--full): HIP events around every k=31 launch of ONE eager step (events cannot be recorded
     # inside a captured graph); the same kernels with the same arguments are what the graph replays.
     # The probe step is launched behind ~15 ms of queued device work, so that the host stays ahead of the GPU for the
     # whole step: the launches then meet the conditions of the graph replays that the timed region consists of (a busy
     # device at its working clocks, the other streams' kernels in flight) instead of an idle GPU waking up for each one.
+    # A plain run skips every measurement below but still trains the probe step and draws the probes' random operands
+    # from the device generator (which also feeds the step's DropPath and tie-break draws): plain and --full runs, and
+    # earlier builds, then train the same trajectory and compute the same outputs.
+    full = args.full
     head = None
     if args.dtype == "bf16":
         C0_ = 128 if args.rep_size == "b" else 192
@@ -263,15 +314,16 @@ def main():
                     ops.dwconv_lk(*head)
 
     torch.cuda.synchronize()
-    head_start(250)
-    ops.PROFILE_DWCONV = []                       # (kind, start_event, end_event) per k=31 launch
-    ops.SYNC_COUNTERS = {}                        # SyncBN launches / collectives of this one eager step
-    pdist.COLLECTIVE_LOG = []                     # (communicator, op, elements, dtype) of every collective, in issue order
+    if full:
+        head_start(250)
+        ops.PROFILE_DWCONV = []                   # (kind, start_event, end_event) per k=31 launch
+        ops.SYNC_COUNTERS = {}                    # SyncBN launches / collectives of this one eager step
+        pdist.COLLECTIVE_LOG = []                 # (communicator, op, elements, dtype) of every collective, in issue order
     engine.step(dict(inputs))
     barrier()
-    events, ops.PROFILE_DWCONV = ops.PROFILE_DWCONV, None
-    sync_counts, ops.SYNC_COUNTERS = ops.SYNC_COUNTERS, None
-    coll_log, pdist.COLLECTIVE_LOG = pdist.COLLECTIVE_LOG, None
+    events, ops.PROFILE_DWCONV = ops.PROFILE_DWCONV or [], None
+    sync_counts, ops.SYNC_COUNTERS = ops.SYNC_COUNTERS or {}, None
+    coll_log, pdist.COLLECTIVE_LOG = pdist.COLLECTIVE_LOG or [], None
     # the same launch (same tensors, same stream) 20x back to back between two HIP events: the kernel's duration
     # without the host gaps that events around ONE ~80 us launch include
     replay_us = {}
@@ -291,25 +343,26 @@ def main():
     # the same pattern around a near-empty kernel, behind the same kind of head start, minus that kernel's own
     # back-to-back cost.  Subtracted from the per-launch figures below.
     event_overhead_us = 0.0
-    with torch.cuda.stream(engine.stream):
-        tiny = torch.zeros(64, device=device)
-        torch.cuda.synchronize()
-        head_start(60)
-        pairs = []
-        for _ in range(24):
+    if full:
+        with torch.cuda.stream(engine.stream):
+            tiny = torch.zeros(64, device=device)
+            torch.cuda.synchronize()
+            head_start(60)
+            pairs = []
+            for _ in range(24):
+                s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s_ev.record()
+                tiny.zero_()
+                e_ev.record()
+                pairs.append((s_ev, e_ev))
             s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             s_ev.record()
-            tiny.zero_()
+            for _ in range(50):
+                tiny.zero_()
             e_ev.record()
-            pairs.append((s_ev, e_ev))
-        s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s_ev.record()
-        for _ in range(50):
-            tiny.zero_()
-        e_ev.record()
-        e_ev.synchronize()
-        singles = sorted(a.elapsed_time(b) * 1e3 for a, b in pairs)
-        event_overhead_us = max(0.0, singles[len(singles) // 2] - s_ev.elapsed_time(e_ev) / 50 * 1e3)
+            e_ev.synchronize()
+            singles = sorted(a.elapsed_time(b) * 1e3 for a, b in pairs)
+            event_overhead_us = max(0.0, singles[len(singles) // 2] - s_ev.elapsed_time(e_ev) / 50 * 1e3)
     head = None
     # the PLAIN 31x31 (+5x5) forward -- round 1 / 2's roofline kernel; in the step its place is taken by the variant with
     # pw1's BatchNorm + ReLU fused into the staging pass -- 20 launches back to back on the launch stream
@@ -320,15 +373,16 @@ def main():
             xx = torch.randn(B, C0_, H // 4, W // 4, device=device).bfloat16()
             wb_ = torch.randn(C0_, 1, 31, 31, device=device) / 31
             ws_ = torch.randn(C0_, 1, 5, 5, device=device) / 5
-            for _ in range(3):
-                ops.dwconv_lk(xx, wb_, ws_)
-            s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s_ev.record()
-            for _ in range(20):
-                ops.dwconv_lk(xx, wb_, ws_)
-            e_ev.record()
-            e_ev.synchronize()
-            plain_us = s_ev.elapsed_time(e_ev) / 20 * 1e3
+            if full:
+                for _ in range(3):
+                    ops.dwconv_lk(xx, wb_, ws_)
+                s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s_ev.record()
+                for _ in range(20):
+                    ops.dwconv_lk(xx, wb_, ws_)
+                e_ev.record()
+                e_ev.synchronize()
+                plain_us = s_ev.elapsed_time(e_ev) / 20 * 1e3
             del xx, wb_, ws_
     barrier()
     # second roofline: the kernel family that carries the most wall time of the step (profiles/r02_wall_attribution.txt) --
@@ -339,22 +393,24 @@ def main():
         with torch.cuda.stream(engine.stream):
             xx = torch.randn(B, 512, 12, 40, device=device).bfloat16()
             aa = (torch.randn(2048, 512, device=device) / 512 ** 0.5).bfloat16()
-            for _ in range(3):
-                ops.pwconv_raw(aa, xx)
-            s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            s_ev.record()
-            for _ in range(20):
-                ops.pwconv_raw(aa, xx)
-            e_ev.record()
-            e_ev.synchronize()
-            t_pw = s_ev.elapsed_time(e_ev) / 20 * 1e-3
-        flops = 2.0 * B * 480 * 512 * 2048
-        pw_roof = {"kernel": "pwconv2_kernel<128,32,0>: 1x1 conv 512 -> 2048 on [%d,512,12,40] (ConvFFN pw1, stage 2)" % B,
-                   "bound": "mfma", "achieved": round(flops / t_pw / 1e12, 1), "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s",
-                   "frac": round(flops / t_pw / 1e12 / MFMA_BF16_PEAK_TF, 4), "traffic": None,
-                   "back_to_back_us": round(t_pw * 1e6, 1), "flops_per_launch": flops,
-                   "note": "host-paced launches; hipGraph-paced per trunk shape vs the library: profiles/r04_pwconv_shapes.txt; "
-                           "algorithmic bytes %.1f MB" % ((B * 480 * (512 + 2048) + 512 * 2048) * 2 / 1e6)}
+            if full:
+                for _ in range(3):
+                    ops.pwconv_raw(aa, xx)
+                s_ev, e_ev = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                s_ev.record()
+                for _ in range(20):
+                    ops.pwconv_raw(aa, xx)
+                e_ev.record()
+                e_ev.synchronize()
+                t_pw = s_ev.elapsed_time(e_ev) / 20 * 1e-3
+        if full:
+            flops = 2.0 * B * 480 * 512 * 2048
+            pw_roof = {"kernel": "pwconv2_kernel<128,32,0>: 1x1 conv 512 -> 2048 on [%d,512,12,40] (ConvFFN pw1, stage 2)" % B,
+                       "bound": "mfma", "achieved": round(flops / t_pw / 1e12, 1), "peak": MFMA_BF16_PEAK_TF, "unit": "TFLOP/s",
+                       "frac": round(flops / t_pw / 1e12 / MFMA_BF16_PEAK_TF, 4), "traffic": None,
+                       "back_to_back_us": round(t_pw * 1e6, 1), "flops_per_launch": flops,
+                       "note": "host-paced launches; hipGraph-paced per trunk shape vs the library: profiles/r04_pwconv_shapes.txt; "
+                               "algorithmic bytes %.1f MB" % ((B * 480 * (512 + 2048) + 512 * 2048) * 2 / 1e6)}
         del xx, aa
     barrier()
     # Several ranks: the captured step also holds the RCCL calls (SyncBN all-gathers / all-reduces on per-branch
@@ -465,31 +521,34 @@ def main():
                        "launch": launch},
             "final_loss": round(loss_val, 5),
             "input_pipeline": pipe_info,
-            "sync_bn": ({"launches_per_step": sync_counts.get("launches", 0),
-                         "collectives_per_step": sync_counts.get("collectives", 0),
-                         "forced_single_rank": bool(pdist.FORCE_COLLECTIVES and world == 1)}
-                        if pdist.collectives_on() else None),
-            "rccl": rccl_census(),
-            "roofline": roof,
-            "roofline_pwconv": pw_roof,
         }
-
+        if args.full:
+            line.update({
+                "sync_bn": ({"launches_per_step": sync_counts.get("launches", 0),
+                             "collectives_per_step": sync_counts.get("collectives", 0),
+                             "forced_single_rank": bool(pdist.FORCE_COLLECTIVES and world == 1)}
+                            if pdist.collectives_on() else None),
+                "rccl": rccl_census(),
+                "roofline": roof,
+                "roofline_pwconv": pw_roof,
+            })
         return line
 
     multi = pdist.collectives_on()
     use_graph = (not args.eager) and (not multi or os.environ.get("PPEA_MULTI_GRAPH", "1") == "1")
 
     def timed(eager):
-        """EXACTLY args.steps steps between barriers; max over ranks."""
+        """EXACTLY args.steps steps between barriers; max over ranks.  -> (seconds, loss, (outputs, losses) of the
+        last step)."""
         barrier()
         t0 = time.time()
         for _ in range(args.steps):
-            _, ls = engine.step(dict(inputs) if eager else inputs)
+            last = engine.step(dict(inputs) if eager else inputs)
         barrier()
         el = torch.tensor([time.time() - t0], device=device, dtype=torch.float64)
         if world > 1:
             dist.all_reduce(el, op=dist.ReduceOp.MAX)
-        return float(el), float(ls["loss"].detach())
+        return float(el), float(last[1]["loss"].detach()), last
 
     # Several ranks: the captured step holds RCCL calls on two communicators next to the compute branches.  That
     # combination cannot run on the one-GPU development box, so it is fenced twice: the eager measurement is taken
@@ -533,7 +592,7 @@ def main():
         line = make_line(dt, loss_val, launch)
         if hang:
             line["hang"] = True
-        if world == 1 and not args.no_cpu_baseline and (H, W) == (192, 640) and not args.dc:
+        if args.full and world == 1 and not args.no_cpu_baseline and (H, W) == (192, 640) and not args.dc:
             import tempfile
             eval_root = tempfile.mkdtemp(prefix="ppea_eval_") if args.rep_size == "b" else None
             try:
@@ -571,11 +630,13 @@ def main():
         for _ in range(2):
             engine.step(inputs)
     if use_graph or fallback is None:
-        dt, loss_val = timed(eager=args.eager)
+        dt, loss_val, last = timed(eager=args.eager)
     else:
-        dt, loss_val = fallback
+        dt, loss_val, last = fallback
     if watchdog is not None:
         watchdog.cancel()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
 
     if rank == 0 and engine.flat is not None and engine.flat.hooked:
         plan = engine.flat.last_plan

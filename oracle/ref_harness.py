@@ -27,6 +27,9 @@ import torch
 import torch.nn as nn
 
 REFERENCE_ROOT = "/root/reference"
+# the reference's `ppeadepth` package byte-compiled by build() (oracle/build_ref.py; sourceless .pyc, never committed):
+# travels with the working tree to machines that have no reference tree
+COMPILED_ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_ref")
 
 
 def reference_available() -> bool:
@@ -137,7 +140,8 @@ def _module(name, **attrs):
 _installed = False
 
 
-def install_stubs():
+def install_stubs(root=REFERENCE_ROOT):
+    """Third-party stand-ins, then `root` (the reference tree, or COMPILED_ROOT) first on sys.path."""
     global _installed
     if _installed:
         return
@@ -189,8 +193,8 @@ def install_stubs():
     _module("torchmetrics", Metric=_Metric)
     sk_t = _module("skimage.transform")
     _module("skimage", transform=sk_t)
-    if REFERENCE_ROOT not in sys.path:
-        sys.path.insert(0, REFERENCE_ROOT)
+    if root not in sys.path:
+        sys.path.insert(0, root)
     _installed = True
 
 

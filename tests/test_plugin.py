@@ -88,18 +88,23 @@ def test_plugin_imports_next_to_a_foreign_ppeadepth_package():
     assert out.strip().endswith("ok")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/ppeadepth"), reason="reference tree only in the build container")
+COMPILED_REF = os.path.join(ROOT, "oracle", "_ref")
+
+
+@pytest.mark.skipif(not os.path.isfile(os.path.join(COMPILED_REF, "ppeadepth", "__init__.pyc")),
+                    reason="build() found no reference tree to compile into oracle/_ref")
 def test_plugin_through_the_unmodified_reference_get_conv2d():
     """The reference's own `get_conv2d` / `ReparamLargeKernelConv` with LARGE_KERNEL_CONV_IMPL set (CPU: construction,
-    state_dict keys, merge_kernel; the forward needs a GPU and is covered by the -m gpu case below)."""
+    state_dict keys, merge_kernel; the forward needs a GPU and is covered by the -m gpu case below).  The reference
+    package is the one build() byte-compiled into oracle/_ref (oracle/build_ref.py)."""
     env = dict(os.environ, LARGE_KERNEL_CONV_IMPL=PKG)
     code = textwrap.dedent(f"""
         import sys
         sys.path.insert(0, {ROOT!r})
         from oracle import ref_harness as rh
-        rh.install_stubs()
+        rh.install_stubs(rh.COMPILED_ROOT)
         import ppeadepth
-        assert ppeadepth.__file__.startswith("/root/reference/")
+        assert ppeadepth.__file__.startswith(rh.COMPILED_ROOT + "/")
         from ppeadepth.networks import replknet_adapter as rka
         blk = rka.ReparamLargeKernelConv(8, 8, 13, 1, 8, small_kernel=5)
         assert type(blk.lkb_origin.conv).__name__ == "DepthWiseConv2dImplicitGEMM"

@@ -10,11 +10,11 @@ OUT=gpurun_out/prof_final
 mkdir -p $OUT
 bash tools/prof_forced.sh $R || exit 1
 cp gpurun_out/prof_fc/${R}_forced_collectives_* $OUT/
-PPEA_FORCE_COLLECTIVES=1 python3 bench.py --no_cpu_baseline > $OUT/${R}_forced_collectives_n1.json 2> $OUT/fc.err || exit 1
-python3 bench.py --no_cpu_baseline --rep_size l --batch 8 > $OUT/${R}_bench_n1_config_l.json 2>> $OUT/cfg.err || exit 1
-python3 bench.py --no_cpu_baseline --dc --height 192 --width 512 --batch 4 > $OUT/${R}_bench_n1_config_dc192.json 2>> $OUT/cfg.err || exit 1
-python3 bench.py --no_cpu_baseline --dc --height 512 --width 1024 --batch 4 > $OUT/${R}_bench_n1_config_dc512.json 2>> $OUT/cfg.err || exit 1
-python3 bench.py --no_cpu_baseline --input_pipeline > $OUT/${R}_bench_n1_input_pipeline.json 2>> $OUT/cfg.err || exit 1
+PPEA_FORCE_COLLECTIVES=1 python3 bench.py --full --no_cpu_baseline > $OUT/${R}_forced_collectives_n1.json 2> $OUT/fc.err || exit 1
+python3 bench.py --full --no_cpu_baseline --rep_size l --batch 8 > $OUT/${R}_bench_n1_config_l.json 2>> $OUT/cfg.err || exit 1
+python3 bench.py --full --no_cpu_baseline --dc --height 192 --width 512 --batch 4 > $OUT/${R}_bench_n1_config_dc192.json 2>> $OUT/cfg.err || exit 1
+python3 bench.py --full --no_cpu_baseline --dc --height 512 --width 1024 --batch 4 > $OUT/${R}_bench_n1_config_dc512.json 2>> $OUT/cfg.err || exit 1
+python3 bench.py --full --no_cpu_baseline --input_pipeline > $OUT/${R}_bench_n1_input_pipeline.json 2>> $OUT/cfg.err || exit 1
 python3 tools/render_parity.py > $OUT/${R}_bf16_render_parity.txt 2>> $OUT/cfg.err || exit 1
 python3 tools/render_parity.py e2e_render_l > $OUT/${R}_bf16_render_parity_l.txt 2>> $OUT/cfg.err || exit 1
 python3 tools/render_parity.py e2e_render_dc > $OUT/${R}_bf16_render_parity_dc.txt 2>> $OUT/cfg.err || exit 1

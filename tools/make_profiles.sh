@@ -10,9 +10,9 @@ mkdir -p $OUT
 if [ -z "$SKIP_BENCH" ]; then
 rm -f $OUT/*
 # 1. the default bench line (no profiler)
-python3 bench.py > $OUT/${R}_bench_n1.json 2> $OUT/bench.err || exit 1
+python3 bench.py --full > $OUT/${R}_bench_n1.json 2> $OUT/bench.err || exit 1
 # 2. kernel trace + stats of the same command (20 timed steps), per-step breakdown
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- python3 bench.py --steps 20 --warmup 3 --no_cpu_baseline \
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_kt -- python3 bench.py --full --steps 20 --warmup 3 --no_cpu_baseline \
     > $OUT/${R}_bench_n1_under_rocprof.json 2> $OUT/rocprof.err || exit 1
 KT=$(find /tmp/prof_kt -name "*kernel_trace.csv" | head -1)
 ST=$(find /tmp/prof_kt -name "*kernel_stats.csv" | head -1)

@@ -8,7 +8,7 @@ cd "$GRAFT_REPO_ROOT" || exit 1
 OUT=gpurun_out/prof_fc
 mkdir -p $OUT
 export PPEA_FORCE_COLLECTIVES=1
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_fc -- python3 bench.py --steps 20 --warmup 3 --no_cpu_baseline \
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_fc -- python3 bench.py --full --steps 20 --warmup 3 --no_cpu_baseline \
     > $OUT/${R}_forced_collectives_under_rocprof.json 2> $OUT/rocprof.err || exit 1
 KT=$(find /tmp/prof_fc -name "*kernel_trace.csv" | head -1)
 ST=$(find /tmp/prof_fc -name "*kernel_stats.csv" | head -1)
