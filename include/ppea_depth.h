@@ -141,6 +141,29 @@ int ppea_bn_finalize_sums_f32(const float* partial, int P, int C, long count, fl
                               float* var, float* invstd, float* running_mean, float* running_var, void* stream);
 int ppea_pwconv_ex_bf16(const void* A, const void* X, const void* bias, int bias_bf16, int epi, const void* aux,
                         void* Y, void* Y2, int B, int M, int K, int HW, int a_transposed, void* stream);
+/* Inference forms of the depthwise convs (eval-mode BatchNorm folded):
+ *   ppea_dwconv_lk_fwd_bias_act_bf16p  y = act(DW_K(x; packed merged filter) + bias[c]) on the MFMA kernel: an eval-mode
+ *       ReparamLargeKernelConv (+ ReLU) in one launch; packed = ppea_dwconv_lk_pack_bf16 of a_big W_k + pad(a_small W_5),
+ *       bias = o_big + o_small; relu != 0: ReLU.  K in {31, 29, 27, 13}; unserved shapes: PPEA_ERR_UNSUPPORTED.
+ *   ppea_dwconv_lk_fwd_bias_act_f32 / _bf16  the same on the fp32-arithmetic kernel with the fp32 filter [C][K][K].
+ *   ppea_dwconv3x3_fwd_affine_f32 / _bf16    y = act(s[c] * DW3x3(x) + o[c]) (stem[1], stem[3], transitions[.][1]). */
+int ppea_dwconv_lk_fwd_bias_act_bf16p(const uint16_t* x, const void* packed, const float* bias, int relu, uint16_t* y, int N,
+                                      int C, int H, int W, int K, void* stream);
+int ppea_dwconv_lk_fwd_bias_act_f32(const void* x, const float* w, const float* bias, int relu, void* y, int N, int C, int H,
+                                    int W, int K, void* stream);
+int ppea_dwconv_lk_fwd_bias_act_bf16(const void* x, const float* w, const float* bias, int relu, void* y, int N, int C, int H,
+                                     int W, int K, void* stream);
+int ppea_dwconv3x3_fwd_affine_f32(const void* x, const float* w, const float* s, const float* o, int relu, void* y, int N, int C,
+                                  int H, int W, int stride, void* stream);
+int ppea_dwconv3x3_fwd_affine_bf16(const void* x, const float* w, const float* s, const float* o, int relu, void* y, int N, int C,
+                                   int H, int W, int stride, void* stream);
+/* Inference form (eval-mode BatchNorm folded into a per-channel fp32 table applied to the accumulator; the matrix is the
+ * training model's bf16 weight, unchanged):  t = act(s[m] * (A X)[m][p] + o[m]), act 0 none / 1 ReLU / 2 GELU(erf), s NULL = 1,
+ * o NULL = 0;  Y = t (+ r1) (+ r2_scale * r2), r1 / r2 [B][M][HW] bf16 or NULL;  Y2 (optional) = s2[m] * Y + o2[m] of Y as
+ * stored: the next block's first BatchNorm.  K % 32 == 0 and HW % 8 == 0, else PPEA_ERR_UNSUPPORTED. */
+int ppea_pwconv_infer_bf16(const void* A, const void* X, const float* s, const float* o, int act, const void* r1,
+                           const void* r2, float r2_scale, const float* s2, const float* o2, void* Y, void* Y2, int B, int M,
+                           int K, int HW, void* stream);
 long ppea_pwgrad_workspace_bytes(int B, int M, int N, int HW);
 int ppea_pwgrad_bf16(const void* P, const void* Q, float* out, void* workspace, int B, int M, int N, int HW,
                      int want_rowsum, void* stream);

@@ -6,11 +6,22 @@
 
 namespace {
 
-template <typename T, int S>
-__global__ __launch_bounds__(256) void dw3_fwd(const T* __restrict__ x, const float* __restrict__ w,
-                                               T* __restrict__ y, int C, int H, int W, int Ho, int Wo) {
+// Inference epilogue (ppea_dwconv3x3_fwd_affine_*): y = act(s[c] * conv + o[c]) -- the eval-mode BatchNorm (+ ReLU) that
+// follows stem[1], stem[3] and transitions[.][1], applied to the fp32 accumulator before the store.
+struct Aff { const float* s; const float* o; int relu; };
+template <bool AFF>
+__device__ __forceinline__ float aff1(float v, float a, float b, int relu) {
+    if constexpr (AFF) { v = fmaf(a, v, b); if (relu) v = fmaxf(v, 0.f); }
+    return v;
+}
+
+template <typename T, int S, bool AFF>
+__device__ __forceinline__ void dw3_fwd_body(const T* __restrict__ x, const float* __restrict__ w,
+                                             T* __restrict__ y, int C, int H, int W, int Ho, int Wo, Aff af) {
     const int plane = blockIdx.y;                          // n * C + c
     const int c = plane % C;
+    float fa = 1.f, fb = 0.f;
+    if constexpr (AFF) { fa = af.s[c]; fb = af.o[c]; }
     const float* wc = w + c * 9;
     float k[9];
 #pragma unroll
@@ -31,8 +42,18 @@ __global__ __launch_bounds__(256) void dw3_fwd(const T* __restrict__ x, const fl
                 if (ix >= 0 && ix < W) acc = fmaf(k[u * 3 + v], ld_f32<T>(xp + (long)iy * W + ix), acc);
             }
         }
-        st_f32<T>(yp + i, acc);
+        st_f32<T>(yp + i, aff1<AFF>(acc, fa, fb, af.relu));
     }
+}
+template <typename T, int S>
+__global__ __launch_bounds__(256) void dw3_fwd(const T* __restrict__ x, const float* __restrict__ w,
+                                               T* __restrict__ y, int C, int H, int W, int Ho, int Wo) {
+    dw3_fwd_body<T, S, false>(x, w, y, C, H, W, Ho, Wo, Aff{nullptr, nullptr, 0});
+}
+template <typename T, int S>
+__global__ __launch_bounds__(256) void dw3_fwd_aff(const T* __restrict__ x, const float* __restrict__ w,
+                                                   T* __restrict__ y, int C, int H, int W, int Ho, int Wo, Aff af) {
+    dw3_fwd_body<T, S, true>(x, w, y, C, H, W, Ho, Wo, af);
 }
 
 // dx[iy][ix] = sum_{u,v} w[u][v] * dy[oy][ox]  with  oy*S - 1 + u = iy,  ox*S - 1 + v = ix
@@ -90,9 +111,9 @@ __device__ __forceinline__ void st8(uint16_t* p, const float (&a)[8]) {
 }
 
 // stride 1 (forward, and data gradient with the taps reversed by the caller flag FLIP): W % 8 == 0
-template <bool FLIP>
-__global__ __launch_bounds__(256) void dw3v_s1(const uint16_t* __restrict__ x, const float* __restrict__ w,
-                                               uint16_t* __restrict__ y, int C, int H, int W, long total) {
+template <bool FLIP, bool AFF>
+__device__ __forceinline__ void dw3v_s1_body(const uint16_t* __restrict__ x, const float* __restrict__ w,
+                                             uint16_t* __restrict__ y, int C, int H, int W, long total, Aff af) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int W8 = W >> 3;
@@ -120,13 +141,28 @@ __global__ __launch_bounds__(256) void dw3v_s1(const uint16_t* __restrict__ x, c
         for (int j = 0; j < 8; ++j)
             acc[j] = fmaf(k[u * 3 + 2], in[j + 2], fmaf(k[u * 3 + 1], in[j + 1], fmaf(k[u * 3], in[j], acc[j])));
     }
+    if constexpr (AFF) {
+        const float fa = af.s[plane % C], fb = af.o[plane % C];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = aff1<true>(acc[j], fa, fb, af.relu);
+    }
     st8(y + (plane * H + oy) * (long)W + x0, acc);
+}
+template <bool FLIP>
+__global__ __launch_bounds__(256) void dw3v_s1(const uint16_t* __restrict__ x, const float* __restrict__ w,
+                                               uint16_t* __restrict__ y, int C, int H, int W, long total) {
+    dw3v_s1_body<FLIP, false>(x, w, y, C, H, W, total, Aff{nullptr, nullptr, 0});
+}
+__global__ __launch_bounds__(256) void dw3v_s1_aff(const uint16_t* __restrict__ x, const float* __restrict__ w,
+                                                   uint16_t* __restrict__ y, int C, int H, int W, long total, Aff af) {
+    dw3v_s1_body<false, true>(x, w, y, C, H, W, total, af);
 }
 
 // stride 2 forward: Wo % 8 == 0, W == 2 * Wo
-__global__ __launch_bounds__(256) void dw3v_s2_fwd(const uint16_t* __restrict__ x, const float* __restrict__ w,
-                                                   uint16_t* __restrict__ y, int C, int H, int W, int Ho, int Wo,
-                                                   long total) {
+template <bool AFF>
+__device__ __forceinline__ void dw3v_s2_fwd_body(const uint16_t* __restrict__ x, const float* __restrict__ w,
+                                                 uint16_t* __restrict__ y, int C, int H, int W, int Ho, int Wo,
+                                                 long total, Aff af) {
     const long idx = (long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= total) return;
     const int W8 = Wo >> 3;
@@ -153,7 +189,22 @@ __global__ __launch_bounds__(256) void dw3v_s2_fwd(const uint16_t* __restrict__ 
         for (int j = 0; j < 8; ++j)
             acc[j] = fmaf(k[u * 3 + 2], in[2 * j + 2], fmaf(k[u * 3 + 1], in[2 * j + 1], fmaf(k[u * 3], in[2 * j], acc[j])));
     }
+    if constexpr (AFF) {
+        const float fa = af.s[plane % C], fb = af.o[plane % C];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc[j] = aff1<true>(acc[j], fa, fb, af.relu);
+    }
     st8(y + (plane * Ho + oy) * (long)Wo + x0, acc);
+}
+__global__ __launch_bounds__(256) void dw3v_s2_fwd(const uint16_t* __restrict__ x, const float* __restrict__ w,
+                                                   uint16_t* __restrict__ y, int C, int H, int W, int Ho, int Wo,
+                                                   long total) {
+    dw3v_s2_fwd_body<false>(x, w, y, C, H, W, Ho, Wo, total, Aff{nullptr, nullptr, 0});
+}
+__global__ __launch_bounds__(256) void dw3v_s2_fwd_aff(const uint16_t* __restrict__ x, const float* __restrict__ w,
+                                                       uint16_t* __restrict__ y, int C, int H, int W, int Ho, int Wo,
+                                                       long total, Aff af) {
+    dw3v_s2_fwd_body<true>(x, w, y, C, H, W, Ho, Wo, total, af);
 }
 
 // stride 2 data gradient: dx[iy][ix] = sum w[u][v] dy[(iy+1-u)/2][(ix+1-v)/2] over even numerators; W % 8 == 0
@@ -240,9 +291,52 @@ int run(bool bwd, const void* a, const float* w, void* o, int N, int C, int H, i
     return launch_status();
 }
 
+template <typename T>
+int run_affine(const void* a, const float* w, const float* s, const float* o, int relu, void* out_, int N, int C, int H, int W,
+               int stride, void* stream) {
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return PPEA_ERR_UNSUPPORTED;
+    if (a == nullptr || w == nullptr || s == nullptr || o == nullptr || out_ == nullptr) return PPEA_ERR_ARG;
+    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
+    const long planes = (long)N * C;
+    if (planes > 65535) return PPEA_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    const Aff af{s, o, relu};
+    if constexpr (sizeof(T) == 2) {
+        const uint16_t* in = (const uint16_t*)a;
+        uint16_t* out = (uint16_t*)out_;
+        if (stride == 1 && (W & 7) == 0) {
+            const long total = planes * H * (W >> 3);
+            hipLaunchKernelGGL(dw3v_s1_aff, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H, W, total, af);
+            return launch_status();
+        }
+        if (stride == 2 && (W & 1) == 0 && (H & 1) == 0 && (Wo & 7) == 0) {
+            const long total = planes * Ho * (Wo >> 3);
+            hipLaunchKernelGGL(dw3v_s2_fwd_aff, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H, W, Ho,
+                               Wo, total, af);
+            return launch_status();
+        }
+    }
+    int bx = (Ho * Wo + 255) / 256;
+    if (bx > 64) bx = 64;
+    dim3 g(bx, (unsigned)planes);
+    if (stride == 1) hipLaunchKernelGGL((dw3_fwd_aff<T, 1>), g, dim3(256), 0, st, (const T*)a, w, (T*)out_, C, H, W, Ho, Wo, af);
+    else hipLaunchKernelGGL((dw3_fwd_aff<T, 2>), g, dim3(256), 0, st, (const T*)a, w, (T*)out_, C, H, W, Ho, Wo, af);
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
+// Inference: y = act(s[c] * DW3x3(x)[c] + o[c]), relu != 0: ReLU (eval-mode BatchNorm folded to a table); shapes as
+// ppea_dwconv3x3_fwd_*; N * C > 65535 or stride not in {1, 2}: PPEA_ERR_UNSUPPORTED.
+int ppea_dwconv3x3_fwd_affine_f32(const void* x, const float* w, const float* s, const float* o, int relu, void* y, int N, int C,
+                                  int H, int W, int stride, void* stream) {
+    return run_affine<float>(x, w, s, o, relu, y, N, C, H, W, stride, stream);
+}
+int ppea_dwconv3x3_fwd_affine_bf16(const void* x, const float* w, const float* s, const float* o, int relu, void* y, int N, int C,
+                                   int H, int W, int stride, void* stream) {
+    return run_affine<uint16_t>(x, w, s, o, relu, y, N, C, H, W, stride, stream);
+}
 // x [N,C,H,W] -> y [N,C,Ho,Wo], Ho = (H-1)/stride + 1; w [C,1,3,3] fp32
 int ppea_dwconv3x3_fwd_f32(const void* x, const float* w, void* y, int N, int C, int H, int W, int stride, void* stream) {
     return run<float>(false, x, w, y, N, C, H, W, stride, stream);

@@ -110,7 +110,9 @@ __device__ __forceinline__ void store_tile(T* plane, const float (&acc)[RY][RX],
 // BWD = true : a = dy_big, b = dy_small (KS > 0), out0 = dx
 constexpr int WPB = 2;   // waves per workgroup (items are wave-private; small groups pack LDS tighter)
 
-template <typename T, int K, int KS, int RY, int RX, int LX, int LY, bool BWD>
+// BA (inference, ppea_dwconv_lk_fwd_bias_act_*): forward of ONE filter (KS = 0) with y = act(conv + bias[c]); the bias
+// table rides in the unused `w_small` slot and `out1 != nullptr` asks for ReLU (out1 is never written).
+template <typename T, int K, int KS, int RY, int RX, int LX, int LY, bool BWD, bool BA = false>
 __global__ __launch_bounds__(64 * WPB) void dwconv_lk_kernel(const T* __restrict__ a, const T* __restrict__ b,
                                                         const float* __restrict__ w_big,
                                                         const float* __restrict__ w_small,
@@ -150,6 +152,18 @@ __global__ __launch_bounds__(64 * WPB) void dwconv_lk_kernel(const T* __restrict
     __syncthreads();
     accumulate<K, 0, BWD, CF, RY, RX>(tile, wb, acc, ly, lx);
 
+    if constexpr (BA) {
+        static_assert(!BWD && KS == 0, "bias + activation: forward of the merged filter");
+        const float bias = w_small[c];
+        const bool relu = out1 != nullptr;
+#pragma unroll
+        for (int i = 0; i < RY; ++i)
+#pragma unroll
+            for (int j = 0; j < RX; ++j) {
+                acc[i][j] += bias;
+                if (relu) acc[i][j] = fmaxf(acc[i][j], 0.f);
+            }
+    }
     if constexpr (!BWD) {
         if (lane_ok) store_tile<T, RY, RX>(out0 + plane_off, acc, H, W, y0, x0, ly, lx);
         if constexpr (KS > 0) {
@@ -237,7 +251,7 @@ __global__ __launch_bounds__(256) void dwconv_wgrad_kernel(const float* __restri
 
 struct Shape { int N, C, H, W; };
 
-template <typename T, int K, int KS, int RY, int RX, int LX, int LY, bool BWD>
+template <typename T, int K, int KS, int RY, int RX, int LX, int LY, bool BWD, bool BA = false>
 int launch_cfg(const T* a, const T* b, const float* wb, const float* ws, T* o0, T* o1, Shape s,
                hipStream_t st) {
     using CF = Cfg<K, RY, RX, LX, LY>;
@@ -247,7 +261,7 @@ int launch_cfg(const T* a, const T* b, const float* wb, const float* ws, T* o0, 
     const long blocks = (n_items + WPB - 1) / WPB;
     const size_t lds = (size_t)WPB * CF::LDS_FLOATS * sizeof(float);
     static_assert(WPB * CF::LDS_FLOATS * sizeof(float) <= 64 * 1024, "LDS tile too large");
-    auto kern = dwconv_lk_kernel<T, K, KS, RY, RX, LX, LY, BWD>;
+    auto kern = dwconv_lk_kernel<T, K, KS, RY, RX, LX, LY, BWD, BA>;
     hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * WPB), lds, st, a, b, wb, ws, o0, o1, s.C, s.H,
                        s.W, tiles_x, tiles_y, n_items);
     return launch_status();
@@ -291,6 +305,33 @@ int dispatch(const T* a, const T* b, const float* wb, const float* ws, T* o0, T*
         default: break;
     }
     return PPEA_ERR_UNSUPPORTED;
+}
+
+#define PPEA_RUN_BA(K_, RY_, RX_, LX_, LY_)                                                     \
+    if (pick == idx++) return launch_cfg<T, K_, 0, RY_, RX_, LX_, LY_, false, true>(x, nullptr, w, bias, y, relu_tag, s, st);
+
+// y = act(DW_K(x; w) + bias[c]): the tuned tiles of `dispatch` with the bias / ReLU epilogue (K in 31 / 29 / 27 / 13)
+template <typename T>
+int dispatch_bias_act(const T* x, const float* w, const float* bias, int relu, T* y, Shape s, int K, hipStream_t st) {
+    T* relu_tag = relu ? y : nullptr;
+    long best = -1;
+    int pick = -1, idx = 0;
+    switch (K) {
+        case 31: { CFGS_31(PPEA_TRY) idx = 0; CFGS_31(PPEA_RUN_BA) break; }
+        case 29: { CFGS_29(PPEA_TRY) idx = 0; CFGS_29(PPEA_RUN_BA) break; }
+        case 27: { CFGS_27(PPEA_TRY) idx = 0; CFGS_27(PPEA_RUN_BA) break; }
+        case 13: { CFGS_13(PPEA_TRY) idx = 0; CFGS_13(PPEA_RUN_BA) break; }
+        default: break;
+    }
+    return PPEA_ERR_UNSUPPORTED;
+}
+
+template <typename T>
+int bias_act_impl(const void* x, const float* w, const float* bias, int relu, void* y, int N, int C, int H, int W, int K,
+                  void* stream) {
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return PPEA_ERR_UNSUPPORTED;
+    if (x == nullptr || w == nullptr || bias == nullptr || y == nullptr) return PPEA_ERR_ARG;
+    return dispatch_bias_act<T>((const T*)x, w, bias, relu, (T*)y, Shape{N, C, H, W}, K, (hipStream_t)stream);
 }
 
 template <typename T>
@@ -352,6 +393,18 @@ __global__ void timestamp_kernel(unsigned long long* slot) { *slot = wall_clock6
 }  // namespace
 
 extern "C" {
+
+// Inference: y = act(DW_K(x; w) + bias[c]) (relu != 0: ReLU) with fp32 filters w [C][K][K] -- the merged filter of an
+// eval-mode ReparamLargeKernelConv; fp32 or bf16 activations, fp32 arithmetic.  K in {31, 29, 27, 13}, else
+// PPEA_ERR_UNSUPPORTED.
+int ppea_dwconv_lk_fwd_bias_act_f32(const void* x, const float* w, const float* bias, int relu, void* y, int N, int C, int H,
+                                    int W, int K, void* stream) {
+    return bias_act_impl<float>(x, w, bias, relu, y, N, C, H, W, K, stream);
+}
+int ppea_dwconv_lk_fwd_bias_act_bf16(const void* x, const float* w, const float* bias, int relu, void* y, int N, int C, int H,
+                                     int W, int K, void* stream) {
+    return bias_act_impl<uint16_t>(x, w, bias, relu, y, N, C, H, W, K, stream);
+}
 
 int ppea_abi_version(void) { return PPEA_ABI_VERSION; }
 

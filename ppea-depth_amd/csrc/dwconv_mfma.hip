@@ -577,13 +577,24 @@ __device__ __forceinline__ void tile_stats(const f32x4& acc, const RowOffs& ro, 
 
 // MODE 0: fwd  (in0 = x; out0 = y_big, out1 = y_small if KS)
 // MODE 1: dgrad (in0 = dy_big, in1 = dy_small if KS; out0 = dx), filters flipped
-template <int K, int KS, int MODE, int NSEG, bool BN = false, bool WS = false>
+// BA (inference, ppea_dwconv_lk_fwd_bias_act_bf16p): y = act(conv + bias[c]) for the merged k x k filter of an eval-mode
+// ReparamLargeKernelConv.  The channel is uniform per wave: one bias scalar, applied where a finished tile's accumulator
+// is converted for the store, outside the MFMA stream.  The arguments ride in the (otherwise unused) BnIn parameter:
+// bn.beta = bias [C], bn.P != 0 = ReLU.
+__device__ __forceinline__ f32x4 bias_act4(f32x4 a, float b, bool relu) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { a[i] += b; if (relu) a[i] = fmaxf(a[i], 0.f); }
+    return a;
+}
+
+template <int K, int KS, int MODE, int NSEG, bool BN = false, bool WS = false, bool BA = false>
 __global__ __launch_bounds__(64 * WAVES, 1) void dwconv_mfma_kernel(
     const uint16_t* __restrict__ in0, const uint16_t* __restrict__ in1, const uint16_t* __restrict__ w_big,
     const uint16_t* __restrict__ w_small, uint16_t* __restrict__ out0, uint16_t* __restrict__ out1, int N, int C,
     int H, int W, int G, int band, int bands, int segs, int items_per_channel, int ipw, int wpc,
     long total_waves, int tile_bytes, int region_bytes, float* __restrict__ stats, BnIn bn) {
     static_assert(!BN || MODE == 0, "the fused input BatchNorm is a forward feature");
+    static_assert(!BA || (MODE == 0 && KS == 0 && !BN), "bias + activation: forward of the merged filter");
     using GE = Geo<K>;
     using GS = Geo<(KS > 0 ? KS : 5)>;
     constexpr int STRIDE_B = Seg<K, NSEG>::STRIDE;
@@ -624,6 +635,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void dwconv_mfma_kernel(
     // fused input BatchNorm: this channel's statistics from the producer's partial sums (bn_finalize_sums' arithmetic)
     float bn_a = 1.f, bn_o = 0.f;
     if constexpr (BN) bn_channel_affine(bn, c, lane, wid == (long)c * wpc, bn_a, bn_o);
+    float ba_bias = 0.f;
+    bool ba_relu = false;
+    if constexpr (BA) { ba_bias = bn.beta[c]; ba_relu = bn.P != 0; }
 
     uint8_t* tile1 = tile0 + tile_bytes;
     constexpr int SM_ROW0 = GE::P - GS::P;                  // small-kernel rows inside the big halo
@@ -718,6 +732,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void dwconv_mfma_kernel(
             auto store3 = [&](const f32x4 (&pb)[NS], const f32x4& ps, const RowOffs& ro, int xt) {
                 f32x4 acc = pb[0];
                 if constexpr (NS == 2) acc = pb[0] + pb[1];
+                if constexpr (BA) acc = bias_act4(acc, ba_bias, ba_relu);
                 store_tile(out0, acc, ro, W, xt, lane);
                 if constexpr (MODE == 0 && KS > 0) store_tile(out1, ps, ro, W, xt, lane);
                 if constexpr (MODE == 0) {
@@ -772,7 +787,8 @@ __global__ __launch_bounds__(64 * WAVES, 1) void dwconv_mfma_kernel(
         int xt_pend = 0;
         bool pend = false;
         auto epilogue = [&](const f32x4 (&pb)[2], const f32x4& ps) {
-            const f32x4 acc = pb[0] + pb[1];
+            f32x4 acc = pb[0] + pb[1];
+            if constexpr (BA) acc = bias_act4(acc, ba_bias, ba_relu);
             store_tile(out0, acc, ro_pend, W, xt_pend, lane);
             if constexpr (MODE == 0 && KS > 0) store_tile(out1, ps, ro_pend, W, xt_pend, lane);
             if constexpr (MODE == 0) {
@@ -1256,7 +1272,7 @@ int launch_bm_w(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, co
 
 // stats / wpc_out: forward only -- per-wave partial sums for the BatchNorm pair (see the kernel); wpc_out != nullptr:
 // do not launch, return the number of waves per channel (= partials per channel) the launch would use
-template <int K, int KS, int MODE, int NSEG, bool BN = false, bool WS = false>
+template <int K, int KS, int MODE, int NSEG, bool BN = false, bool WS = false, bool BA = false>
 int launch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0,
            uint16_t* o1, int N, int C, int H, int W, hipStream_t st, float* stats = nullptr, int* wpc_out = nullptr,
            const BnIn* bn = nullptr) {
@@ -1296,7 +1312,7 @@ int launch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const u
     if constexpr (WS) {
         if (!(G == 1 && band == 48 && H % 48 == 0)) return PPEA_ERR_UNSUPPORTED;       // every item: one 48-row band
     }
-    auto kern = dwconv_mfma_kernel<K, KS, MODE, NSEG, BN, WS>;
+    auto kern = dwconv_mfma_kernel<K, KS, MODE, NSEG, BN, WS, BA>;
     const BnIn bnv = bn != nullptr ? *bn : BnIn{nullptr, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static bool attr_done = false;
     if (!attr_done) {
@@ -1357,6 +1373,18 @@ int launch_k(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const
     return launch<K, KS, MODE, 2>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out);
 }
 
+// Merged filter + bias (+ ReLU), forward: the general kernel with the column-segment choice of launch_k.
+template <int K>
+int launch_bias_act(const uint16_t* x, const uint16_t* wb, uint16_t* y, const float* bias, int relu, int N, int C, int H,
+                    int W, hipStream_t st) {
+    const long c5 = staged_cols<K>(W, 5), c3 = staged_cols<K>(W, 3), c2 = staged_cols<K>(W, 2);
+    const int nseg = (c5 <= c3 && c5 <= c2) ? 5 : (c3 <= c2 ? 3 : 2);
+    const BnIn ba{nullptr, relu ? 1 : 0, 0.f, 0.f, 0.f, nullptr, bias, nullptr, nullptr, nullptr, nullptr};
+    if (nseg == 5) return launch<K, 0, 0, 5, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba);
+    if (nseg == 3) return launch<K, 0, 0, 3, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba);
+    return launch<K, 0, 0, 2, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba);
+}
+
 template <int MODE>
 int dispatch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0,
              uint16_t* o1, int N, int C, int H, int W, int K, int KS, hipStream_t st, float* stats = nullptr,
@@ -1404,6 +1432,24 @@ int ppea_dwconv_lk_fwd_bf16p(const uint16_t* x, const void* packed_big, const vo
     if (KS != 0 && KS != 5) return PPEA_ERR_UNSUPPORTED;
     return dispatch<0>(x, nullptr, (const uint16_t*)packed_big, (const uint16_t*)packed_small, y_big, y_small, N, C,
                        H, W, K, KS, (hipStream_t)stream);
+}
+
+// Inference: y = act(DW_k(x; merged filter) + bias[c]), relu != 0: ReLU -- an eval-mode ReparamLargeKernelConv + ReLU in one
+// launch (packed image of a_big W_k + pad(a_small W_5), bias = o_big + o_small).  K in {31, 29, 27, 13}; other shapes:
+// PPEA_ERR_UNSUPPORTED.
+int ppea_dwconv_lk_fwd_bias_act_bf16p(const uint16_t* x, const void* packed, const float* bias, int relu, uint16_t* y, int N,
+                                      int C, int H, int W, int K, void* stream) {
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return PPEA_ERR_UNSUPPORTED;
+    if (x == nullptr || packed == nullptr || bias == nullptr || y == nullptr) return PPEA_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const uint16_t* wb = (const uint16_t*)packed;
+    switch (K) {
+        case 31: return launch_bias_act<31>(x, wb, y, bias, relu, N, C, H, W, st);
+        case 29: return launch_bias_act<29>(x, wb, y, bias, relu, N, C, H, W, st);
+        case 27: return launch_bias_act<27>(x, wb, y, bias, relu, N, C, H, W, st);
+        case 13: return launch_bias_act<13>(x, wb, y, bias, relu, N, C, H, W, st);
+        default: return PPEA_ERR_UNSUPPORTED;
+    }
 }
 
 // Forward as above plus the statistics of the two BatchNorms that follow (rka.py:232-239): stats [2][C][P][2] fp32 =

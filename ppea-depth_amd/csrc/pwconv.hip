@@ -255,6 +255,16 @@ __global__ __launch_bounds__(256) void pwconv_kernel(const uint16_t* __restrict_
 // Requirements: K % BK == 0, HW % 8 == 0; TA: BM = 128, M % 8 == 0.
 constexpr int NSTAGE = 3;
 
+// EPI 5 (inference, eval-mode BatchNorm folded to a per-channel table; ppea_pwconv_infer_bf16):
+//     t = act(s[m] * acc + o[m])   Y = t (+ r1) (+ r2_scale * r2)   Y2 = s2[m] * Y + o2[m]  (Y as stored; Y2 optional)
+// Its arguments ride in a trailing kernel parameter that is an empty struct for every other epilogue.
+struct PwInfer {
+    const float* s; const float* o; const uint16_t* r1; const uint16_t* r2; float r2_scale;
+    const float* s2; const float* o2; int act;
+};
+template <int EPI> struct PwExtra {};
+template <> struct PwExtra<5> { PwInfer v; };
+
 template <int BK> __device__ __forceinline__ int a_swz16(int row) {
     return BK == 64 ? ((row >> 1) & 7) : (2 * ((row >> 2) & 1));
 }
@@ -264,7 +274,7 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
                                                       const void* __restrict__ bias, int bias_bf16,
                                                       const uint16_t* __restrict__ aux, uint16_t* __restrict__ Y,
                                                       uint16_t* __restrict__ Y2, int M, int K, int HW, int nb, int mtiles,
-                                                      int total) {
+                                                      int total, PwExtra<EPI> ex = {}) {
     constexpr int WM = BM >= 64 ? 2 : 1, WN = 4 / WM;
     constexpr int TM = BM / WM, TN = BN / WN, MT = TM / 16, NT = TN / 16;
     static_assert(!TA || BM == 128, "the transposed-A tile reuses the X tile's 256-byte-row layout");
@@ -405,6 +415,14 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
             bv = bias_bf16 ? bf2f(reinterpret_cast<const uint16_t*>(bias)[m]) : reinterpret_cast<const float*>(bias)[m];
         float st_s = 0.f, st_q = 0.f;
         uint2 v[NT], w[NT];
+        float sc = 1.f, sh = 0.f, sc2 = 0.f, sh2 = 0.f;              // EPI 5: this lane's channel of the tables
+        if constexpr (EPI == 5) {
+            if (m_ok) {
+                if (ex.v.s != nullptr) sc = ex.v.s[m];
+                if (ex.v.o != nullptr) sh = ex.v.o[m];
+                if (Y2 != nullptr) { sc2 = ex.v.s2[m]; sh2 = ex.v.o2[m]; }
+            }
+        }
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int p = p0 + wn * TN + 16 * j + 4 * g;
@@ -418,6 +436,24 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
                                        (uint16_t)(a.y >> 16)};
 #pragma unroll
                 for (int r = 0; r < 4; ++r) e[r] = f2bf(acc[i][j][r] * dgelu_f(bf2f(x[r])));
+            } else if constexpr (EPI == 5) {
+                uint2 a1 = make_uint2(0, 0), a2 = make_uint2(0, 0);
+                if (ok && ex.v.r1 != nullptr) a1 = *reinterpret_cast<const uint2*>(ex.v.r1 + o);
+                if (ok && ex.v.r2 != nullptr) a2 = *reinterpret_cast<const uint2*>(ex.v.r2 + o);
+                const uint16_t x1[4] = {(uint16_t)(a1.x & 0xffffu), (uint16_t)(a1.x >> 16), (uint16_t)(a1.y & 0xffffu),
+                                        (uint16_t)(a1.y >> 16)};
+                const uint16_t x2[4] = {(uint16_t)(a2.x & 0xffffu), (uint16_t)(a2.x >> 16), (uint16_t)(a2.y & 0xffffu),
+                                        (uint16_t)(a2.y >> 16)};
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    float t = fmaf(sc, acc[i][j][r], sh);
+                    if (ex.v.act == 1) t = fmaxf(t, 0.f);
+                    else if (ex.v.act == 2) t = gelu_f(t);
+                    t += bf2f(x1[r]);
+                    t = fmaf(ex.v.r2_scale, bf2f(x2[r]), t);
+                    e[r] = f2bf(t);
+                    f[r] = f2bf(fmaf(sc2, bf2f(e[r]), sh2));          // the next block's pre-BN of the tensor as stored
+                }
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -440,10 +476,11 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
             const int p = p0 + wn * TN + 16 * (j + (g & 1)) + 8 * (g >> 1);
             const long o = (long)n * M * HW + (long)m * HW + p;
             if (m_ok && p < HW) *reinterpret_cast<uint4*>(Y + o) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-            if constexpr (EPI == 1) {
+            if constexpr (EPI == 1 || EPI == 5) {
                 auto tx = __builtin_amdgcn_permlane16_swap(w[j].x, w[j + 1].x, false, false);
                 auto ty = __builtin_amdgcn_permlane16_swap(w[j].y, w[j + 1].y, false, false);
-                if (m_ok && p < HW) *reinterpret_cast<uint4*>(Y2 + o) = make_uint4(tx[0], ty[0], tx[1], ty[1]);
+                if (m_ok && p < HW && (EPI == 1 || Y2 != nullptr))
+                    *reinterpret_cast<uint4*>(Y2 + o) = make_uint4(tx[0], ty[0], tx[1], ty[1]);
             }
         }
         if constexpr (EPI == 4) {
@@ -499,7 +536,7 @@ PwCfg pw_choose(int B, int M, int K, int HW, bool ta) {
 
 template <int BM, int BK, int EPI, bool TA = false>
 int launch_pw2_t(const void* A, const void* X, const void* bias, int bias_bf16, const void* aux, void* Y, void* Y2, int B,
-                 int M, int K, int HW, hipStream_t st) {
+                 int M, int K, int HW, hipStream_t st, PwExtra<EPI> ex = {}) {
     constexpr int smem = NSTAGE * (BM * BK * 2 + BK * B_STRIDE);
     static bool ready = false;                                   // per instantiation
     auto kern = pwconv2_kernel<BM, BK, EPI, TA>;
@@ -512,7 +549,7 @@ int launch_pw2_t(const void* A, const void* X, const void* bias, int bias_bf16, 
     const long total = (long)nb * mtiles * B;
     if (total > 0x7fffffffL) return PPEA_ERR_UNSUPPORTED;
     hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256), smem, st, (const uint16_t*)A, (const uint16_t*)X, bias, bias_bf16,
-                       (const uint16_t*)aux, (uint16_t*)Y, (uint16_t*)Y2, M, K, HW, nb, mtiles, (int)total);
+                       (const uint16_t*)aux, (uint16_t*)Y, (uint16_t*)Y2, M, K, HW, nb, mtiles, (int)total, ex);
     return launch_status();
 }
 
@@ -605,6 +642,32 @@ int ppea_pwconv_ex_bf16(const void* A, const void* X, const void* bias, int bias
         }
     }
     return PPEA_ERR_ARG;
+}
+
+// Inference form of the 1x1 conv + BatchNorm (+ activation, residual, adapter add, next block's first BatchNorm) of the
+// trunk (replknet_adapter.py:270-326 in eval mode): the BatchNorm is a per-channel table (s, o) applied to the fp32
+// accumulator, so the weights stay the training model's bf16 matrices.
+//   t = act(s[m] * (A X)[m][p] + o[m])   act: 0 none, 1 ReLU, 2 GELU (erf);  s NULL = 1, o NULL = 0
+//   Y = t (+ r1[b][m][p]) (+ r2_scale * r2[b][m][p])                          r1 / r2 [B][M][HW] bf16 or NULL
+//   Y2 = s2[m] * Y + o2[m]   (of Y as stored in bf16)                         Y2 NULL: not written
+// Served by the LDS-DMA kernel only: K % 32 == 0, HW % 8 == 0, else PPEA_ERR_UNSUPPORTED.
+int ppea_pwconv_infer_bf16(const void* A, const void* X, const float* s, const float* o, int act, const void* r1,
+                           const void* r2, float r2_scale, const float* s2, const float* o2, void* Y, void* Y2, int B, int M,
+                           int K, int HW, void* stream) {
+    if (B <= 0 || M <= 0 || K <= 0 || HW <= 0 || (K % 32) != 0 || (HW % 8) != 0 || B > 65535)
+        return PPEA_ERR_UNSUPPORTED;
+    if (A == nullptr || X == nullptr || Y == nullptr || act < 0 || act > 2) return PPEA_ERR_ARG;
+    if (Y2 != nullptr && (s2 == nullptr || o2 == nullptr)) return PPEA_ERR_ARG;
+    const PwCfg c = pw_choose(B, M, K, HW, false);
+    if (!c.v2) return PPEA_ERR_UNSUPPORTED;
+    PwExtra<5> ex;
+    ex.v = PwInfer{s, o, (const uint16_t*)r1, (const uint16_t*)r2, r2_scale, s2, o2, act};
+    hipStream_t st = (hipStream_t)stream;
+#define PW2I(BM_, BK_) return launch_pw2_t<BM_, BK_, 5>(A, X, nullptr, 0, nullptr, Y, Y2, B, M, K, HW, st, ex)
+    if (c.bm == 128) { if (c.bk == 64) PW2I(128, 64); else PW2I(128, 32); }
+    if (c.bm == 64) { if (c.bk == 64) PW2I(64, 64); else PW2I(64, 32); }
+    PW2I(32, 64);
+#undef PW2I
 }
 
 }  // extern "C"

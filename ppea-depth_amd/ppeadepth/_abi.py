@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -36,6 +36,12 @@ SIGNATURES = {
     "ppea_dwconv_lk_fwd_bn_bf16p": [_vp] * 6 + [_i, _l, _vp, _vp, _f, _f] + [_vp] * 4 + [_i] * 6 + [_vp],
     "ppea_pwconv_bf16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "ppea_pwconv_ex_bf16": [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "ppea_dwconv_lk_fwd_bias_act_bf16p": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "ppea_dwconv_lk_fwd_bias_act_f32": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "ppea_dwconv_lk_fwd_bias_act_bf16": [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "ppea_dwconv3x3_fwd_affine_f32": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "ppea_dwconv3x3_fwd_affine_bf16": [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp],
+    "ppea_pwconv_infer_bf16": [_vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "ppea_pwgrad_workspace_bytes": [_i, _i, _i, _i],
     "ppea_pwgrad_bf16": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ppea_pwgrad_ex_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _i, _i, _vp],

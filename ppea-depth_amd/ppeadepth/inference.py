@@ -1,0 +1,480 @@
+"""Inference path: `DepthPredictor` walks a (live, possibly training-mode) `RepDepth` and launches the eval-mode schedule
+itself, with every eval BatchNorm folded into a per-channel table.
+
+In eval mode BatchNorm is y = s * x + o with s = gamma / sqrt(running_var + eps), o = beta - running_mean * s, known before
+the launch.  What folds where (reference: networks/replknet_adapter.py:182-326, 511-542):
+
+  * 1x1 conv + BN (+ ReLU / GELU) (+ residual + gamma * adapter) (+ the NEXT block's first BN as a second output):
+    the epilogue of the MFMA GEMM (`ppea_pwconv_infer_bf16`).  The table is applied to the fp32 accumulator, so the
+    predictor shares the training model's bf16 weight matrices: no second copy of the frozen parameters.
+  * large-kernel pair BN(DW_k) + BN(DW_5) + ReLU: ONE k x k depthwise launch with the merged filter
+    s_big W_k + pad(s_small W_5) (held by the predictor, packed for the MFMA depthwise kernel), bias o_big + o_small and the
+    ReLU in its epilogue (`ppea_dwconv_lk_fwd_bias_act_*`).
+  * depthwise 3x3 + BN + ReLU: one launch (`ppea_dwconv3x3_fwd_affine_*`).
+  * stem[0] / InputAdapter convs + BN (+ act): conv kernel + one `ppea_bn_apply_*` launch.
+  * stand-alone BNs (first block's prelkb_bn, `stages[s].norm`): one `ppea_bn_apply_*` launch with the constant table.
+  * pose ResNet-18: `ppea_nhwc_bn_apply_*` with the (a, b) table built from the running statistics.
+
+The predictor never replaces or deletes a module or parameter and never flips `model.training`.  Sub-modules WITHOUT
+BatchNorm, dropout or DropPath (adapters, depth decoders, pose decoder, reduce_conv) compute the same function in both
+modes and are called as they are.  `device="cpu"` runs the same schedule and the same tables with torch ops.
+"""
+import contextlib
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from .layers import transformation_from_parameters
+
+ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
+
+
+def _kernel_error(msg):
+    from ._abi import PpeaKernelError
+    return PpeaKernelError(msg)
+
+
+def _act(x, act):
+    return F.relu(x) if act == ACT_RELU else (F.gelu(x) if act == ACT_GELU else x)
+
+
+def bn_table(bn):
+    """(s, o) fp32 of an eval-mode BatchNorm: y = s * x + o."""
+    s = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+    return torch.stack([s, bn.bias.detach().float() - bn.running_mean.detach().float() * s])
+
+
+def merged_lk(lk):
+    """ReparamLargeKernelConv in eval mode as ONE k x k depthwise filter + bias (rka.py:250-261), from tables."""
+    tb, wb = bn_table(lk.lkb_origin.bn), lk.lkb_origin.conv.weight.detach().float()
+    w, bias = wb * tb[0].view(-1, 1, 1, 1), tb[1]
+    if hasattr(lk, "small_conv"):
+        ts, ws = bn_table(lk.small_conv.bn), lk.small_conv.conv.weight.detach().float()
+        p = (wb.shape[-1] - ws.shape[-1]) // 2
+        w = w + F.pad(ws * ts[0].view(-1, 1, 1, 1), [p] * 4)
+        bias = bias + ts[1]
+    return w.contiguous(), torch.stack([torch.ones_like(bias), bias])
+
+
+def cost_volume_cpu(cur, look, poses, K, inv_K, bins, eps=1e-7):
+    """torch composite of `ops.cost_volume` (replk_matching_adapter.py:261-340, one lookup frame): raw cost [B,D,h,w]."""
+    B, C, h, w = cur.shape
+    D = bins.shape[0]
+    ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
+    pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(h * w)], 0)
+    inner = torch.zeros(h, w)
+    inner[2:-2, 2:-2] = 1.0
+    out = []
+    for b in range(B):
+        if float(poses[b].sum()) == 0.0:
+            out.append(torch.zeros(D, h, w))
+            continue
+        rays = inv_K[b, :3, :3] @ pix
+        pts = torch.cat([bins.view(D, 1, 1) * rays[None], torch.ones(D, 1, h * w)], 1)
+        cam = (K[b] @ poses[b])[:3][None] @ pts
+        xy = cam[:, :2] / (cam[:, 2:3] + eps)
+        gx = ((xy[:, 0] / (w - 1)) - 0.5) * 2
+        gy = ((xy[:, 1] / (h - 1)) - 0.5) * 2
+        grid = torch.stack([gx, gy], -1).reshape(D, h, w, 2)
+        warped = F.grid_sample(look[b][None].expand(D, C, h, w), grid, mode="bilinear", padding_mode="zeros",
+                               align_corners=True)
+        xv, yv = (grid[..., 0] / 2 + 0.5) * (w - 1), (grid[..., 1] / 2 + 0.5) * (h - 1)
+        edge = ((xv >= 2.0) & (xv <= w - 2) & (yv >= 2.0) & (yv <= h - 2)).float()
+        diff = (warped - cur[b:b + 1]).abs().mean(1) * (edge * inner)
+        out.append(diff / ((diff > 0).float() + 1e-7))
+    return torch.stack(out)
+
+
+def cost_volume_reduce_cpu(raw, bins):
+    """torch composite of `ops.cost_volume_reduce`: (masked cost, confidence, argmin, lowest-cost 1/depth)."""
+    D = raw.shape[1]
+    missing = (raw == 0).float()
+    filled = raw * (1 - missing) + raw.max(1, keepdim=True)[0] * missing
+    conf = (((filled * (1 - missing)) > 0).sum(1) == D).float()
+    viz = torch.where(filled == 0, torch.full_like(filled, 100.0), filled)
+    idx = torch.min(viz, 1)[1]
+    return filled * conf.unsqueeze(1), conf, idx, 1.0 / bins[idx]
+
+
+class DepthPredictor:
+    def __init__(self, model, opt, amp_dtype=torch.bfloat16, device=None):
+        self.model = getattr(model, "module", model)
+        self.opt = opt
+        mdev = next(self.model.parameters()).device
+        self.device = torch.device(mdev if device is None else device)
+        self.cpu = self.device.type == "cpu"
+        if self.cpu:
+            amp_dtype = None
+            if mdev.type != "cpu":
+                raise _kernel_error("a device='cpu' predictor needs the model on the CPU")
+        elif mdev != self.device:
+            raise _kernel_error(f"model on {mdev}, predictor asked for {self.device}")
+        if amp_dtype not in (None, torch.bfloat16):
+            raise _kernel_error(f"amp_dtype {amp_dtype} is not served (bf16 or None = fp32)")
+        self.amp_dtype = amp_dtype
+        self.bf16 = amp_dtype == torch.bfloat16
+        if getattr(opt, "num_matching_frames", 1) != 1 or getattr(opt, "use_future_frame", False):
+            raise _kernel_error("the predictor serves one lookup frame (num_matching_frames = 1, no future frame)")
+        from .networks import replknet_adapter as rka
+        self._rka = rka
+        for enc in (self.model.encoder.replk, self.model.mono_encoder):
+            for m in enc.modules():
+                if isinstance(m, rka.ReparamLargeKernelConv):
+                    if not hasattr(m, "lkb_origin"):
+                        raise _kernel_error("structurally re-parameterised encoders are not served: build the predictor "
+                                            "from the training form")
+                    if not isinstance(m.lkb_origin.conv, rka.LargeKernelDW):
+                        raise _kernel_error("large-kernel branch is not a depthwise k x k conv with k > 5")
+        self.tab, self.lk, self.pose_ab = {}, {}, {}
+        self._graphs, self._unit = {}, {}
+        self.refresh()
+
+    # ---- tables ---------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def refresh(self):
+        """Rebuild every table and merged depthwise filter from the model's CURRENT weights and running statistics, in
+        place where the storage exists (a captured graph keeps reading the same buffers)."""
+        from .batchnorm import BatchNorm2d
+        rka = self._rka
+
+        def put(store, key, val):
+            old = store.get(key)
+            if old is not None and old.shape == val.shape:
+                old.copy_(val)
+            else:
+                store[key] = val.clone()
+
+        for enc in (self.model.encoder.replk, self.model.mono_encoder):
+            for m in enc.modules():
+                if isinstance(m, (BatchNorm2d, nn.BatchNorm2d)):
+                    put(self.tab, id(m), bn_table(m))
+                elif isinstance(m, rka.ReparamLargeKernelConv):
+                    w, tb = merged_lk(m)
+                    e = self.lk.setdefault(id(m), {})
+                    put(e, "w", w)
+                    put(e, "tab", tb)
+                    if self.bf16:
+                        self._pack(e)
+        for m in self.model.pose_encoder.modules():
+            if isinstance(m, nn.BatchNorm2d):
+                put(self.pose_ab, id(m), bn_table(m))
+
+    def _pack(self, e):
+        from . import _abi, ops
+        w = e["w"]
+        C, K = w.shape[0], w.shape[-1]
+        if K not in ops._MFMA_K:
+            e["packed"] = None
+            return
+        if e.get("packed") is None:
+            e["packed"] = torch.empty(_abi.lib.ppea_dwconv_lk_packed_bytes(C, K), dtype=torch.uint8, device=w.device)
+        _abi.call("ppea_dwconv_lk_pack_bf16", _abi.ptr(w), _abi.ptr(e["packed"]), C, K, 0, _abi.stream_ptr())
+
+    def _unit_vecs(self, C):
+        u = self._unit.get(C)
+        if u is None:
+            u = self._unit[C] = (torch.zeros(C, device=self.device), torch.ones(C, device=self.device))
+        return u
+
+    # ---- primitives -----------------------------------------------------------------------------------------------
+    def affine(self, x, tab, act=ACT_NONE, x2=None, tab2=None, r1=None, r2=None, r2_scale=1.0):
+        """act(s x + o [+ s2 x2 + o2]) (+ r1) (+ r2_scale r2), per-channel tables, NCHW."""
+        if self.cpu:
+            y = x * tab[0].view(1, -1, 1, 1) + tab[1].view(1, -1, 1, 1)
+            if x2 is not None:
+                y = y + (x2 * tab2[0].view(1, -1, 1, 1) + tab2[1].view(1, -1, 1, 1))
+            y = _act(y, act)
+            if r1 is not None:
+                y = y + r1
+            return y if r2 is None else y + r2_scale * r2
+        from . import ops
+        from ._abi import call, ptr, stream_ptr
+        x = x.contiguous()
+        N, C = x.shape[0], x.shape[1]
+        zero, one = self._unit_vecs(C)
+        st = (zero, tab[0], one, tab[1]) + ((zero, tab2[0], one, tab2[1]) if x2 is not None else (None,) * 4)
+        cast = lambda t: None if t is None else t.contiguous().to(x.dtype)       # noqa: E731
+        x2, r1, r2 = cast(x2), cast(r1), cast(r2)
+        y = torch.empty_like(x)
+        call(f"ppea_bn_apply_{ops._suffix(x)}", ptr(x), ptr(x2), ops._stats_array(st), None, ptr(r1), ptr(r2),
+             float(r2_scale), ptr(y), int(act), N, C, x.numel() // (N * C), stream_ptr())
+        return y
+
+    def pw(self, x, conv, tab, act=ACT_NONE, r1=None, r2=None, r2_scale=1.0, nxt=None):
+        """1x1 conv + table (+ act, residual, adapter add) -> (y, nxt table applied to y or None)."""
+        w = conv.weight
+        if not self.cpu and self.bf16:
+            from . import _abi, ops
+            B, K, H, W = x.shape
+            M = w.shape[0]
+            if x.dtype == torch.bfloat16 and K % 32 == 0 and (H * W) % 8 == 0:
+                a, _ = ops._pw_matrices(w)
+                x = x.contiguous()
+                y = torch.empty(B, M, H, W, device=x.device, dtype=torch.bfloat16)
+                y2 = torch.empty_like(y) if nxt is not None else None
+                cast = lambda t: None if t is None else t.contiguous().to(torch.bfloat16)       # noqa: E731
+                r1c, r2c = cast(r1), cast(r2)
+                p = _abi.ptr
+                err = _abi.lib.ppea_pwconv_infer_bf16(
+                    p(a), p(x), p(tab[0]), p(tab[1]), int(act), p(r1c), p(r2c), float(r2_scale),
+                    None if nxt is None else p(nxt[0]), None if nxt is None else p(nxt[1]), p(y), p(y2), B, M, K, H * W,
+                    _abi.stream_ptr())
+                if err == 0:
+                    return y, y2
+                if err != -1:
+                    _abi.check(err, "ppea_pwconv_infer_bf16")
+        if self.cpu:
+            z = F.conv2d(x, w)
+        else:
+            from . import ops
+            z = ops.conv2d_f32(x, w.detach())
+        y = self.affine(z, tab, act, r1=r1, r2=r2, r2_scale=r2_scale)
+        return y, (None if nxt is None else self.affine(y, nxt))
+
+    def dw_lk(self, x, lk):
+        """relu(BN(DW_k(x)) + BN(DW_5(x))) as one merged depthwise conv + bias + ReLU."""
+        e = self.lk[id(lk)]
+        w = e["w"]
+        if self.cpu:
+            return F.relu(F.conv2d(x, w, e["tab"][1], 1, w.shape[-1] // 2, 1, w.shape[0]))
+        from . import _abi, ops
+        x = x.contiguous()
+        N, C, H, W = x.shape
+        K = w.shape[-1]
+        y = torch.empty_like(x)
+        p = _abi.ptr
+        bias, st = e["tab"][1], _abi.stream_ptr()
+        err = -1
+        if x.dtype == torch.bfloat16 and e.get("packed") is not None:           # MFMA kernel, bias + ReLU in its epilogue
+            err = _abi.lib.ppea_dwconv_lk_fwd_bias_act_bf16p(p(x), p(e["packed"]), p(bias), 1, p(y), N, C, H, W, K, st)
+        if err == -1:                                                            # fp32-arithmetic kernel, same epilogue
+            err = getattr(_abi.lib, f"ppea_dwconv_lk_fwd_bias_act_{ops._suffix(x)}")(p(x), p(w), p(bias), 1, p(y), N, C, H, W,
+                                                                                    K, st)
+        if err == 0:
+            return y
+        if err != -1:
+            _abi.check(err, "ppea_dwconv_lk_fwd_bias_act")
+        # kernel sizes without a tuned tile: the one-thread-per-output kernel, then bias + ReLU as a table launch
+        _abi.call(f"ppea_dwconv_lk_fwd_{ops._suffix(x)}", p(x), p(w), None, p(y), None, N, C, H, W, K, 0, st)
+        return self.affine(y, e["tab"], ACT_RELU)
+
+    def conv_bn(self, x, seq, act):
+        """ConvBNAct with a dense or depthwise 3x3 conv (stem[0], stem[1], stem[3], transitions[.][1])."""
+        conv, tab = seq.conv, self.tab[id(seq.bn)]
+        if self.cpu:
+            return self.affine(F.conv2d(x, conv.weight, None, conv.stride, conv.padding, 1, conv.groups), tab, act)
+        from . import ops
+        rka = self._rka
+        if isinstance(conv, rka.SmallDW):
+            from . import _abi
+            x = x.contiguous()
+            N, C, H, W = x.shape
+            sd = conv.stride[0]
+            y = torch.empty(N, C, (H - 1) // sd + 1, (W - 1) // sd + 1, device=x.device, dtype=x.dtype)
+            wf = conv.weight.detach().float().contiguous()
+            err = getattr(_abi.lib, f"ppea_dwconv3x3_fwd_affine_{ops._suffix(x)}")(
+                _abi.ptr(x), _abi.ptr(wf), _abi.ptr(tab[0]), _abi.ptr(tab[1]), int(act == ACT_RELU), _abi.ptr(y), N, C, H, W, sd,
+                _abi.stream_ptr())
+            if err == 0 and act in (ACT_NONE, ACT_RELU):
+                return y
+            if err != -1:
+                _abi.check(err, "ppea_dwconv3x3_fwd_affine")
+            z = ops.dwconv3x3(x, conv.weight, sd)
+        elif conv.groups == 1:
+            z = ops.conv_module(conv, x, out_nchw=True) if isinstance(conv, rka.ImageConv) else None
+            if z is None:
+                z = ops.conv2d_f32(x if x.dtype != torch.float32 or not self.bf16 else x.to(torch.bfloat16),
+                                   conv.weight.detach(), None, conv.stride[0], conv.padding[0])
+        else:
+            raise _kernel_error(f"no inference kernel for conv {conv}")
+        return self.affine(z, tab, act)
+
+    def dense(self, x, conv):
+        """Dense conv with bias (InputAdapter) on this build's kernels."""
+        if self.cpu:
+            return F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding)
+        from . import ops
+        return ops.conv2d_f32(x, conv.weight.detach(), conv.bias, conv.stride[0], conv.padding[0])
+
+    # ---- RepLKNet trunk -------------------------------------------------------------------------------------------
+    def _stem(self, net, img):
+        x = self.conv_bn(img, net.stem[0], ACT_RELU)
+        adpt = None
+        if net.input_adpt:
+            ia = net.input_adapter
+            h = self.affine(self.dense(x, ia.D_fc1), self.tab[id(ia.bn1)], ACT_GELU)
+            adpt = self.affine(self.dense(h, ia.D_fc2), self.tab[id(ia.bn2)])
+        x = self.conv_bn(x, net.stem[1], ACT_RELU)
+        x, _ = self.pw(x, net.stem[2].conv, self.tab[id(net.stem[2].bn)], ACT_RELU)
+        x = self.conv_bn(x, net.stem[3], ACT_RELU)
+        return x if adpt is None else x + adpt
+
+    def _stage(self, net, s, x):
+        rka = self._rka
+        blocks = net.stages[s].blocks
+        pre = None
+        for i, blk in enumerate(blocks):
+            if pre is None:
+                pre = self.affine(x, self.tab[id(blk.pre_bn)])
+            nxt = self.tab[id(blocks[i + 1].pre_bn)] if i + 1 < len(blocks) else None
+            if isinstance(blk, rka.RepLKBlock):
+                adpt = blk.adapter(pre) if blk.test_id >= 0 else None
+                t, _ = self.pw(pre, blk.pw1.conv, self.tab[id(blk.pw1.bn)], ACT_RELU)
+                t = self.dw_lk(t, blk.large_kernel)
+            else:
+                adpt = blk.mlp_adapter(pre) if blk.test_id >= 0 else None
+                t, _ = self.pw(pre, blk.pw1.conv, self.tab[id(blk.pw1.bn)], ACT_GELU)
+            x, pre = self.pw(t, blk.pw2.conv, self.tab[id(blk.pw2.bn)], ACT_NONE, r1=x, r2=adpt, r2_scale=float(blk.gamma),
+                             nxt=nxt)
+        return x
+
+    def _norm(self, net, s, x):
+        n = net.stages[s].norm
+        return x if isinstance(n, nn.Identity) else self.affine(x, self.tab[id(n)])
+
+    def _transition(self, net, s, x):
+        tr = net.transitions[s]
+        x, _ = self.pw(x, tr[0].conv, self.tab[id(tr[0].bn)], ACT_RELU)
+        x = self.conv_bn(x, tr[1], ACT_RELU)
+        if net.trans_adpt:
+            x = x + net.trans_adpt[s](x)
+        return x
+
+    def _rest(self, net, x, feats, first):
+        for s in range(first, net.num_stages):
+            x = self._stage(net, s, x)
+            if s in net.out_indices:
+                feats.append(self._norm(net, s, x))
+            if s < net.num_stages - 1:
+                x = self._transition(net, s, x)
+        return feats
+
+    # ---- pose network ---------------------------------------------------------------------------------------------
+    def _pose_bn(self, x, bn, act, res=None):
+        ab = self.pose_ab[id(bn)]
+        if self.cpu:
+            y = x * ab[0].view(1, -1, 1, 1) + ab[1].view(1, -1, 1, 1)
+            return _act(y if res is None else y + res, act)
+        from . import ops
+        from ._abi import call, ptr, stream_ptr
+        if ops.nhwc_bn_supported(x) and (res is None or res.is_contiguous(memory_format=torch.channels_last)):
+            N, C, H, W = x.shape
+            y = torch.empty_like(x)
+            call(f"ppea_nhwc_bn_apply_{ops._suffix(x)}", ops._raw(x), ops._raw(res), ptr(ab), ops._raw(y), N * H * W, C, 1,
+                 int(act), stream_ptr())
+            return y
+        one = self._unit_vecs(x.shape[1])[1]
+        return self.affine(x, ab, act, x2=res, tab2=None if res is None else torch.stack([one, one * 0]))
+
+    def _pose(self, pair):
+        from .networks import resnet_encoder as rn
+        e = self.model.pose_encoder.encoder
+        if self.cpu:
+            conv = lambda c, x: c(x)                                   # noqa: E731
+            pool = lambda x: F.max_pool2d(x, 3, 2, 1)                  # noqa: E731
+            x = (pair - 0.45) / 0.225
+        else:
+            from . import ops
+            conv, pool = rn._conv, (lambda x: rn._maxpool(e.maxpool, x))
+            x = ops.image_to_nhwc(pair, 8, 0.45, 0.225) if self.bf16 else (pair - 0.45) / 0.225
+        x = pool(self._pose_bn(conv(e.conv1, x), e.bn1, ACT_RELU))
+        for layer in (e.layer1, e.layer2, e.layer3, e.layer4):
+            for blk in layer:
+                idt = x if blk.downsample is None else self._pose_bn(conv(blk.downsample[0], x), blk.downsample[1], ACT_NONE)
+                out = self._pose_bn(conv(blk.conv1, x), blk.bn1, ACT_RELU)
+                x = self._pose_bn(conv(blk.conv2, out), blk.bn2, ACT_RELU, idt)
+        axisangle, translation = self.model.pose([[x]])
+        return transformation_from_parameters(axisangle[:, 0].float(), translation[:, 0].float(), invert=True)
+
+    # ---- public ---------------------------------------------------------------------------------------------------
+    def _ctx(self):
+        return torch.autocast("cuda", dtype=self.amp_dtype) if self.bf16 else contextlib.nullcontext()
+
+    @torch.no_grad()
+    def _mono(self, color):
+        with self._ctx():
+            net = self.model.mono_encoder
+            feats = self._rest(net, self._stem(net, color), [], 0)
+            return self.model.mono_depth(feats)[("disp", 0)].float()
+
+    @torch.no_grad()
+    def _multi(self, color0, color_m1, K2, inv_K2, min_bin, max_bin):
+        with self._ctx():
+            enc = self.model.encoder
+            net = enc.replk
+            B = color0.shape[0]
+            pose = self._pose(torch.cat([color_m1, color0], 1))
+            mn = torch.as_tensor(min_bin, dtype=torch.float32, device=self.device).reshape(())
+            mx = torch.as_tensor(max_bin, dtype=torch.float32, device=self.device).reshape(())
+            bins = enc.compute_depth_bins(mn, mx, self.device)
+            # the current and the lookup frame share stem + stage 0 (eval BatchNorm is per sample): one 2B batch
+            x = self._stage(net, 0, self._stem(net, torch.cat([color0, color_m1], 0)))
+            feat0, look = self._norm(net, 0, x[:B]), x[B:]
+            if self.cpu:
+                raw = cost_volume_cpu(feat0, look, pose, K2.float(), inv_K2.float(), bins)
+                cost, _conf, _idx, lowest = cost_volume_reduce_cpu(raw, bins)
+                xr = enc.reduce_conv(torch.cat([feat0, cost], 1))
+            else:
+                from . import ops
+                raw = ops.cost_volume(feat0.contiguous(), look.contiguous(), pose, K2, inv_K2, bins)
+                cost, _conf, _idx, lowest = ops.cost_volume_reduce(raw, bins)
+                cat = torch.cat([feat0, cost.to(feat0.dtype)], 1)
+                xr = ops.conv_module(enc.reduce_conv[0], cat, "relu", out_nchw=True)
+                if xr is None:
+                    xr = F.relu(enc.reduce_conv[0](cat))
+            feats = self._rest(net, self._transition(net, 0, xr), [feat0], 1)
+            disp = self.model.depth(feats)[("disp", 0)].float()
+            return disp, lowest, pose
+
+    def predict_mono(self, color):
+        """Teacher: color [B,3,H,W] in [0,1] -> disparity [B,1,H,W] fp32."""
+        g = self._graphs.get(("mono", tuple(color.shape)))
+        if g is None:
+            return self._mono(color.to(self.device))
+        g["in"][0].copy_(color)
+        g["graph"].replay()
+        return g["out"].clone()
+
+    def predict(self, color0, color_m1, K2, inv_K2, min_bin, max_bin):
+        """Pose network -> cost volume -> multi-frame encoder -> decoder (as `Trainer.predict_disps`).
+        -> dict(disp [B,1,H,W], lowest_cost [B,h/4,w/4], pose [B,4,4])."""
+        g = self._graphs.get(("multi", tuple(color0.shape)))
+        if g is None:
+            d = self.device
+            out = self._multi(color0.to(d), color_m1.to(d), K2.to(d), inv_K2.to(d), min_bin, max_bin)
+        else:
+            mn = torch.as_tensor(min_bin, dtype=torch.float32).reshape(())
+            mx = torch.as_tensor(max_bin, dtype=torch.float32).reshape(())
+            for dst, src in zip(g["in"], (color0, color_m1, K2, inv_K2, mn, mx)):
+                dst.copy_(src)
+            g["graph"].replay()
+            out = tuple(t.clone() for t in g["out"])
+        return {"disp": out[0], "lowest_cost": out[1], "pose": out[2]}
+
+    def capture(self, B, mono=True, multi=True):
+        """torch.cuda.graph over static buffers for batch B at (opt.height, opt.width); predict* then replay."""
+        if self.cpu:
+            raise _kernel_error("capture needs a HIP device")
+        H, W, d = self.opt.height, self.opt.width, self.device
+        img = lambda: torch.rand(B, 3, H, W, device=d)                  # noqa: E731
+        eye = torch.eye(4, device=d).repeat(B, 1, 1)
+        jobs = []
+        if mono:
+            jobs.append(("mono", [img()], lambda i: self._mono(i[0])))
+        if multi:
+            ins = [img(), img(), eye.clone(), eye.clone(), torch.tensor(0.1, device=d), torch.tensor(10.0, device=d)]
+            jobs.append(("multi", ins, lambda i: self._multi(*i)))
+        for name, ins, fn in jobs:
+            side = torch.cuda.Stream(d)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):                                      # warm-up: caches, lazy kernel attributes
+                    fn(ins)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                out = fn(ins)
+            self._graphs[(name, (B, 3, H, W))] = {"graph": graph, "in": ins, "out": out}
+        return self

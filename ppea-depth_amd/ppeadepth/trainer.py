@@ -169,13 +169,26 @@ class Trainer:
 
     # ---- trainer.py:653-857 -----------------------------------------------------------------------
     @torch.no_grad()
-    def predict_disps(self, data, mono=True):
+    def predict_disps(self, data, mono=True, predictor=None):
         """Inference path of `val` for one batch (trainer.py:676-752): pose of the lookup frame from the pose network,
         cost volume + multi-frame encoder + decoder, optionally the single-frame teacher; model in eval mode.
-        -> (scaled multi-frame disparity [B,H,W], scaled teacher disparity or None), as `disp_to_depth(., 1e-3, 80)`."""
+        -> (scaled multi-frame disparity [B,H,W], scaled teacher disparity or None), as `disp_to_depth(., 1e-3, 80)`.
+        predictor: an `inference.DepthPredictor` of this model -- the same outputs from its fused schedule."""
         from .layers import transformation_from_parameters
         model = self._module()
         dev = self.device
+        if predictor is not None:
+            tracker = self.depth_bin_tracker
+            mn, mx = ((tracker.min_depth, tracker.max_depth) if getattr(self.opt, "notadabins", False)
+                      else tracker.compute())
+            r = predictor.predict(data[("color", 0, 0)], data[("color", -1, 0)], data[("K", 2)], data[("inv_K", 2)], mn, mx)
+            data[("relative_pose", -1)] = r["pose"]
+            pred, _ = disp_to_depth(r["disp"], MIN_VAL_EVAL, 80)
+            pred_mono = None
+            if mono:
+                pred_mono, _ = disp_to_depth(predictor.predict_mono(data[("color", 0, 0)]), MIN_VAL_EVAL, self.opt.max_depth)
+                pred_mono = pred_mono[:, 0]
+            return pred[:, 0], pred_mono
         ctx = torch.autocast("cuda", dtype=self.amp_dtype) if self.amp_dtype is not None else contextlib.nullcontext()
         color = {f: data[("color", f, 0)].to(dev) for f in (0, -1)}
         with ctx:
@@ -199,7 +212,7 @@ class Trainer:
                 pred_mono = pred_mono[:, 0]
         return pred[:, 0], pred_mono
 
-    def val(self, batches, gt_depths, eval_split="eigen", hard_test_mono=False, median_scaling=None):
+    def val(self, batches, gt_depths, eval_split="eigen", hard_test_mono=False, median_scaling=None, predictor=None):
         """`Trainer.val` (trainer.py:653-857) over an iterable of row-P batches and the split's ground-truth depth
         maps (`gt_depths.npz["data"]`, trainer.py:766-767): mean of (abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3) for
         the multi-frame network and, unless the teacher is frozen, for the teacher."""
@@ -212,7 +225,7 @@ class Trainer:
         disps, disps_mono = [], []
         try:
             for data in batches:
-                d, dm = self.predict_disps(data, mono_flag)
+                d, dm = self.predict_disps(data, mono_flag, predictor)
                 disps.append(d.cpu().numpy())
                 if mono_flag:
                     disps_mono.append(dm.cpu().numpy())
