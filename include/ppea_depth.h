@@ -560,6 +560,25 @@ int ppea_cost_volume_reduce_f32(const float* cost, const float* bins, float* cos
                                 int B, int D, int h, int w, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Depth errors of one validation batch (trainer.py:780-843, evaluate_depth.py:35-54): resize the predicted disparity to the
+ * ground-truth size, 1 / x, scale factor, crop + validity mask, median scaling, clamp to [1e-3, 80], the 7 errors.
+ *   pred_disp [B,h,w] fp32 = disp_to_depth-scaled disparity; gt = flat fp32 buffer of gt_len values holding ragged
+ *   ground-truth maps; table [B][3] int64 = (offset into gt, H_gt, W_gt) of each image of the batch;
+ *   mode 0: range test only, 1: eigen (Garg/Eigen crop), 2: cityscapes (first round(0.75 H) rows, window [256:, 192:1856]);
+ *   max_region >= the largest scored rectangle (rows x columns after the crop) of the batch: the workspace stride.  An image
+ *   whose table row does not fit gt_len / max_region, or with no valid pixel, gives NaN errors and count 0;
+ *   workspace: ppea_depth_errors_workspace_bytes(B, max_region) bytes, contents free before and after the call;
+ *   errors [B][7] fp64 (abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3), ratio [B] fp32 = median(gt) / median(pred) (applied
+ *   only if median_scaling), count [B] int32 = valid pixels.  One memset + 7 launches for any B; bitwise reproducible.
+ * ppea_depth_errors_mean_f64: mean [7] = mean over n rows of errors [n][7] (the split's result).
+ * ---------------------------------------------------------------------------------------- */
+long ppea_depth_errors_workspace_bytes(int B, long max_region);
+int ppea_depth_errors_f32(const float* pred_disp, const float* gt, long gt_len, const int64_t* table, void* workspace,
+                          double* errors, float* ratio, int32_t* count, int B, int h, int w, long max_region, int mode,
+                          int median_scaling, float scale, void* stream);
+int ppea_depth_errors_mean_f64(const double* errors, double* mean, int n, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training-mode BatchNorm (+ReLU, + residual added before the activation) on channels_last data: the ResNet-18 pose
  * trunk (networks/resnet_encoder.py:25-72).  The tensor is G consecutive sub-batches [G][P][C] (C contiguous,
  * C / 8 a power of two <= 256), each normalised with its own statistics (per-pair statistics of a 2B pose batch).

@@ -3,8 +3,11 @@
 Restates the reference's metric code: `compute_errors` (evaluate_depth.py:35-54) and the per-image protocol inside
 `Trainer.val` (trainer.py:780-835: resize the predicted disparity to the ground-truth size, Eigen crop, validity mask,
 median scaling, clamp to [1e-3, 80]).  `cv2.resize(..., INTER_LINEAR)` is bilinear with half-pixel centres and no
-antialiasing, i.e. `F.interpolate(mode="bilinear", align_corners=False)`.  Host-side numpy like the reference: the
-metric runs once per validation image on a few hundred thousand LiDAR points, not in the training step.
+antialiasing, i.e. `F.interpolate(mode="bilinear", align_corners=False)`.
+
+Two statements of the same protocol: host-side numpy like the reference (`evaluate_image`, `evaluate_disps`), and the
+device path (`DeviceGroundTruth`, `evaluate_disps_device`, `Trainer.val(metrics="device")`) that scores the disparities
+where the predictor left them, on `ops.depth_errors` (csrc/eval_metrics.hip), with one copy to the host per split.
 """
 import numpy as np
 import torch
@@ -79,3 +82,62 @@ def evaluate_disps(pred_disps, gt_depths, eval_split="eigen", median_scaling=Tru
     errors = [evaluate_image(pred_disps[i], gt_depths[i], eval_split, median_scaling, pred_depth_scale_factor)[0]
               for i in range(len(pred_disps))]
     return np.array(errors).mean(0)
+
+
+# ---- device path ---------------------------------------------------------------------------------------------------
+def region_size(eval_split, gt_height, gt_width):
+    """Rows x columns of the rectangle `evaluate_image` scores in a [gt_height, gt_width] map (the crop before the range
+    test): the stride of the device workspace.  Mirrors the slicing above and `region_of` in csrc/eval_metrics.hip."""
+    if eval_split == "eigen":
+        crop = np.array([0.40810811 * gt_height, 0.99189189 * gt_height,
+                         0.03594771 * gt_width, 0.96405229 * gt_width]).astype(np.int32)
+        return max(int(crop[1] - crop[0]), 0) * max(int(crop[3] - crop[2]), 0)
+    if eval_split == "cityscapes":
+        return max(int(round(gt_height * 0.75)) - 256, 0) * max(min(1856, gt_width) - 192, 0)
+    return gt_height * gt_width
+
+
+class DeviceGroundTruth:
+    """A split's ground-truth depth maps on the device, uploaded once and reusable across validations: one flat fp32
+    buffer (KITTI maps differ in size) and the per-image table (offset, H_gt, W_gt) `ops.depth_errors` reads."""
+
+    def __init__(self, gt_depths, device):
+        maps = [np.ascontiguousarray(g, dtype=np.float32) for g in gt_depths]
+        if not maps or any(m.ndim != 2 for m in maps):
+            raise ValueError("gt_depths: a non-empty sequence of [H,W] depth maps")
+        self.shapes = [m.shape for m in maps]
+        offsets = np.concatenate([[0], np.cumsum([m.size for m in maps])])
+        self.device = torch.device(device)
+        self.flat = torch.from_numpy(np.concatenate([m.reshape(-1) for m in maps])).to(self.device)
+        self.table = torch.tensor([[int(offsets[i]), h, w] for i, (h, w) in enumerate(self.shapes)],
+                                  dtype=torch.int64).to(self.device)
+
+    def __len__(self):
+        return len(self.shapes)
+
+    def max_region(self, eval_split, first=0, count=None):
+        last = len(self) if count is None else first + count
+        return max(region_size(eval_split, h, w) for h, w in self.shapes[first:last])
+
+    def score(self, pred_disps, first, eval_split="eigen", median_scaling=True, scale=1.0, out=None):
+        """Images [first, first + B) of the split against pred_disps [B,h,w] (device, fp32): `ops.depth_errors`."""
+        from . import ops
+        B = pred_disps.shape[0]
+        if first < 0 or first + B > len(self):
+            raise ops._abi.PpeaKernelError(f"images [{first}, {first + B}) are not in a split of {len(self)}")
+        return ops.depth_errors(pred_disps, self.flat, self.table[first:first + B], self.max_region(eval_split, first, B),
+                                eval_split, median_scaling, scale, out=out)
+
+
+def evaluate_disps_device(pred_disps, gt, eval_split="eigen", median_scaling=True, pred_depth_scale_factor=1.0, batch=16):
+    """`evaluate_disps` on the device: pred_disps [N,h,w] (device tensor, or numpy: uploaded), gt a `DeviceGroundTruth`
+    -> the 7 mean errors (numpy fp64).  Scored `batch` images at a time; one copy to the host."""
+    from . import ops
+    if not torch.is_tensor(pred_disps):
+        pred_disps = torch.from_numpy(np.ascontiguousarray(pred_disps)).to(gt.device)
+    if pred_disps.shape[0] != len(gt):
+        raise ops._abi.PpeaKernelError(f"{pred_disps.shape[0]} predictions for a split of {len(gt)} images")
+    errors = torch.empty(len(gt), 7, device=pred_disps.device, dtype=torch.float64)
+    for i in range(0, len(gt), batch):
+        gt.score(pred_disps[i:i + batch], i, eval_split, median_scaling, pred_depth_scale_factor, out=errors[i:i + batch])
+    return ops.depth_errors_mean(errors).cpu().numpy()

@@ -518,6 +518,50 @@ def cost_volume_reduce(cost, bins):
 
 
 # ---------------------------------------------------------------------------------------------
+# Validation metric (trainer.py:780-843): the per-image error protocol on the device   (csrc/eval_metrics.hip)
+# ---------------------------------------------------------------------------------------------
+EVAL_MODES = {"eigen": 1, "cityscapes": 2}          # any other split name: the range test only (mode 0)
+
+
+@torch.no_grad()
+def depth_errors(pred_disp, gt, table, max_region, eval_split="eigen", median_scaling=True, scale=1.0, out=None):
+    """pred_disp [B,h,w] fp32 scaled disparity; gt flat fp32 ground truth; table [B,3] int64 (offset, H_gt, W_gt) of the
+    batch's images; max_region >= the largest cropped rectangle of the batch (evaluate.region_size).
+    -> (errors [B,7] fp64, ratio [B] fp32, count [B] int32); `out`: a contiguous [B,7] fp64 tensor to write the errors to."""
+    if pred_disp.dim() != 3:
+        raise _abi.PpeaKernelError(f"expected a [B,h,w] disparity batch, got {tuple(pred_disp.shape)}")
+    B, h, w = pred_disp.shape
+    if table.dim() != 2 or tuple(table.shape) != (B, 3):
+        raise _abi.PpeaKernelError(f"ground-truth table {tuple(table.shape)} does not describe a batch of {B} images")
+    if gt.dim() != 1:
+        raise _abi.PpeaKernelError("the ground truth is one flat buffer")
+    dev = pred_disp.device
+    p, g, t = ptr(pred_disp, _F32), ptr(gt, _F32), ptr(table, torch.int64)
+    errors = torch.empty(B, 7, device=dev, dtype=torch.float64) if out is None else out
+    if tuple(errors.shape) != (B, 7):
+        raise _abi.PpeaKernelError(f"errors output {tuple(errors.shape)} != {(B, 7)}")
+    ratio = torch.empty(B, device=dev, dtype=_F32)
+    count = torch.empty(B, device=dev, dtype=torch.int32)
+    nbytes = _abi.lib.ppea_depth_errors_workspace_bytes(B, int(max_region))
+    if nbytes < 0:
+        _abi.check(int(nbytes), "ppea_depth_errors_workspace_bytes")
+    ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    call("ppea_depth_errors_f32", p, g, gt.numel(), t, ptr(ws), ptr(errors, torch.float64), ptr(ratio), ptr(count), B, h, w,
+         int(max_region), EVAL_MODES.get(eval_split, 0), int(bool(median_scaling)), float(scale), stream_ptr())
+    return errors, ratio, count
+
+
+@torch.no_grad()
+def depth_errors_mean(errors):
+    """errors [N,7] fp64 -> their mean over the split [7] fp64, on the device."""
+    if errors.dim() != 2 or errors.shape[1] != 7 or errors.shape[0] == 0:
+        raise _abi.PpeaKernelError(f"expected [N,7] errors, got {tuple(errors.shape)}")
+    mean = torch.empty(7, device=errors.device, dtype=torch.float64)
+    call("ppea_depth_errors_mean_f64", ptr(errors, torch.float64), ptr(mean), errors.shape[0], stream_ptr())
+    return mean
+
+
+# ---------------------------------------------------------------------------------------------
 # A2 + block glue: y = act(BN_a(z1) [+ BN_b(z2)]) [* mask[n]] [+ r1] [+ s * r2]   (csrc/bn_fused.hip)
 # ---------------------------------------------------------------------------------------------
 import ctypes as _ct

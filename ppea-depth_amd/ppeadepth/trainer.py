@@ -212,16 +212,48 @@ class Trainer:
                 pred_mono = pred_mono[:, 0]
         return pred[:, 0], pred_mono
 
-    def val(self, batches, gt_depths, eval_split="eigen", hard_test_mono=False, median_scaling=None, predictor=None):
+    def val(self, batches, gt_depths, eval_split="eigen", hard_test_mono=False, median_scaling=None, predictor=None,
+            metrics="host"):
         """`Trainer.val` (trainer.py:653-857) over an iterable of row-P batches and the split's ground-truth depth
         maps (`gt_depths.npz["data"]`, trainer.py:766-767): mean of (abs_rel, sq_rel, rmse, rmse_log, a1, a2, a3) for
-        the multi-frame network and, unless the teacher is frozen, for the teacher."""
+        the multi-frame network and, unless the teacher is frozen, for the teacher.
+        metrics="host": the reference's numpy protocol on disparities copied to the host per batch;
+        metrics="device": every batch is scored where it was predicted (`evaluate.DeviceGroundTruth.score`), the mean over
+        the split is taken on the device and one copy brings the result back; `gt_depths` may then also be a
+        `DeviceGroundTruth` uploaded earlier."""
         import numpy as np
         from . import evaluate
+        if metrics not in ("host", "device"):
+            raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
         model = self._module()
         was_training = model.training
         model.eval()
         mono_flag = (not self.freeze_tp) or hard_test_mono
+        # trainer.py:818-822: `--pred_depth_scale_factor`, `--disable_median_scaling` (the teacher is always median-scaled
+        # and never takes the scale factor, trainer.py:838-842)
+        scale = float(getattr(self.opt, "pred_depth_scale_factor", 1.0))
+        if median_scaling is None:
+            median_scaling = not getattr(self.opt, "disable_median_scaling", False)
+        if metrics == "device":
+            gt = gt_depths
+            if not isinstance(gt, evaluate.DeviceGroundTruth):
+                gt = evaluate.DeviceGroundTruth(gt_depths, self.device)
+            errors = torch.empty(1 + int(mono_flag), len(gt), 7, device=self.device, dtype=torch.float64)
+            first = 0
+            try:
+                for data in batches:
+                    d, dm = self.predict_disps(data, mono_flag, predictor)
+                    B = d.shape[0]
+                    gt.score(d.float().contiguous(), first, eval_split, median_scaling, scale, out=errors[0, first:first + B])
+                    if mono_flag:
+                        gt.score(dm.float().contiguous(), first, eval_split, True, 1.0, out=errors[1, first:first + B])
+                    first += B
+            finally:
+                model.train(was_training)
+            if first != len(gt):
+                raise ValueError(f"{first} predictions for a split of {len(gt)} ground-truth maps")
+            means = torch.stack([ops.depth_errors_mean(e) for e in errors]).cpu().numpy()
+            return (means[0], means[1]) if mono_flag else means[0]
         disps, disps_mono = [], []
         try:
             for data in batches:
@@ -232,11 +264,6 @@ class Trainer:
         finally:
             model.train(was_training)
         disps = np.concatenate(disps)
-        # trainer.py:818-822: `--pred_depth_scale_factor`, `--disable_median_scaling` (the teacher is always median-scaled
-        # and never takes the scale factor, trainer.py:838-842)
-        scale = float(getattr(self.opt, "pred_depth_scale_factor", 1.0))
-        if median_scaling is None:
-            median_scaling = not getattr(self.opt, "disable_median_scaling", False)
         mean_errors = evaluate.evaluate_disps(disps, gt_depths, eval_split, median_scaling, scale)
         if mono_flag:
             return mean_errors, evaluate.evaluate_disps(np.concatenate(disps_mono), gt_depths, eval_split, True)
