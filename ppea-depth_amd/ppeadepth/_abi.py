@@ -228,3 +228,12 @@ def check(err, name):
 
 def call(name, *args):
     check(getattr(lib, name)(*args), name)
+
+
+def try_call(name, *args):
+    """One rung of a kernel ladder: True when the entry point ran, False when it does not serve this argument
+    combination (-1: the caller tries its next kernel); any other status raises."""
+    err = getattr(lib, name)(*args)
+    if err != -1:
+        check(err, name)
+    return err != -1

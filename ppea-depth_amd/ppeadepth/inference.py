@@ -25,14 +25,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import ops
+from ._abi import PpeaKernelError
 from .layers import transformation_from_parameters
-
-ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
-
-
-def _kernel_error(msg):
-    from ._abi import PpeaKernelError
-    return PpeaKernelError(msg)
+from .ops import ACT_GELU, ACT_NONE, ACT_RELU
 
 
 def _act(x, act):
@@ -107,27 +103,27 @@ class DepthPredictor:
         if self.cpu:
             amp_dtype = None
             if mdev.type != "cpu":
-                raise _kernel_error("a device='cpu' predictor needs the model on the CPU")
+                raise PpeaKernelError("a device='cpu' predictor needs the model on the CPU")
         elif mdev != self.device:
-            raise _kernel_error(f"model on {mdev}, predictor asked for {self.device}")
+            raise PpeaKernelError(f"model on {mdev}, predictor asked for {self.device}")
         if amp_dtype not in (None, torch.bfloat16):
-            raise _kernel_error(f"amp_dtype {amp_dtype} is not served (bf16 or None = fp32)")
+            raise PpeaKernelError(f"amp_dtype {amp_dtype} is not served (bf16 or None = fp32)")
         self.amp_dtype = amp_dtype
         self.bf16 = amp_dtype == torch.bfloat16
         if getattr(opt, "num_matching_frames", 1) != 1 or getattr(opt, "use_future_frame", False):
-            raise _kernel_error("the predictor serves one lookup frame (num_matching_frames = 1, no future frame)")
+            raise PpeaKernelError("the predictor serves one lookup frame (num_matching_frames = 1, no future frame)")
         from .networks import replknet_adapter as rka
         self._rka = rka
         for enc in (self.model.encoder.replk, self.model.mono_encoder):
             for m in enc.modules():
                 if isinstance(m, rka.ReparamLargeKernelConv):
                     if not hasattr(m, "lkb_origin"):
-                        raise _kernel_error("structurally re-parameterised encoders are not served: build the predictor "
-                                            "from the training form")
+                        raise PpeaKernelError("structurally re-parameterised encoders are not served: build the predictor "
+                                              "from the training form")
                     if not isinstance(m.lkb_origin.conv, rka.LargeKernelDW):
-                        raise _kernel_error("large-kernel branch is not a depthwise k x k conv with k > 5")
+                        raise PpeaKernelError("large-kernel branch is not a depthwise k x k conv with k > 5")
         self.tab, self.lk, self.pose_ab = {}, {}, {}
-        self._graphs, self._unit = {}, {}
+        self._graphs = {}
         self.refresh()
 
     # ---- tables ---------------------------------------------------------------------------------------------------
@@ -154,28 +150,12 @@ class DepthPredictor:
                     e = self.lk.setdefault(id(m), {})
                     put(e, "w", w)
                     put(e, "tab", tb)
-                    if self.bf16:
-                        self._pack(e)
+                    if self.bf16:         # packed in place: a captured graph keeps reading the same buffer
+                        e["packed"] = (ops.pack_dwconv_filter(e["w"], False, out=e.get("packed"))
+                                       if ops.dwconv_lk_packed_supported(w.shape[-1]) else None)
         for m in self.model.pose_encoder.modules():
             if isinstance(m, nn.BatchNorm2d):
                 put(self.pose_ab, id(m), bn_table(m))
-
-    def _pack(self, e):
-        from . import _abi, ops
-        w = e["w"]
-        C, K = w.shape[0], w.shape[-1]
-        if K not in ops._MFMA_K:
-            e["packed"] = None
-            return
-        if e.get("packed") is None:
-            e["packed"] = torch.empty(_abi.lib.ppea_dwconv_lk_packed_bytes(C, K), dtype=torch.uint8, device=w.device)
-        _abi.call("ppea_dwconv_lk_pack_bf16", _abi.ptr(w), _abi.ptr(e["packed"]), C, K, 0, _abi.stream_ptr())
-
-    def _unit_vecs(self, C):
-        u = self._unit.get(C)
-        if u is None:
-            u = self._unit[C] = (torch.zeros(C, device=self.device), torch.ones(C, device=self.device))
-        return u
 
     # ---- primitives -----------------------------------------------------------------------------------------------
     def affine(self, x, tab, act=ACT_NONE, x2=None, tab2=None, r1=None, r2=None, r2_scale=1.0):
@@ -188,47 +168,16 @@ class DepthPredictor:
             if r1 is not None:
                 y = y + r1
             return y if r2 is None else y + r2_scale * r2
-        from . import ops
-        from ._abi import call, ptr, stream_ptr
-        x = x.contiguous()
-        N, C = x.shape[0], x.shape[1]
-        zero, one = self._unit_vecs(C)
-        st = (zero, tab[0], one, tab[1]) + ((zero, tab2[0], one, tab2[1]) if x2 is not None else (None,) * 4)
-        cast = lambda t: None if t is None else t.contiguous().to(x.dtype)       # noqa: E731
-        x2, r1, r2 = cast(x2), cast(r1), cast(r2)
-        y = torch.empty_like(x)
-        call(f"ppea_bn_apply_{ops._suffix(x)}", ptr(x), ptr(x2), ops._stats_array(st), None, ptr(r1), ptr(r2),
-             float(r2_scale), ptr(y), int(act), N, C, x.numel() // (N * C), stream_ptr())
-        return y
+        return ops.table_affine(x, tab, act, x2, tab2, r1, r2, r2_scale)
 
     def pw(self, x, conv, tab, act=ACT_NONE, r1=None, r2=None, r2_scale=1.0, nxt=None):
         """1x1 conv + table (+ act, residual, adapter add) -> (y, nxt table applied to y or None)."""
         w = conv.weight
-        if not self.cpu and self.bf16:
-            from . import _abi, ops
-            B, K, H, W = x.shape
-            M = w.shape[0]
-            if x.dtype == torch.bfloat16 and K % 32 == 0 and (H * W) % 8 == 0:
-                a, _ = ops._pw_matrices(w)
-                x = x.contiguous()
-                y = torch.empty(B, M, H, W, device=x.device, dtype=torch.bfloat16)
-                y2 = torch.empty_like(y) if nxt is not None else None
-                cast = lambda t: None if t is None else t.contiguous().to(torch.bfloat16)       # noqa: E731
-                r1c, r2c = cast(r1), cast(r2)
-                p = _abi.ptr
-                err = _abi.lib.ppea_pwconv_infer_bf16(
-                    p(a), p(x), p(tab[0]), p(tab[1]), int(act), p(r1c), p(r2c), float(r2_scale),
-                    None if nxt is None else p(nxt[0]), None if nxt is None else p(nxt[1]), p(y), p(y2), B, M, K, H * W,
-                    _abi.stream_ptr())
-                if err == 0:
-                    return y, y2
-                if err != -1:
-                    _abi.check(err, "ppea_pwconv_infer_bf16")
-        if self.cpu:
-            z = F.conv2d(x, w)
-        else:
-            from . import ops
-            z = ops.conv2d_f32(x, w.detach())
+        if self.bf16 and x.shape[1] % 32 == 0 and (x.shape[2] * x.shape[3]) % 8 == 0:      # (bf16 x: the op checks)
+            out = ops.pwconv_table(x, w, tab, act, r1, r2, r2_scale, nxt)
+            if out is not None:
+                return out
+        z = F.conv2d(x, w) if self.cpu else ops.conv2d_f32(x, w.detach())
         y = self.affine(z, tab, act, r1=r1, r2=r2, r2_scale=r2_scale)
         return y, (None if nxt is None else self.affine(y, nxt))
 
@@ -238,63 +187,36 @@ class DepthPredictor:
         w = e["w"]
         if self.cpu:
             return F.relu(F.conv2d(x, w, e["tab"][1], 1, w.shape[-1] // 2, 1, w.shape[0]))
-        from . import _abi, ops
-        x = x.contiguous()
-        N, C, H, W = x.shape
-        K = w.shape[-1]
-        y = torch.empty_like(x)
-        p = _abi.ptr
-        bias, st = e["tab"][1], _abi.stream_ptr()
-        err = -1
-        if x.dtype == torch.bfloat16 and e.get("packed") is not None:           # MFMA kernel, bias + ReLU in its epilogue
-            err = _abi.lib.ppea_dwconv_lk_fwd_bias_act_bf16p(p(x), p(e["packed"]), p(bias), 1, p(y), N, C, H, W, K, st)
-        if err == -1:                                                            # fp32-arithmetic kernel, same epilogue
-            err = getattr(_abi.lib, f"ppea_dwconv_lk_fwd_bias_act_{ops._suffix(x)}")(p(x), p(w), p(bias), 1, p(y), N, C, H, W,
-                                                                                    K, st)
-        if err == 0:
+        y = ops.dwconv_lk_bias_act(x, w, e.get("packed"), e["tab"][1], True)   # bias + ReLU in the kernel's epilogue
+        if y is not None:
             return y
-        if err != -1:
-            _abi.check(err, "ppea_dwconv_lk_fwd_bias_act")
         # kernel sizes without a tuned tile: the one-thread-per-output kernel, then bias + ReLU as a table launch
-        _abi.call(f"ppea_dwconv_lk_fwd_{ops._suffix(x)}", p(x), p(w), None, p(y), None, N, C, H, W, K, 0, st)
-        return self.affine(y, e["tab"], ACT_RELU)
+        return self.affine(ops.dwconv_lk_plain(x, w), e["tab"], ACT_RELU)
 
     def conv_bn(self, x, seq, act):
         """ConvBNAct with a dense or depthwise 3x3 conv (stem[0], stem[1], stem[3], transitions[.][1])."""
         conv, tab = seq.conv, self.tab[id(seq.bn)]
         if self.cpu:
             return self.affine(F.conv2d(x, conv.weight, None, conv.stride, conv.padding, 1, conv.groups), tab, act)
-        from . import ops
         rka = self._rka
         if isinstance(conv, rka.SmallDW):
-            from . import _abi
-            x = x.contiguous()
-            N, C, H, W = x.shape
-            sd = conv.stride[0]
-            y = torch.empty(N, C, (H - 1) // sd + 1, (W - 1) // sd + 1, device=x.device, dtype=x.dtype)
-            wf = conv.weight.detach().float().contiguous()
-            err = getattr(_abi.lib, f"ppea_dwconv3x3_fwd_affine_{ops._suffix(x)}")(
-                _abi.ptr(x), _abi.ptr(wf), _abi.ptr(tab[0]), _abi.ptr(tab[1]), int(act == ACT_RELU), _abi.ptr(y), N, C, H, W, sd,
-                _abi.stream_ptr())
-            if err == 0 and act in (ACT_NONE, ACT_RELU):
+            y = ops.dwconv3x3_affine(x, conv.weight, tab, act == ACT_RELU, conv.stride[0]) if act != ACT_GELU else None
+            if y is not None:
                 return y
-            if err != -1:
-                _abi.check(err, "ppea_dwconv3x3_fwd_affine")
-            z = ops.dwconv3x3(x, conv.weight, sd)
+            z = ops.dwconv3x3(x, conv.weight, conv.stride[0])
         elif conv.groups == 1:
             z = ops.conv_module(conv, x, out_nchw=True) if isinstance(conv, rka.ImageConv) else None
             if z is None:
                 z = ops.conv2d_f32(x if x.dtype != torch.float32 or not self.bf16 else x.to(torch.bfloat16),
                                    conv.weight.detach(), None, conv.stride[0], conv.padding[0])
         else:
-            raise _kernel_error(f"no inference kernel for conv {conv}")
+            raise PpeaKernelError(f"no inference kernel for conv {conv}")
         return self.affine(z, tab, act)
 
     def dense(self, x, conv):
         """Dense conv with bias (InputAdapter) on this build's kernels."""
         if self.cpu:
             return F.conv2d(x, conv.weight, conv.bias, conv.stride, conv.padding)
-        from . import ops
         return ops.conv2d_f32(x, conv.weight.detach(), conv.bias, conv.stride[0], conv.padding[0])
 
     # ---- RepLKNet trunk -------------------------------------------------------------------------------------------
@@ -356,15 +278,10 @@ class DepthPredictor:
         if self.cpu:
             y = x * ab[0].view(1, -1, 1, 1) + ab[1].view(1, -1, 1, 1)
             return _act(y if res is None else y + res, act)
-        from . import ops
-        from ._abi import call, ptr, stream_ptr
-        if ops.nhwc_bn_supported(x) and (res is None or res.is_contiguous(memory_format=torch.channels_last)):
-            N, C, H, W = x.shape
-            y = torch.empty_like(x)
-            call(f"ppea_nhwc_bn_apply_{ops._suffix(x)}", ops._raw(x), ops._raw(res), ptr(ab), ops._raw(y), N * H * W, C, 1,
-                 int(act), stream_ptr())
+        y = ops.nhwc_table_affine(x, ab, act, res)
+        if y is not None:
             return y
-        one = self._unit_vecs(x.shape[1])[1]
+        one = ops.unit_vecs(x.shape[1], x.device)[1]
         return self.affine(x, ab, act, x2=res, tab2=None if res is None else torch.stack([one, one * 0]))
 
     def _pose(self, pair):
@@ -375,7 +292,6 @@ class DepthPredictor:
             pool = lambda x: F.max_pool2d(x, 3, 2, 1)                  # noqa: E731
             x = (pair - 0.45) / 0.225
         else:
-            from . import ops
             conv, pool = rn._conv, (lambda x: rn._maxpool(e.maxpool, x))
             x = ops.image_to_nhwc(pair, 8, 0.45, 0.225) if self.bf16 else (pair - 0.45) / 0.225
         x = pool(self._pose_bn(conv(e.conv1, x), e.bn1, ACT_RELU))
@@ -416,7 +332,6 @@ class DepthPredictor:
                 cost, _conf, _idx, lowest = cost_volume_reduce_cpu(raw, bins)
                 xr = enc.reduce_conv(torch.cat([feat0, cost], 1))
             else:
-                from . import ops
                 raw = ops.cost_volume(feat0.contiguous(), look.contiguous(), pose, K2, inv_K2, bins)
                 cost, _conf, _idx, lowest = ops.cost_volume_reduce(raw, bins)
                 cat = torch.cat([feat0, cost.to(feat0.dtype)], 1)
@@ -455,7 +370,7 @@ class DepthPredictor:
     def capture(self, B, mono=True, multi=True):
         """torch.cuda.graph over static buffers for batch B at (opt.height, opt.width); predict* then replay."""
         if self.cpu:
-            raise _kernel_error("capture needs a HIP device")
+            raise PpeaKernelError("capture needs a HIP device")
         H, W, d = self.opt.height, self.opt.width, self.device
         img = lambda: torch.rand(B, 3, H, W, device=d)                  # noqa: E731
         eye = torch.eye(4, device=d).repeat(B, 1, 1)

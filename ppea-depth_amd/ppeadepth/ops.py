@@ -8,7 +8,7 @@ import weakref
 import torch
 
 from . import _abi
-from ._abi import call, ptr, stream_ptr
+from ._abi import call, ptr, stream_ptr, try_call
 
 _F32 = torch.float32
 _BF16 = torch.bfloat16
@@ -42,32 +42,50 @@ def _suffix(t):
 
 
 # ---------------------------------------------------------------------------------------------
-# packed bf16 filter images for the MFMA depthwise kernel, cached per (weight storage, version, flip)
+# kernel-layout images of weights (packed filters, bf16 matrices), one cache for all of them
 # ---------------------------------------------------------------------------------------------
-_PACK_CACHE = {}
+_WEIGHT_IMAGES = {}
+
+
+def _weight_image(w, tag, build, cache_trainable=False):
+    """build(w), kept per weight OBJECT and `tag` (the kind of image).  An entry is keyed by the tensor object through a
+    weak reference, not by its address (a freed weight's address can be handed to another model's weight), holds while
+    the weight's version counter and shape are the recorded ones, and leaves with the weight.
+    Policy: a trainable weight is updated by the flat Adam kernel through raw pointers, which does not bump the version
+    counter, so the conv and depthwise packers build its image on every use (the pack launch is then part of the captured
+    step as well).  `cache_trainable`: `_pw_matrices`, which is only ever given frozen 1x1 weights, caches what it gets."""
+    if w.requires_grad and not cache_trainable:
+        return build(w)
+    key = (id(w), tag)
+    hit = _WEIGHT_IMAGES.get(key)
+    if hit is not None and hit[0]() is w and hit[1] == w._version and hit[2] == w.shape:
+        return hit[3]
+    image = build(w)
+    _WEIGHT_IMAGES[key] = (weakref.ref(w, lambda _r: _WEIGHT_IMAGES.pop(key, None)), w._version, w.shape, image)
+    return image
+
+
 _MFMA_K = (31, 29, 27, 13)
 
 
-def _packed_filter(w, flip):
-    """uint8 buffer with the bf16 Toeplitz source image of w [C,1,K,K]; rebuilt when w changes in place.
-    Keyed by the tensor object (weak reference), not by its address: a freed weight's address can be handed to
-    another model's weight."""
-    key = (id(w), int(flip))
-    ver = w._version
-    # A trainable filter (--fullft_reb) is updated by the flat Adam kernel through raw pointers, which does not
-    # bump `_version`: pack it on every use (the pack launch is then part of the captured step as well).
-    cacheable = not w.requires_grad
-    hit = _PACK_CACHE.get(key) if cacheable else None
-    if hit is not None and hit[3]() is w and hit[0] == ver and hit[2] == tuple(w.shape):
-        return hit[1]
+def dwconv_lk_packed_supported(K):
+    """The MFMA depthwise kernels (the ones that read a packed filter image) serve this kernel size."""
+    return K in _MFMA_K
+
+
+def pack_dwconv_filter(w, flip, out=None):
+    """uint8 buffer with the bf16 Toeplitz source image of w [C,1,K,K] for the MFMA depthwise kernels (flip: the
+    data-gradient image).  `out`: a buffer of an earlier call to rewrite in place (a captured graph keeps reading it)."""
     C, K = w.shape[0], w.shape[-1]
-    nbytes = _abi.lib.ppea_dwconv_lk_packed_bytes(C, K)
-    buf = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    if out is None:
+        out = torch.empty(_abi.lib.ppea_dwconv_lk_packed_bytes(C, K), dtype=torch.uint8, device=w.device)
     wf = w.detach().to(_F32).contiguous()
-    call("ppea_dwconv_lk_pack_bf16", ptr(wf), ptr(buf), C, K, int(flip), stream_ptr())
-    if cacheable:
-        _PACK_CACHE[key] = (ver, buf, tuple(w.shape), weakref.ref(w, lambda _r, k=key: _PACK_CACHE.pop(k, None)))
-    return buf
+    call("ppea_dwconv_lk_pack_bf16", ptr(wf), ptr(out), C, K, int(flip), stream_ptr())
+    return out
+
+
+def _packed_filter(w, flip):
+    return _weight_image(w, ("dw", bool(flip)), lambda t: pack_dwconv_filter(t, flip))
 
 
 def _mfma_ok(x, K, KS):
@@ -95,23 +113,21 @@ class _DwConvLK(torch.autograd.Function):
             pb = _packed_filter(w_big, False)
             ps = _packed_filter(w_small, False) if KS else None
             P = _abi.lib.ppea_dwconv_lk_stats_partials(N, C, H, W, K, KS) if (want_sums and KS) else 0
-            err = -1
             if P > 0:
                 # per-channel partial sums of both outputs from the conv's epilogue: the BatchNorm pair after it needs
                 # no statistics pass (batchnorm.fused_bn_act(..., sums=(sums[0], sums[1])))
                 sums = torch.empty(2, C, P, 2, device=x.device, dtype=_F32)
-                err = _timed("fwd31", K, lambda: _abi.lib.ppea_dwconv_lk_fwd_stats_bf16p(
-                    ptr(x), ptr(pb), ptr(ps), ptr(y_big), ptr(y_small), ptr(sums), N, C, H, W, K, KS, stream_ptr()))
-                if err != 0:
+                done = _timed("fwd31", K, lambda: try_call(
+                    "ppea_dwconv_lk_fwd_stats_bf16p", ptr(x), ptr(pb), ptr(ps), ptr(y_big), ptr(y_small), ptr(sums), N, C, H,
+                    W, K, KS, stream_ptr()))
+                if not done:
                     sums = None
-            if sums is None:
-                err = _timed("fwd31", K, lambda: _abi.lib.ppea_dwconv_lk_fwd_bf16p(
-                    ptr(x), ptr(pb), ptr(ps), ptr(y_big), ptr(y_small), N, C, H, W, K, KS, stream_ptr()))
-            if err == 0:
-                done = True
+            if not done:
+                done = _timed("fwd31", K, lambda: try_call(
+                    "ppea_dwconv_lk_fwd_bf16p", ptr(x), ptr(pb), ptr(ps), ptr(y_big), ptr(y_small), N, C, H, W, K, KS,
+                    stream_ptr()))
+            if done:
                 ctx.packed = (w_big, w_small)
-            elif err != -1:
-                _abi.check(err, "ppea_dwconv_lk_fwd_bf16p")
         if not done:
             _timed("fwd31", K, lambda: call(f"ppea_dwconv_lk_fwd_{_suffix(x)}", ptr(x), ptr(wb, _F32), ptr(ws),
                                              ptr(y_big), ptr(y_small), N, C, H, W, K, KS, stream_ptr()))
@@ -146,12 +162,9 @@ class _DwConvLK(torch.autograd.Function):
             if ctx.packed is not None:
                 pb = _packed_filter(ctx.packed[0], True)
                 ps = _packed_filter(ctx.packed[1], True) if KS else None
-                err = _timed("bwd31", K, lambda: _abi.lib.ppea_dwconv_lk_bwd_data_bf16p(
-                    ptr(dy_big), ptr(dy_small), ptr(pb), ptr(ps), ptr(dx), N, C, H, W, K, KS, stream_ptr()))
-                if err == 0:
-                    done = True
-                elif err != -1:
-                    _abi.check(err, "ppea_dwconv_lk_bwd_data_bf16p")
+                done = _timed("bwd31", K, lambda: try_call(
+                    "ppea_dwconv_lk_bwd_data_bf16p", ptr(dy_big), ptr(dy_small), ptr(pb), ptr(ps), ptr(dx), N, C, H, W, K, KS,
+                    stream_ptr()))
             if not done:
                 _timed("bwd31", K, lambda: call(f"ppea_dwconv_lk_bwd_data_{_suffix(x)}", ptr(dy_big),
                                                  ptr(dy_small), ptr(wb), ptr(ws), ptr(dx), N, C, H, W, K, KS,
@@ -216,15 +229,12 @@ class _DwConvLKBn(torch.autograd.Function):
             call(f"ppea_bn_bwd_channel_{sfx}", ptr(dt), ptr(z), None, stats, None, 1.0 / float(N * HW), None, ptr(dz), None,
                  ptr(sums), ACT_RELU, N, C, HW, stream_ptr())
         else:
-            err = getattr(_abi.lib, f"ppea_bn_bwd_reduce_final_{sfx}")(ptr(dt), ptr(z), None, stats, None, ptr(sums), ACT_RELU,
-                                                                       N, C, HW, stream_ptr())
-            if err == -1:
+            if not try_call(f"ppea_bn_bwd_reduce_final_{sfx}", ptr(dt), ptr(z), None, stats, None, ptr(sums), ACT_RELU, N, C,
+                            HW, stream_ptr()):
                 partial = torch.empty(C * N * 3, device=z.device, dtype=_F32)
                 call(f"ppea_bn_bwd_reduce_{sfx}", ptr(dt), ptr(z), None, stats, None, ptr(partial), ACT_RELU, N, C, HW,
                      stream_ptr())
                 call("ppea_bn_bwd_finalize_f32", ptr(partial), N, C, ptr(sums), stream_ptr())
-            else:
-                _abi.check(err, "ppea_bn_bwd_reduce_final")
             call(f"ppea_bn_bwd_apply_{sfx}", ptr(dt), ptr(z), None, stats, None, ptr(sums), 1.0 / float(N * HW), ptr(dz), None,
                  ACT_RELU, N, C, HW, stream_ptr())
         dg = sums[1].to(ctx.pdt[0]) if ctx.needs_input_grad[2] else None
@@ -584,13 +594,9 @@ def bn_batch_stats(z, eps, momentum, running_mean=None, running_var=None):
     HW = z.numel() // (N * C)
     dev = z.device
     out = torch.empty(3, C, device=dev, dtype=_F32)
-    err = getattr(_abi.lib, f"ppea_bn_stats_final_{_suffix(z)}")(
-        ptr(z), N, C, HW, float(eps), float(momentum), ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(running_mean),
-        ptr(running_var), stream_ptr())
-    if err == 0:                            # small channels: statistics final in one launch
-        return out[0], out[1], out[2]
-    if err != -1:
-        _abi.check(err, "ppea_bn_stats_final")
+    if try_call(f"ppea_bn_stats_final_{_suffix(z)}", ptr(z), N, C, HW, float(eps), float(momentum), ptr(out[0]), ptr(out[1]),
+                ptr(out[2]), ptr(running_mean), ptr(running_var), stream_ptr()):
+        return out[0], out[1], out[2]       # small channels: statistics final in one launch
     partial = torch.empty(C * N * 2, device=dev, dtype=_F32)
     call(f"ppea_bn_stats_{_suffix(z)}", ptr(z), ptr(partial), N, C, HW, stream_ptr())
     call("ppea_bn_finalize_f32", ptr(partial), N, C, HW, float(eps), float(momentum), ptr(out[0]), ptr(out[1]),
@@ -614,11 +620,8 @@ def bn_local_stats_packed(z):
     N, C = z.shape[0], z.shape[1]
     HW = z.numel() // (N * C)
     packed = torch.empty(2 * C + 1, device=z.device, dtype=_F32)
-    err = getattr(_abi.lib, f"ppea_bn_stats_packed_{_suffix(z)}")(ptr(z), N, C, HW, ptr(packed), stream_ptr())
-    if err == 0:
+    if try_call(f"ppea_bn_stats_packed_{_suffix(z)}", ptr(z), N, C, HW, ptr(packed), stream_ptr()):
         return packed
-    if err != -1:
-        _abi.check(err, "ppea_bn_stats_packed")
     partial = torch.empty(C * N * 2, device=z.device, dtype=_F32)
     call(f"ppea_bn_stats_{_suffix(z)}", ptr(z), ptr(partial), N, C, HW, stream_ptr())
     call("ppea_bn_finalize_packed_f32", ptr(partial), N, C, HW, ptr(packed), stream_ptr())
@@ -669,15 +672,12 @@ class _BnAct(torch.autograd.Function):
         st = _stats_array((mean1, invstd1, g1f, b1f, mean2, invstd2, g2f, b2f))
         sums = torch.empty(3, C, device=dev, dtype=_F32)
         sfx = _suffix(z1)
-        err = getattr(_abi.lib, f"ppea_bn_bwd_reduce_final_{sfx}")(
-            ptr(dy), ptr(z1), ptr(z2), st, ptr(maskf), ptr(sums), ctx.act, N, C, HW, stream_ptr())
-        if err == -1:                       # large planes: per-plane partials + finalize
+        if not try_call(f"ppea_bn_bwd_reduce_final_{sfx}", ptr(dy), ptr(z1), ptr(z2), st, ptr(maskf), ptr(sums), ctx.act, N, C,
+                        HW, stream_ptr()):                       # large planes: per-plane partials + finalize
             partial = torch.empty(C * N * 3, device=dev, dtype=_F32)
             call(f"ppea_bn_bwd_reduce_{sfx}", ptr(dy), ptr(z1), ptr(z2), st, ptr(maskf), ptr(partial), ctx.act, N, C,
                  HW, stream_ptr())
             call("ppea_bn_bwd_finalize_f32", ptr(partial), N, C, ptr(sums), stream_ptr())
-        elif err != 0:
-            _abi.check(err, "ppea_bn_bwd_reduce_final")
         inv_count = 1.0 / ctx.count
         gscale = None
         if ctx.group is not None:                      # SyncBN: sums of the global batch (ctx.count is the global count)
@@ -1043,21 +1043,18 @@ class _SyncBnAct(torch.autograd.Function):
         if dyb is not None:
             dyb = dyb.contiguous().to(z1.dtype)
             dym = torch.empty_like(z1)
-            err = getattr(_abi.lib, f"ppea_bn_bwd_reduce_final_dup_{sfx}")(
-                ptr(dy), ptr(dyb), ptr(dym), ptr(z1), ptr(z2), stats, ptr(maskf), ptr(sums), ctx.act, N, C, HW, stream_ptr())
-            dy = dym if err != -1 else dy + dyb
+            final = try_call(f"ppea_bn_bwd_reduce_final_dup_{sfx}", ptr(dy), ptr(dyb), ptr(dym), ptr(z1), ptr(z2), stats,
+                             ptr(maskf), ptr(sums), ctx.act, N, C, HW, stream_ptr())
+            dy = dym if final else dy + dyb
         else:
-            err = getattr(_abi.lib, f"ppea_bn_bwd_reduce_final_{sfx}")(
-                ptr(dy), ptr(z1), ptr(z2), stats, ptr(maskf), ptr(sums), ctx.act, N, C, HW, stream_ptr())
-        if err == -1:                       # large planes: per-plane partials + finalize
+            final = try_call(f"ppea_bn_bwd_reduce_final_{sfx}", ptr(dy), ptr(z1), ptr(z2), stats, ptr(maskf), ptr(sums),
+                             ctx.act, N, C, HW, stream_ptr())
+        if not final:                       # large planes: per-plane partials + finalize
             partial = torch.empty(C * N * 3, device=dev, dtype=_F32)
             call(f"ppea_bn_bwd_reduce_{sfx}", ptr(dy), ptr(z1), ptr(z2), stats, ptr(maskf), ptr(partial), ctx.act, N, C,
                  HW, stream_ptr())
             call("ppea_bn_bwd_finalize_f32", ptr(partial), N, C, ptr(sums), stream_ptr())
-            _count(launches=2)
-        else:
-            _abi.check(err, "ppea_bn_bwd_reduce_final")
-            _count(launches=1)
+        _count(launches=1 if final else 2)
         reduce_sums(sums, ctx.group)                            # -> sums of the global batch
         dz1 = torch.empty_like(z1)
         dz2 = torch.empty_like(z2) if two else None
@@ -1354,19 +1351,12 @@ def dwconv3x3(x, w, stride):
 # ---------------------------------------------------------------------------------------------
 # A5/A6  pointwise conv on MFMA (frozen 1x1 convs: forward with W, data gradient with W^T)
 # ---------------------------------------------------------------------------------------------
-_PW_CACHE = {}
-
-
 def _pw_matrices(w):
-    """(W [Cout][Cin] bf16, W^T [Cin][Cout] bf16) of a frozen 1x1 conv weight, cached per tensor object/version."""
-    key = id(w)
-    hit = _PW_CACHE.get(key)
-    if hit is not None and hit[4]() is w and hit[0] == w._version and hit[3] == tuple(w.shape):
-        return hit[1], hit[2]
-    m = w.detach().reshape(w.shape[0], w.shape[1]).to(_BF16).contiguous()
-    mt = m.t().contiguous()
-    _PW_CACHE[key] = (w._version, m, mt, tuple(w.shape), weakref.ref(w, lambda _r, k=key: _PW_CACHE.pop(k, None)))
-    return m, mt
+    """(W [Cout][Cin] bf16, W^T [Cin][Cout] bf16) of a frozen 1x1 conv weight."""
+    def build(w):
+        m = w.detach().reshape(w.shape[0], w.shape[1]).to(_BF16).contiguous()
+        return m, m.t().contiguous()
+    return _weight_image(w, "pw", build, cache_trainable=True)
 
 
 def pwconv_raw(a_mat, x, bias=None):
@@ -1374,11 +1364,8 @@ def pwconv_raw(a_mat, x, bias=None):
     B, K, H, W = x.shape
     M = a_mat.shape[0]
     y = torch.empty(B, M, H, W, device=x.device, dtype=_BF16)
-    err = _abi.lib.ppea_pwconv_bf16(ptr(a_mat, _BF16), ptr(x, _BF16), ptr(bias), ptr(y), B, M, K, H * W, stream_ptr())
-    if err == -1:
-        return None
-    _abi.check(err, "ppea_pwconv_bf16")
-    return y
+    served = try_call("ppea_pwconv_bf16", ptr(a_mat, _BF16), ptr(x, _BF16), ptr(bias), ptr(y), B, M, K, H * W, stream_ptr())
+    return y if served else None
 
 
 class _PwConvFrozen(torch.autograd.Function):
@@ -1935,26 +1922,23 @@ def conv_module(conv, x, act="none", reflect=False, out_nchw=False):
     if reflect and (x.shape[2] < 3 or x.shape[3] < 3):        # the fold kernel of the data gradient needs a 3 x 3 interior
         return None
     return conv2d_nhwc(x, conv.weight, conv.bias, conv.stride[0], 1 if reflect else conv.padding[0], reflect, act, out_nchw)
-_CONV_PACK_CACHE = {}
+
+
+def _pack_source(w):
+    """The weight as the conv pack kernels read it: contiguous fp32 or bf16."""
+    wd = w.detach()
+    return wd if wd.dtype in (_F32, _BF16) and wd.is_contiguous() else wd.float().contiguous()
 
 
 def _conv_packed(w, flip):
-    """bf16 operand image of w [Cout,Cin,R,S] (flip: the data-gradient operand).  Frozen weights are packed once per
-    version; trainable ones on every use (the flat Adam kernel updates them through raw pointers)."""
-    Cout, Cin, R, S = w.shape
-    cacheable = not w.requires_grad
-    key = (id(w), int(flip))
-    hit = _CONV_PACK_CACHE.get(key) if cacheable else None
-    if hit is not None and hit[2]() is w and hit[0] == w._version:
-        return hit[1]
-    wd = w.detach()
-    if wd.dtype not in (_F32, _BF16) or not wd.is_contiguous():
-        wd = wd.float().contiguous()
-    buf = torch.empty(_abi.lib.ppea_conv_packed_bytes(Cout, Cin, R, S, int(flip)) // 2, dtype=_BF16, device=w.device)
-    call("ppea_conv_pack_weights", ptr(wd), int(wd.dtype == _BF16), ptr(buf), Cout, Cin, R, S, int(flip), stream_ptr())
-    if cacheable:
-        _CONV_PACK_CACHE[key] = (w._version, buf, weakref.ref(w, lambda _r, k=key: _CONV_PACK_CACHE.pop(k, None)))
-    return buf
+    """bf16 operand image of w [Cout,Cin,R,S] (flip: the data-gradient operand)."""
+    def build(w):
+        Cout, Cin, R, S = w.shape
+        wd = _pack_source(w)
+        buf = torch.empty(_abi.lib.ppea_conv_packed_bytes(Cout, Cin, R, S, int(flip)) // 2, dtype=_BF16, device=w.device)
+        call("ppea_conv_pack_weights", ptr(wd), int(wd.dtype == _BF16), ptr(buf), Cout, Cin, R, S, int(flip), stream_ptr())
+        return buf
+    return _weight_image(w, ("conv", bool(flip)), build)
 
 
 def _nhwc_raw(t):
@@ -2108,24 +2092,15 @@ class _ConvNhwc(torch.autograd.Function):
         return dx, dw, db, None, None, None, None, None
 
 
-_IMG_PACK_CACHE = {}
-
-
 def _image_packed(w):
-    Cout, Cin, K, _ = w.shape
-    cacheable = not w.requires_grad
-    key = id(w)
-    hit = _IMG_PACK_CACHE.get(key) if cacheable else None
-    if hit is not None and hit[2]() is w and hit[0] == w._version:
-        return hit[1]
-    wd = w.detach()
-    if wd.dtype not in (_F32, _BF16) or not wd.is_contiguous():
-        wd = wd.float().contiguous()
-    buf = torch.empty(_abi.lib.ppea_conv_image_packed_bytes(Cout, K) // 2, dtype=_BF16, device=w.device)
-    call("ppea_conv_image_pack_weights", ptr(wd), int(wd.dtype == _BF16), ptr(buf), Cout, Cin, K, stream_ptr())
-    if cacheable:
-        _IMG_PACK_CACHE[key] = (w._version, buf, weakref.ref(w, lambda _r, k=key: _IMG_PACK_CACHE.pop(k, None)))
-    return buf
+    """bf16 row-packed operand image of w [Cout,Cin,K,K] for the image-fed conv kernels."""
+    def build(w):
+        Cout, Cin, K, _ = w.shape
+        wd = _pack_source(w)
+        buf = torch.empty(_abi.lib.ppea_conv_image_packed_bytes(Cout, K) // 2, dtype=_BF16, device=w.device)
+        call("ppea_conv_image_pack_weights", ptr(wd), int(wd.dtype == _BF16), ptr(buf), Cout, Cin, K, stream_ptr())
+        return buf
+    return _weight_image(w, "image", build)
 
 
 class _ConvImage(torch.autograd.Function):
@@ -2187,4 +2162,104 @@ def image_to_nhwc(x, cp=8, sub=0.0, div=1.0):
     N, C, H, W = x.shape
     y = torch.empty(N, cp, H, W, device=x.device, dtype=_BF16, memory_format=torch.channels_last)
     call("ppea_image_to_nhwc_bf16", ptr(x), _nhwc_raw(y), N, C, H, W, cp, float(sub), float(div), stream_ptr())
+    return y
+
+
+# ---------------------------------------------------------------------------------------------
+# inference (inference.DepthPredictor): eval-mode BatchNorm as a per-channel table tab = [s; o] fp32, y = s x + o, folded
+# into the launch that produces or consumes the tensor.  No autograd; None when no kernel serves the call.
+# ---------------------------------------------------------------------------------------------
+_UNIT_VECS = {}
+
+
+def unit_vecs(C, device):
+    """(zeros [C], ones [C]) fp32 on `device`, allocated once."""
+    key = (C, torch.device(device))
+    if key not in _UNIT_VECS:
+        _UNIT_VECS[key] = (torch.zeros(C, device=device), torch.ones(C, device=device))
+    return _UNIT_VECS[key]
+
+
+def _as(t, dtype):
+    return None if t is None else t.contiguous().to(dtype)
+
+
+@torch.no_grad()
+def table_affine(x, tab, act=ACT_NONE, x2=None, tab2=None, r1=None, r2=None, r2_scale=1.0):
+    """act(s x + o [+ s2 x2 + o2]) (+ r1) (+ r2_scale r2), NCHW: `ppea_bn_apply_*` with mean = 0, invstd = s, gamma = 1,
+    beta = o."""
+    x = x.contiguous()
+    N, C = x.shape[0], x.shape[1]
+    zero, one = unit_vecs(C, x.device)
+    st = (zero, tab[0], one, tab[1]) + ((zero, tab2[0], one, tab2[1]) if x2 is not None else (None,) * 4)
+    y = torch.empty_like(x)
+    call(f"ppea_bn_apply_{_suffix(x)}", ptr(x), ptr(_as(x2, x.dtype)), _stats_array(st), None, ptr(_as(r1, x.dtype)),
+         ptr(_as(r2, x.dtype)), float(r2_scale), ptr(y), int(act), N, C, x.numel() // (N * C), stream_ptr())
+    return y
+
+
+@torch.no_grad()
+def pwconv_table(x, w, tab, act=ACT_NONE, r1=None, r2=None, r2_scale=1.0, nxt=None):
+    """1x1 conv with weight w [M,K(,1,1)] + table (tab None: s = 1, o = 0) + act (+ r1) (+ r2_scale r2) in the MFMA GEMM's
+    epilogue -> (y, y2 = `nxt` table applied to y as stored, or None).  None when x is not bf16 or
+    `ppea_pwconv_infer_bf16` does not serve the shape."""
+    if x.dtype != _BF16:
+        return None
+    a, _ = _pw_matrices(w)
+    x = x.contiguous()
+    B, K, H, W = x.shape
+    M = a.shape[0]
+    s, o = (None, None) if tab is None else (tab[0], tab[1])
+    s2, o2 = (None, None) if nxt is None else (nxt[0], nxt[1])
+    y = torch.empty(B, M, H, W, device=x.device, dtype=_BF16)
+    y2 = torch.empty_like(y) if nxt is not None else None
+    served = try_call("ppea_pwconv_infer_bf16", ptr(a), ptr(x), ptr(s), ptr(o), int(act), ptr(_as(r1, _BF16)),
+                      ptr(_as(r2, _BF16)), float(r2_scale), ptr(s2), ptr(o2), ptr(y), ptr(y2), B, M, K, H * W, stream_ptr())
+    return (y, y2) if served else None
+
+
+@torch.no_grad()
+def dwconv_lk_bias_act(x, w, packed, bias, relu):
+    """act(DW_k(x; w) + bias), w [C,1,K,K] fp32: the MFMA kernel on `packed` (pack_dwconv_filter(w, False); bf16 x), then
+    the fp32-arithmetic kernel of x's dtype on w.  None when neither serves the kernel size."""
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    y = torch.empty_like(x)
+    tail = (ptr(bias), int(bool(relu)), ptr(y), N, C, H, W, w.shape[-1], stream_ptr())
+    if x.dtype == _BF16 and packed is not None and try_call("ppea_dwconv_lk_fwd_bias_act_bf16p", ptr(x), ptr(packed), *tail):
+        return y
+    return y if try_call(f"ppea_dwconv_lk_fwd_bias_act_{_suffix(x)}", ptr(x), ptr(w, _F32), *tail) else None
+
+
+@torch.no_grad()
+def dwconv_lk_plain(x, w):
+    """DW_k(x; w), w [C,1,K,K] fp32, on the fp32-arithmetic kernels (any odd K <= 31; no packed image involved)."""
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    y = torch.empty_like(x)
+    call(f"ppea_dwconv_lk_fwd_{_suffix(x)}", ptr(x), ptr(w, _F32), None, ptr(y), None, N, C, H, W, w.shape[-1], 0, stream_ptr())
+    return y
+
+
+@torch.no_grad()
+def dwconv3x3_affine(x, w, tab, relu, stride):
+    """[relu](s DW_3(x; w) + o), pad 1, in one launch; None when `ppea_dwconv3x3_fwd_affine_*` does not serve the call."""
+    x = x.contiguous()
+    N, C, H, W = x.shape
+    y = torch.empty(N, C, (H - 1) // stride + 1, (W - 1) // stride + 1, device=x.device, dtype=x.dtype)
+    wf = w.detach().float().contiguous()
+    served = try_call(f"ppea_dwconv3x3_fwd_affine_{_suffix(x)}", ptr(x), ptr(wf), ptr(tab[0]), ptr(tab[1]), int(bool(relu)),
+                      ptr(y), N, C, H, W, stride, stream_ptr())
+    return y if served else None
+
+
+@torch.no_grad()
+def nhwc_table_affine(x, ab, act=ACT_NONE, res=None):
+    """act(a x + b [+ res]) on channels_last tensors (`ppea_nhwc_bn_apply_*`, ab [2,C] fp32); None when the layout or the
+    channel count is not served."""
+    if not (nhwc_bn_supported(x) and (res is None or res.is_contiguous(memory_format=torch.channels_last))):
+        return None
+    N, C, H, W = x.shape
+    y = torch.empty_like(x)
+    call(f"ppea_nhwc_bn_apply_{_suffix(x)}", _raw(x), _raw(res), ptr(ab), _raw(y), N * H * W, C, 1, int(act), stream_ptr())
     return y

@@ -563,3 +563,39 @@ def test_trans_input_adapters_and_decoder_designs_have_the_reference_state_dict(
     for tid in (1, 2, 3, 4, 8, 10):
         dec = DepthDecoderV2(np.array([128, 256, 512, 1024]), range(4), False, dc=True, test_id=tid)
         assert list(dec.state_dict().keys()) == [str(n) for n in z[f"{tid}:names"]], tid
+
+
+def test_weight_image_cache_follows_the_tensor_its_version_and_the_packers_policy():
+    """`ops._weight_image`, the one cache behind `_packed_filter`, `_pw_matrices`, `_conv_packed` and `_image_packed`, with a
+    counting build function on CPU tensors (no kernel involved)."""
+    import gc
+    from ppeadepth import ops
+    built = []
+
+    def build(t):
+        built.append(t)
+        return len(built)
+
+    entries = lambda ident: [k for k in ops._WEIGHT_IMAGES if k[0] == ident]      # noqa: E731  (other tests' weights may live)
+    w = torch.zeros(4, 1, 3, 3)
+    wid = id(w)
+    assert ops._weight_image(w, ("dw", False), build) == 1
+    assert ops._weight_image(w, ("dw", False), build) == 1 and len(built) == 1      # unchanged tensor: not rebuilt
+    w.add_(1.0)                                                                     # in-place update bumps the version
+    assert ops._weight_image(w, ("dw", False), build) == 2
+    assert ops._weight_image(w, ("dw", False), build) == 2 and len(built) == 2
+    assert ops._weight_image(w, ("dw", True), build) == 3                           # another tag: a separate entry
+    assert ops._weight_image(w, ("dw", False), build) == 2 and len(entries(wid)) == 2
+    assert all(t is w for t in built)
+    del built[:], w
+    gc.collect()
+    assert not entries(wid)                                                         # the entries leave with the tensor
+    p = torch.nn.Parameter(torch.zeros(4, 1, 3, 3))
+    assert [ops._weight_image(p, "conv", build) for _ in range(3)] == [1, 2, 3]     # trainable: built on every use
+    assert not entries(id(p))
+    assert [ops._weight_image(p, "pw", build, cache_trainable=True) for _ in range(3)] == [4, 4, 4]
+    assert len(entries(id(p))) == 1
+    pid = id(p)
+    del built[:], p
+    gc.collect()
+    assert not entries(pid)

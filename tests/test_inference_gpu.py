@@ -27,16 +27,12 @@ def _g(seed):
 
 
 def _infer(a, x, s, o, act, r1, r2, r2s, s2, o2, want2):
-    from ppeadepth import _abi
-    B, K, H, W = x.shape
-    M = a.shape[0]
-    y = torch.full((B, M, H, W), float("nan"), device=x.device, dtype=torch.bfloat16)
-    y2 = torch.full_like(y, float("nan")) if want2 else None
-    p = _abi.ptr
-    err = _abi.lib.ppea_pwconv_infer_bf16(p(a), p(x), p(s), p(o), act, p(r1), p(r2), float(r2s), p(s2), p(o2), p(y), p(y2), B,
-                                          M, K, H * W, _abi.stream_ptr())
+    """`ops.pwconv_table` (the operator the predictor launches `ppea_pwconv_infer_bf16` through) -> (served, y, y2)."""
+    from ppeadepth import ops
+    out = ops.pwconv_table(x, a, None if s is None else torch.stack([s, o]), act, r1, r2, r2s,
+                           torch.stack([s2, o2]) if want2 else None)
     torch.cuda.synchronize()
-    return err, y, y2
+    return (False, None, None) if out is None else (True,) + out
 
 
 # the trunk's 1x1 convs at 192 x 640, batch 12 (31B and 31L), and batch 1
@@ -61,8 +57,8 @@ def test_pwconv_inference_epilogue_against_fp64(device, B, M, K, H, W):
     acc = torch.einsum("mk,bkhw->bmhw", a.double(), x.double())
     v = lambda t: t.double().view(1, -1, 1, 1)               # noqa: E731
     for act, use1, use2, want2 in COMBOS:
-        err, y, y2 = _infer(a, x, s, o, act, r1 if use1 else None, r2 if use2 else None, 0.75, s2, o2, want2)
-        assert err == 0, (act, use1, use2, want2, err)
+        ok, y, y2 = _infer(a, x, s, o, act, r1 if use1 else None, r2 if use2 else None, 0.75, s2, o2, want2)
+        assert ok and (y2 is not None) == want2, (act, use1, use2, want2)
         t = v(s) * acc + v(o)
         t = torch.relu(t) if act == 1 else (torch.nn.functional.gelu(t) if act == 2 else t)
         ref = t + (r1.double() if use1 else 0) + (0.75 * r2.double() if use2 else 0)
@@ -79,8 +75,8 @@ def test_pwconv_inference_epilogue_against_fp64(device, B, M, K, H, W):
             assert (y2.float() - again.float()).abs().max() <= 2 ** -7 * again.float().abs().max()
         print()
     # s = NULL is 1, o = NULL is 0
-    err, y, _ = _infer(a, x, None, None, 0, None, None, 1.0, None, None, False)
-    assert err == 0 and float((y.double() - acc).abs().max() / acc.abs().max()) <= PW_TOL
+    ok, y, _ = _infer(a, x, None, None, 0, None, None, 1.0, None, None, False)
+    assert ok and float((y.double() - acc).abs().max() / acc.abs().max()) <= PW_TOL
 
 
 @pytest.mark.parametrize("B,M,K,H,W", [(2, 128, 128, 6, 21), (2, 128, 72, 12, 40)])
@@ -88,9 +84,8 @@ def test_pwconv_inference_epilogue_refuses_shapes_it_does_not_serve(device, B, M
     x = torch.randn(B, K, H, W, generator=_g(1)).bfloat16().to(device)
     a = torch.randn(M, K, generator=_g(2)).bfloat16().to(device)
     s = torch.ones(M, device=device)
-    err, y, _ = _infer(a, x, s, s, 0, None, None, 1.0, None, None, False)
-    assert err == -1                                         # PPEA_ERR_UNSUPPORTED
-    assert bool(torch.isnan(y.float()).all())
+    ok, y, _ = _infer(a, x, s, s, 0, None, None, 1.0, None, None, False)
+    assert not ok and y is None                              # PPEA_ERR_UNSUPPORTED: the operator has no result
 
 
 # the large-kernel depthwise convs of the trunk at 192 x 640: 31B stages 0-3, 31L stage 0 / 3, batch 1
@@ -109,27 +104,19 @@ def test_merged_large_kernel_bias_relu_against_fp64(device, N, C, H, W, K):
     """`ppea_dwconv_lk_fwd_bias_act_bf16p` (MFMA) and `_bf16` / `_f32` (fp32 arithmetic) against an fp64 composite on the
     bf16-rounded operands, with and without ReLU.  Bounds: bf16 outputs as test_dwconv_bf16_mfma_full_size_vs_fp32_kernel
     (|err| <= |ref| 2^-7 + max|ref| 1e-3), fp32 as the fp32 kernel's FWD_TOL (2e-5 relative)."""
-    from ppeadepth import _abi
+    from ppeadepth import ops
     g = _g(N + C + K)
     w = (torch.randn(C, 1, K, K, generator=g) / K).bfloat16().float().to(device)
     bias = (0.5 * torch.randn(C, generator=g)).to(device)
     x = torch.randn(N, C, H, W, generator=g).bfloat16().to(device)
-    packed = torch.empty(_abi.lib.ppea_dwconv_lk_packed_bytes(C, K), dtype=torch.uint8, device=device)
-    p, st = _abi.ptr, _abi.stream_ptr
-    _abi.call("ppea_dwconv_lk_pack_bf16", p(w), p(packed), C, K, 0, st())
+    packed = ops.pack_dwconv_filter(w, False)
     for relu in (1, 0):
         ref = _dw_ref(x, w, bias, relu)
-        ys = {}
-        y = torch.full_like(x, float("nan"))
-        _abi.call("ppea_dwconv_lk_fwd_bias_act_bf16p", p(x), p(packed), p(bias), relu, p(y), N, C, H, W, K, st())
-        ys["bf16p"] = y
-        y = torch.full_like(x, float("nan"))
-        _abi.call("ppea_dwconv_lk_fwd_bias_act_bf16", p(x), p(w), p(bias), relu, p(y), N, C, H, W, K, st())
-        ys["bf16"] = y
-        xf = x.float()
-        y32 = torch.full_like(xf, float("nan"))
-        _abi.call("ppea_dwconv_lk_fwd_bias_act_f32", p(xf), p(w), p(bias), relu, p(y32), N, C, H, W, K, st())
+        # the operator's ladder: packed image + bf16 x -> the MFMA kernel; no image -> the plain kernel of x's dtype
+        ys = {"bf16p": ops.dwconv_lk_bias_act(x, w, packed, bias, relu), "bf16": ops.dwconv_lk_bias_act(x, w, None, bias, relu)}
+        y32 = ops.dwconv_lk_bias_act(x.float(), w, None, bias, relu)
         torch.cuda.synchronize()
+        assert y32.dtype == torch.float32 and all(y.dtype == torch.bfloat16 for y in ys.values())
         for name, y in ys.items():
             err = (y.double().cpu() - ref).abs()
             print(f"[{N},{C},{H}x{W}] K {K} relu {relu} {name}: {float(err.max() / ref.abs().max()):.3e}")
@@ -140,18 +127,15 @@ def test_merged_large_kernel_bias_relu_against_fp64(device, N, C, H, W, K):
 
 
 def test_merged_large_kernel_bias_relu_refuses_kernel_sizes_without_a_tile(device):
-    from ppeadepth import _abi
+    from ppeadepth import ops
     N, C, H, W, K = 2, 32, 12, 40, 7
     x = torch.randn(N, C, H, W, generator=_g(3)).bfloat16().to(device)
     w = torch.randn(C, 1, K, K, generator=_g(4)).to(device)
     bias = torch.zeros(C, device=device)
-    packed = torch.empty(_abi.lib.ppea_dwconv_lk_packed_bytes(C, K), dtype=torch.uint8, device=device)
-    y = torch.full_like(x, float("nan"))
-    p, st = _abi.ptr, _abi.stream_ptr
-    assert _abi.lib.ppea_dwconv_lk_fwd_bias_act_bf16p(p(x), p(packed), p(bias), 1, p(y), N, C, H, W, K, st()) == -1
-    assert _abi.lib.ppea_dwconv_lk_fwd_bias_act_bf16(p(x), p(w), p(bias), 1, p(y), N, C, H, W, K, st()) == -1
+    # None = the packed MFMA kernel AND the plain bf16 kernel answered PPEA_ERR_UNSUPPORTED (any other status raises)
+    assert ops.dwconv_lk_bias_act(x, w, ops.pack_dwconv_filter(w, False), bias, 1) is None
+    assert ops.dwconv_lk_bias_act(x, w, None, bias, 1) is None
     torch.cuda.synchronize()
-    assert bool(torch.isnan(y.float()).all())
 
 
 @pytest.mark.parametrize("N,C,H,W,stride", [(12, 128, 96, 320, 1), (12, 128, 96, 320, 2), (12, 256, 48, 160, 2),
@@ -160,29 +144,24 @@ def test_merged_large_kernel_bias_relu_refuses_kernel_sizes_without_a_tile(devic
 def test_depthwise3x3_affine_relu_against_fp64(device, N, C, H, W, stride):
     """`ppea_dwconv3x3_fwd_affine_*` (stem[1], stem[3], transitions[.][1] + eval BatchNorm + ReLU) against an fp64 composite.
     Bounds: bf16 one rounding of the output (2^-7 of the output scale, as the other bf16 kernels here), fp32 2e-5."""
-    from ppeadepth import _abi
+    from ppeadepth import ops
     g = _g(N + C + H + stride)
     w = (torch.randn(C, 1, 3, 3, generator=g) / 3).to(device)
     s, o = (torch.rand(C, generator=g) + 0.5).to(device), (0.3 * torch.randn(C, generator=g)).to(device)
     x = torch.randn(N, C, H, W, generator=g).bfloat16().to(device)
-    p, st = _abi.ptr, _abi.stream_ptr
+    tab, xf = torch.stack([s, o]), x.float()
     for relu in (1, 0):
         ref = torch.nn.functional.conv2d(x.double().cpu(), w.double().cpu(), None, stride, 1, 1, C)
         ref = ref * s.double().cpu().view(1, -1, 1, 1) + o.double().cpu().view(1, -1, 1, 1)
         ref = torch.relu(ref) if relu else ref
-        y16 = torch.full(ref.shape, float("nan"), device=device, dtype=torch.bfloat16)
-        _abi.call("ppea_dwconv3x3_fwd_affine_bf16", p(x), p(w), p(s), p(o), relu, p(y16), N, C, H, W, stride, st())
-        xf = x.float()
-        y32 = torch.full(ref.shape, float("nan"), device=device)
-        _abi.call("ppea_dwconv3x3_fwd_affine_f32", p(xf), p(w), p(s), p(o), relu, p(y32), N, C, H, W, stride, st())
+        y16, y32 = ops.dwconv3x3_affine(x, w, tab, relu, stride), ops.dwconv3x3_affine(xf, w, tab, relu, stride)
         torch.cuda.synchronize()
+        assert y16.dtype == torch.bfloat16 and y32.dtype == torch.float32 and y16.shape == y32.shape == ref.shape
         e16, e32 = rel_err(y16.cpu(), ref), rel_err(y32.cpu(), ref)
         print(f"[{N},{C},{H}x{W}] stride {stride} relu {relu}: bf16 {e16:.3e} f32 {e32:.3e}")
         assert e16 <= 2 ** -7 and e32 <= 2e-5
-    y = torch.full((N, C, H, W), float("nan"), device=device)
-    assert _abi.lib.ppea_dwconv3x3_fwd_affine_f32(p(xf), p(w), p(s), p(o), 1, p(y), N, C, H, W, 3, st()) == -1
+    assert ops.dwconv3x3_affine(xf, w, tab, 1, 3) is None      # stride 3: PPEA_ERR_UNSUPPORTED
     torch.cuda.synchronize()
-    assert bool(torch.isnan(y).all())
 
 
 # ---- end to end ---------------------------------------------------------------------------------------------------
