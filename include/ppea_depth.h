@@ -555,6 +555,18 @@ int ppea_cost_volume_fwd_f32(const float* cur, const float* lookup, const float*
 int ppea_cost_volume_fwd_bf16(const void* cur, const void* lookup, void* pairs, const float* P, const float* inv_K,
                               const float* bins, const int32_t* skip, float* cost, int B, int C, int h, int w, int D,
                               float eps, void* stream);
+/* Several lookup frames in ONE launch (match_features' loop over the lookups, :289-326): lookup [B,F,C,h,w], P [B,F,3,4],
+ * skip [B,F] int32 (required), F = 1 .. 4 (larger: PPEA_ERR_UNSUPPORTED).  Per (item, bin, pixel): diff_f as the single-frame
+ * kernel computes it for every frame that is not skipped and whose sample lies inside the edge mask;
+ * cost = (((0 + diff_0) + diff_1) + ...) / (#{f: diff_f > 0} + 1e-7) in fp32, frames in order.  The bf16 form packs the
+ * (1 + F) maps into channel-pair dwords first (`pairs`: caller-owned workspace of (1 + F) * B * C/2 * h * w uint32) and is
+ * bit-identical to the fp32 form on the widened features.  C even for bf16. */
+int ppea_cost_volume_multi_fwd_f32(const float* cur, const float* lookup, const float* P, const float* inv_K,
+                                   const float* bins, const int32_t* skip, float* cost, int B, int F, int C, int h, int w,
+                                   int D, float eps, void* stream);
+int ppea_cost_volume_multi_fwd_bf16(const void* cur, const void* lookup, void* pairs, const float* P, const float* inv_K,
+                                    const float* bins, const int32_t* skip, float* cost, int B, int F, int C, int h, int w,
+                                    int D, float eps, void* stream);
 int ppea_cost_volume_reduce_f32(const float* cost, const float* bins, float* cost_out,
                                 float* confidence, int64_t* argmin, float* lowest,
                                 int B, int D, int h, int w, void* stream);

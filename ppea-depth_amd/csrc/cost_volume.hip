@@ -247,6 +247,171 @@ __global__ __launch_bounds__(256) void cost_volume_fwd_bf16(const uint32_t* __re
     }
 }
 
+// ---- several lookup frames (rkm.py:289-326) ----------------------------------------------------------------------------
+// cost = (sum over the frames f that contribute of diff_f) / (#{f: diff_f > 0} + 1e-7), diff_f the single-frame masked mean
+// |warp_f(lookup_f) - cur|.  One thread = one pixel x DB bins x all F frames, channel loop outermost: the current frame's
+// feature does not depend on the frame either, so one load of it serves F * DB samples, and the F single-frame volumes
+// never exist.  The F * DB sums stay apart until the epilogue (the count needs each frame's own diff); they are added in
+// frame order in fp32, as the reference's `cost_volume + diffs` does.
+// PK: features are bf16 channel pairs (cv_pack_pairs), one dword = channels 2c, 2c + 1; CE = C / 2 elements per position.
+template <bool PK> struct CvFeat { using T = float; };
+template <> struct CvFeat<true> { using T = uint32_t; };
+template <typename T> struct alignas(4) Pair2 { T a, b; };
+
+template <bool PK, typename T>
+__device__ __forceinline__ void cv_accum(double& acc, T v00, T v01, T v10, T v11, float w00, float w01, float w10,
+                                         float w11, T cv) {
+    if constexpr (PK) {
+        const float wa = ((lo_f(v00) * w00 + lo_f(v01) * w01) + lo_f(v10) * w10) + lo_f(v11) * w11;
+        acc += (double)fabsf(wa - lo_f(cv));
+        const float wb = ((hi_f(v00) * w00 + hi_f(v01) * w01) + hi_f(v10) * w10) + hi_f(v11) * w11;
+        acc += (double)fabsf(wb - hi_f(cv));
+    } else {
+        const float warped = ((v00 * w00 + v01 * w01) + v10 * w10) + v11 * w11;
+        acc += (double)fabsf(warped - cv);
+    }
+}
+
+template <int F, int DB, bool PK>
+__global__ __launch_bounds__(256) void cost_volume_multi_fwd(const typename CvFeat<PK>::T* __restrict__ cur,
+                                                             const typename CvFeat<PK>::T* __restrict__ lookup,
+                                                             const float* __restrict__ P,       // [B][F][3][4]
+                                                             const float* __restrict__ inv_K,
+                                                             const float* __restrict__ bins,
+                                                             const int32_t* __restrict__ skip,  // [B][F]
+                                                             float* __restrict__ cost, int C, int h, int w, int D,
+                                                             float eps) {
+    using T = typename CvFeat<PK>::T;
+    const int b = blockIdx.z, d0 = blockIdx.y * DB;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int hw = h * w, CE = PK ? (C >> 1) : C;
+    if (i >= hw) return;
+    float* outp = cost + ((long)b * D + d0) * hw + i;
+    const int nd = min(DB, D - d0);
+    const int py = i / w, px = i - py * w;
+    bool any = false;                                  // same in every lane
+#pragma unroll
+    for (int f = 0; f < F; ++f) any = any || skip[b * F + f] == 0;
+    if (!any || px < 2 || px >= w - 2 || py < 2 || py >= h - 2) {
+        for (int k = 0; k < nd; ++k) outp[(long)k * hw] = 0.f;
+        return;
+    }
+    const float* ik = inv_K + b * 16;
+    const float fx = (float)px, fy = (float)py;
+    float ray[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ray[k] = (ik[k * 4] * fx + ik[k * 4 + 1] * fy) + ik[k * 4 + 2];
+    const T* cu = cur + (long)b * CE * hw + i;
+    // off: y0 * w + x0 of the footprint's top-left corner; -1: the sample adds nothing (frame skipped or outside the edge
+    // mask); -2: resolved below, its diff is in w00
+    int off[F][DB];
+    float w00[F][DB], w01[F][DB], w10[F][DB], w11[F][DB];
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        const float* pm = P + ((long)b * F + f) * 12;
+        const bool fskip = skip[b * F + f] != 0;
+#pragma unroll
+        for (int k = 0; k < DB; ++k) {
+            off[f][k] = -1;
+            w00[f][k] = w01[f][k] = w10[f][k] = w11[f][k] = 0.f;
+            if (fskip || k >= nd) continue;
+            const float depth = bins[d0 + k];
+            float X[3], cam[3];
+#pragma unroll
+            for (int q = 0; q < 3; ++q) X[q] = depth * ray[q];
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                cam[q] = ((pm[q * 4] * X[0] + pm[q * 4 + 1] * X[1]) + pm[q * 4 + 2] * X[2]) + pm[q * 4 + 3];
+            const float iz = cam[2] + eps;
+            const float gx = ((cam[0] / iz) / (float)(w - 1) - 0.5f) * 2.f;     // as cost_volume_fwd, line by line
+            const float gy = ((cam[1] / iz) / (float)(h - 1) - 0.5f) * 2.f;
+            const float xv = (gx / 2.f + 0.5f) * (float)(w - 1);
+            const float yv = (gy / 2.f + 0.5f) * (float)(h - 1);
+            if (!(xv >= 2.0f && xv <= (float)(w - 2) && yv >= 2.0f && yv <= (float)(h - 2))) continue;
+            const float ix = ((gx + 1.f) / 2.f) * (float)(w - 1);
+            const float iy = ((gy + 1.f) / 2.f) * (float)(h - 1);
+            const float flx = floorf(ix), fly = floorf(iy);
+            const int x0 = (int)flx, y0 = (int)fly;
+            const float tx = ix - flx, ty = iy - fly;
+            w00[f][k] = (1.f - tx) * (1.f - ty); w01[f][k] = tx * (1.f - ty); w10[f][k] = (1.f - tx) * ty; w11[f][k] = tx * ty;
+            off[f][k] = y0 * w + x0;
+            if (!(x0 + 1 < w && y0 + 1 < h)) {
+                // rare: the footprint touches the last column / row.  Corner by corner with zero fill, as grid_sample does
+                const T* lk = lookup + ((long)b * F + f) * CE * hw + off[f][k];
+                double acc = 0.0;
+                for (int c = 0; c < CE; ++c) {
+                    const T* l = lk + (long)c * hw;
+                    const T v01 = (x0 + 1 < w) ? l[1] : (T)0;
+                    const T v10 = (y0 + 1 < h) ? l[w] : (T)0;
+                    cv_accum<PK, T>(acc, l[0], v01, v10, (T)0, w00[f][k], w01[f][k], w10[f][k], w11[f][k], cu[(long)c * hw]);
+                }
+                w00[f][k] = (float)(acc / (double)C);
+                off[f][k] = -2;
+            }
+        }
+    }
+    double acc[F][DB];
+#pragma unroll
+    for (int f = 0; f < F; ++f)
+#pragma unroll
+        for (int k = 0; k < DB; ++k) acc[f][k] = 0.0;
+    const T* lkb = lookup + (long)b * F * CE * hw;
+    for (int c = 0; c < CE; ++c) {
+        const T cv = cu[(long)c * hw];
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            const T* lc = lkb + ((long)f * CE + c) * hw;
+#pragma unroll
+            for (int k = 0; k < DB; ++k) {
+                if (off[f][k] < 0) continue;
+                const Pair2<T> top = *reinterpret_cast<const Pair2<T>*>(lc + off[f][k]);
+                const Pair2<T> bot = *reinterpret_cast<const Pair2<T>*>(lc + off[f][k] + w);
+                cv_accum<PK, T>(acc[f][k], top.a, top.b, bot.a, bot.b, w00[f][k], w01[f][k], w10[f][k], w11[f][k], cv);
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < DB; ++k) {
+        if (k >= nd) continue;
+        float sum = 0.f, count = 0.f;
+#pragma unroll
+        for (int f = 0; f < F; ++f) {
+            if (off[f][k] == -1) continue;
+            const float diff = off[f][k] == -2 ? w00[f][k] : (float)(acc[f][k] / (double)C);
+            sum = sum + diff;
+            count += diff > 0.f ? 1.f : 0.f;
+        }
+        outp[(long)k * hw] = sum / (count + 1e-7f);          // average over the frames that saw the point (:323-326)
+    }
+}
+
+// (1 + F) maps [n][2 * C2][hw] bf16 -> channel-pair dwords [n][C2][hw]: the current frame's, then the lookups'
+__global__ __launch_bounds__(256) void cv_pack_pairs_multi(const uint16_t* __restrict__ cur, const uint16_t* __restrict__ look,
+                                                           uint32_t* __restrict__ out, int C2, int hw, long n_cur, long total) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;      // over (B + B * F) * C/2 * hw
+    if (i >= total) return;
+    const uint16_t* src = i < n_cur ? cur : look;
+    const long j = i < n_cur ? i : i - n_cur;
+    const long p = j % hw, c2 = (j / hw) % C2, n = j / ((long)hw * C2);
+    const long s = (n * 2 * C2 + 2 * c2) * hw + p;
+    out[i] = (uint32_t)src[s] | ((uint32_t)src[s + hw] << 16);
+}
+
+// Bins per thread for F lookup frames: the F * DB samples of a thread each hold a double sum, an offset and four weights.
+// 3 - 4 samples per thread keep the kernel at 8 waves / SIMD (<= 62 VGPRs), where the single-frame kernel was measured best
+// ("Several lookup frames": registers and occupancy per F and DB).
+template <bool PK, typename T>
+int cost_volume_multi_launch(const T* cur, const T* lookup, const float* P, const float* inv_K, const float* bins,
+                             const int32_t* skip, float* cost, int B, int F, int C, int h, int w, int D, float eps,
+                             hipStream_t stream) {
+#define CVM_LAUNCH(F_, DB_)                                                                                              \
+    hipLaunchKernelGGL((cost_volume_multi_fwd<F_, DB_, PK>), dim3((h * w + 255) / 256, (D + DB_ - 1) / DB_, B), dim3(256), \
+                       0, stream, cur, lookup, P, inv_K, bins, skip, cost, C, h, w, D, eps)
+    if (F == 1) CVM_LAUNCH(1, 4); else if (F == 2) CVM_LAUNCH(2, 2); else if (F == 3) CVM_LAUNCH(3, 1); else CVM_LAUNCH(4, 1);
+#undef CVM_LAUNCH
+    return launch_status();
+}
+
 __global__ __launch_bounds__(256) void cost_volume_reduce(const float* __restrict__ cost,
                                                           const float* __restrict__ bins,
                                                           float* __restrict__ cost_out,
@@ -317,6 +482,33 @@ int ppea_cost_volume_fwd_bf16(const void* cur, const void* lookup, void* pairs, 
     hipLaunchKernelGGL(cost_volume_fwd_bf16<DB>, dim3((h * w + 255) / 256, (D + DB - 1) / DB, B), dim3(256), 0,
                        (hipStream_t)stream, pc, pl, P, inv_K, bins, skip, cost, C, h, w, D, eps);
     return launch_status();
+}
+
+// Several lookup frames in one launch: lookup [B][F][C][h][w], P [B][F][3][4], skip [B][F]; F = 1 .. 4.
+int ppea_cost_volume_multi_fwd_f32(const float* cur, const float* lookup, const float* P, const float* inv_K,
+                                   const float* bins, const int32_t* skip, float* cost, int B, int F, int C, int h, int w,
+                                   int D, float eps, void* stream) {
+    if (B < 0 || F < 1 || F > 4 || C <= 0 || h < 5 || w < 5 || D <= 0 || D > 65535) return PPEA_ERR_UNSUPPORTED;
+    if (B == 0) return 0;
+    if (skip == nullptr) return PPEA_ERR_ARG;
+    return cost_volume_multi_launch<false>(cur, lookup, P, inv_K, bins, skip, cost, B, F, C, h, w, D, eps,
+                                           (hipStream_t)stream);
+}
+
+// bf16 features (C even); `pairs`: caller-owned workspace of (1 + F) * B * C/2 * h * w uint32 (= the inputs' bytes).
+// Same result, bit for bit, as ppea_cost_volume_multi_fwd_f32 on the features widened to fp32.
+int ppea_cost_volume_multi_fwd_bf16(const void* cur, const void* lookup, void* pairs, const float* P, const float* inv_K,
+                                    const float* bins, const int32_t* skip, float* cost, int B, int F, int C, int h, int w,
+                                    int D, float eps, void* stream) {
+    if (B < 0 || F < 1 || F > 4 || C <= 0 || (C & 1) || h < 5 || w < 5 || D <= 0 || D > 65535) return PPEA_ERR_UNSUPPORTED;
+    if (B == 0) return 0;
+    if (pairs == nullptr || skip == nullptr) return PPEA_ERR_ARG;
+    const long n = (long)B * (C / 2) * h * w;
+    uint32_t* pc = (uint32_t*)pairs;
+    hipLaunchKernelGGL(cv_pack_pairs_multi, dim3((unsigned)((n * (1 + F) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const uint16_t*)cur, (const uint16_t*)lookup, pc, C / 2, h * w, n, n * (1 + F));
+    return cost_volume_multi_launch<true>((const uint32_t*)pc, (const uint32_t*)(pc + n), P, inv_K, bins, skip, cost, B, F, C,
+                                          h, w, D, eps, (hipStream_t)stream);
 }
 
 int ppea_cost_volume_reduce_f32(const float* cost, const float* bins, float* cost_out, float* confidence,

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -172,6 +172,8 @@ SIGNATURES = {
     "ppea_loss_tail_bwd_f32": [_vp] * 9 + [_i] * 3 + [_vp],
     "ppea_cost_volume_fwd_bf16": [_vp] * 8 + [_i] * 5 + [_f, _vp],
     "ppea_cost_volume_reduce_f32": [_vp] * 6 + [_i] * 4 + [_vp],
+    "ppea_cost_volume_multi_fwd_f32": [_vp] * 7 + [_i] * 6 + [_f, _vp],
+    "ppea_cost_volume_multi_fwd_bf16": [_vp] * 8 + [_i] * 6 + [_f, _vp],
     "ppea_depth_errors_workspace_bytes": [_i, _l],
     "ppea_depth_errors_f32": [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _i, _i, _f, _vp],
     "ppea_depth_errors_mean_f64": [_vp, _vp, _i, _vp],

@@ -487,6 +487,12 @@ class TrainEngine:
         restore_state: put model / optimizer / tracker state back to what it was before the warm-up steps (in place,
         so the graph's addresses stay valid) -- the first replay is then step 1 of the run."""
         from . import rng
+        from ._abi import PpeaKernelError
+        ids = list(self.trainer._module().matching_ids)
+        if ids != [0, -1]:
+            # the captured step's stream plan (pose network replayed on the adapter stream) is verified for one lookup frame
+            raise PpeaKernelError(f"the captured training step serves matching_ids [0, -1], the model has {ids}: "
+                                  "train with eager steps (TrainEngine.step without capture)")
         dev = self.params[0].device
         snap = self.snapshot() if restore_state else None
         self.static_inputs = {k: v.clone() for k, v in inputs.items()}

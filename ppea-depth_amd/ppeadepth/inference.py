@@ -54,7 +54,11 @@ def merged_lk(lk):
 
 
 def cost_volume_cpu(cur, look, poses, K, inv_K, bins, eps=1e-7):
-    """torch composite of `ops.cost_volume` (replk_matching_adapter.py:261-340, one lookup frame): raw cost [B,D,h,w]."""
+    """torch composite of `ops.cost_volume` / `ops.cost_volume_multi` (replk_matching_adapter.py:261-340): raw cost [B,D,h,w].
+    look [B,C,h,w] with poses [B,4,4], or F lookup frames as look [B,F,C,h,w] with poses [B,F,4,4]: the masked differences of
+    the frames whose pose is not zeroed are summed in frame order and divided by the number of frames that contributed."""
+    if look.dim() == 4:
+        look, poses = look[:, None], poses[:, None]
     B, C, h, w = cur.shape
     D = bins.shape[0]
     ys, xs = torch.meshgrid(torch.arange(h, dtype=torch.float32), torch.arange(w, dtype=torch.float32), indexing="ij")
@@ -63,22 +67,25 @@ def cost_volume_cpu(cur, look, poses, K, inv_K, bins, eps=1e-7):
     inner[2:-2, 2:-2] = 1.0
     out = []
     for b in range(B):
-        if float(poses[b].sum()) == 0.0:
-            out.append(torch.zeros(D, h, w))
-            continue
-        rays = inv_K[b, :3, :3] @ pix
-        pts = torch.cat([bins.view(D, 1, 1) * rays[None], torch.ones(D, 1, h * w)], 1)
-        cam = (K[b] @ poses[b])[:3][None] @ pts
-        xy = cam[:, :2] / (cam[:, 2:3] + eps)
-        gx = ((xy[:, 0] / (w - 1)) - 0.5) * 2
-        gy = ((xy[:, 1] / (h - 1)) - 0.5) * 2
-        grid = torch.stack([gx, gy], -1).reshape(D, h, w, 2)
-        warped = F.grid_sample(look[b][None].expand(D, C, h, w), grid, mode="bilinear", padding_mode="zeros",
-                               align_corners=True)
-        xv, yv = (grid[..., 0] / 2 + 0.5) * (w - 1), (grid[..., 1] / 2 + 0.5) * (h - 1)
-        edge = ((xv >= 2.0) & (xv <= w - 2) & (yv >= 2.0) & (yv <= h - 2)).float()
-        diff = (warped - cur[b:b + 1]).abs().mean(1) * (edge * inner)
-        out.append(diff / ((diff > 0).float() + 1e-7))
+        cost, counts = torch.zeros(D, h, w), torch.zeros(D, h, w)
+        for f in range(look.shape[1]):
+            if float(poses[b, f].sum()) == 0.0:
+                continue
+            rays = inv_K[b, :3, :3] @ pix
+            pts = torch.cat([bins.view(D, 1, 1) * rays[None], torch.ones(D, 1, h * w)], 1)
+            cam = (K[b] @ poses[b, f])[:3][None] @ pts
+            xy = cam[:, :2] / (cam[:, 2:3] + eps)
+            gx = ((xy[:, 0] / (w - 1)) - 0.5) * 2
+            gy = ((xy[:, 1] / (h - 1)) - 0.5) * 2
+            grid = torch.stack([gx, gy], -1).reshape(D, h, w, 2)
+            warped = F.grid_sample(look[b, f][None].expand(D, C, h, w), grid, mode="bilinear", padding_mode="zeros",
+                                   align_corners=True)
+            xv, yv = (grid[..., 0] / 2 + 0.5) * (w - 1), (grid[..., 1] / 2 + 0.5) * (h - 1)
+            edge = ((xv >= 2.0) & (xv <= w - 2) & (yv >= 2.0) & (yv <= h - 2)).float()
+            diff = (warped - cur[b:b + 1]).abs().mean(1) * (edge * inner)
+            cost = cost + diff
+            counts = counts + (diff > 0).float()
+        out.append(cost / (counts + 1e-7))
     return torch.stack(out)
 
 
@@ -110,8 +117,15 @@ class DepthPredictor:
             raise PpeaKernelError(f"amp_dtype {amp_dtype} is not served (bf16 or None = fp32)")
         self.amp_dtype = amp_dtype
         self.bf16 = amp_dtype == torch.bfloat16
-        if getattr(opt, "num_matching_frames", 1) != 1 or getattr(opt, "use_future_frame", False):
-            raise PpeaKernelError("the predictor serves one lookup frame (num_matching_frames = 1, no future frame)")
+        # the lookup frames are the model's; an `opt` that describes another set is an inconsistency, not a request
+        self.lookup_ids = [int(f) for f in self.model.matching_ids[1:]]
+        asked = ([1] if getattr(opt, "use_future_frame", False) else []) + [
+            -k for k in range(1, 1 + getattr(opt, "num_matching_frames", 1))]
+        if asked != self.lookup_ids:
+            raise PpeaKernelError(f"opt describes lookup frames {asked}, the model was built with {self.lookup_ids}")
+        if not 1 <= len(self.lookup_ids) <= ops.CV_MAX_FRAMES:
+            raise PpeaKernelError(f"the cost volume serves 1 .. {ops.CV_MAX_FRAMES} lookup frames, the model has "
+                                  f"{len(self.lookup_ids)}")
         from .networks import replknet_adapter as rka
         self._rka = rka
         for enc in (self.model.encoder.replk, self.model.mono_encoder):
@@ -284,7 +298,7 @@ class DepthPredictor:
         one = ops.unit_vecs(x.shape[1], x.device)[1]
         return self.affine(x, ab, act, x2=res, tab2=None if res is None else torch.stack([one, one * 0]))
 
-    def _pose(self, pair):
+    def _pose_features(self, pair):
         from .networks import resnet_encoder as rn
         e = self.model.pose_encoder.encoder
         if self.cpu:
@@ -300,8 +314,23 @@ class DepthPredictor:
                 idt = x if blk.downsample is None else self._pose_bn(conv(blk.downsample[0], x), blk.downsample[1], ACT_NONE)
                 out = self._pose_bn(conv(blk.conv1, x), blk.bn1, ACT_RELU)
                 x = self._pose_bn(conv(blk.conv2, out), blk.bn2, ACT_RELU, idt)
+        return x
+
+    def _poses(self, color0, looks):
+        """Relative poses 0 -> f of the lookup frames, [B,F,4,4] in `lookup_ids` order: the pairs (f, f + 1), inverted, for
+        f < 0 and (f - 1, f) for f > 0 through the pose network as one F * B batch, then chained (repdepth.py:471-500)."""
+        B, ids = color0.shape[0], self.lookup_ids
+        frames = {0: color0, **{f: looks[:, j] for j, f in enumerate(ids)}}
+        pairs = [torch.cat([frames[f], frames[f + 1]] if f < 0 else [frames[f - 1], frames[f]], 1) for f in ids]
+        x = self._pose_features(pairs[0] if len(pairs) == 1 else torch.cat(pairs, 0))
         axisangle, translation = self.model.pose([[x]])
-        return transformation_from_parameters(axisangle[:, 0].float(), translation[:, 0].float(), invert=True)
+        rel = {}
+        for j, f in enumerate(ids):          # (+1,) -1, -2, ...: the neighbour towards frame 0 comes first
+            T = transformation_from_parameters(axisangle[j * B:(j + 1) * B, 0].float(),
+                                               translation[j * B:(j + 1) * B, 0].float(), invert=f < 0)
+            near = f + 1 if f < 0 else f - 1
+            rel[f] = T if near == 0 else torch.matmul(T, rel[near])
+        return torch.stack([rel[f] for f in ids], 1) if len(ids) > 1 else rel[ids[0]][:, None]
 
     # ---- public ---------------------------------------------------------------------------------------------------
     def _ctx(self):
@@ -315,24 +344,25 @@ class DepthPredictor:
             return self.model.mono_depth(feats)[("disp", 0)].float()
 
     @torch.no_grad()
-    def _multi(self, color0, color_m1, K2, inv_K2, min_bin, max_bin):
+    def _multi(self, color0, looks, K2, inv_K2, min_bin, max_bin):
+        """looks [B,F,3,H,W] in `lookup_ids` order -> (disp, lowest_cost, poses [B,F,4,4])."""
         with self._ctx():
             enc = self.model.encoder
             net = enc.replk
-            B = color0.shape[0]
-            pose = self._pose(torch.cat([color_m1, color0], 1))
+            B, Fr = looks.shape[:2]
+            pose = self._poses(color0, looks)
             mn = torch.as_tensor(min_bin, dtype=torch.float32, device=self.device).reshape(())
             mx = torch.as_tensor(max_bin, dtype=torch.float32, device=self.device).reshape(())
             bins = enc.compute_depth_bins(mn, mx, self.device)
-            # the current and the lookup frame share stem + stage 0 (eval BatchNorm is per sample): one 2B batch
-            x = self._stage(net, 0, self._stem(net, torch.cat([color0, color_m1], 0)))
-            feat0, look = self._norm(net, 0, x[:B]), x[B:]
+            # the current and the lookup frames share stem + stage 0 (eval BatchNorm is per sample): one (1 + F) B batch
+            x = self._stage(net, 0, self._stem(net, torch.cat([color0, looks.reshape(B * Fr, *looks.shape[2:])], 0)))
+            feat0, look = self._norm(net, 0, x[:B]), x[B:].reshape(B, Fr, *x.shape[1:])
             if self.cpu:
                 raw = cost_volume_cpu(feat0, look, pose, K2.float(), inv_K2.float(), bins)
                 cost, _conf, _idx, lowest = cost_volume_reduce_cpu(raw, bins)
                 xr = enc.reduce_conv(torch.cat([feat0, cost], 1))
             else:
-                raw = ops.cost_volume(feat0.contiguous(), look.contiguous(), pose, K2, inv_K2, bins)
+                raw = ops.cost_volume_multi(feat0.contiguous(), look.contiguous(), pose, K2, inv_K2, bins)
                 cost, _conf, _idx, lowest = ops.cost_volume_reduce(raw, bins)
                 cat = torch.cat([feat0, cost.to(feat0.dtype)], 1)
                 xr = ops.conv_module(enc.reduce_conv[0], cat, "relu", out_nchw=True)
@@ -351,21 +381,26 @@ class DepthPredictor:
         g["graph"].replay()
         return g["out"].clone()
 
-    def predict(self, color0, color_m1, K2, inv_K2, min_bin, max_bin):
+    def predict(self, color0, lookups, K2, inv_K2, min_bin, max_bin):
         """Pose network -> cost volume -> multi-frame encoder -> decoder (as `Trainer.predict_disps`).
-        -> dict(disp [B,1,H,W], lowest_cost [B,h/4,w/4], pose [B,4,4])."""
+        lookups: [B,3,H,W] for a model with one lookup frame, or [B,F,3,H,W] in `model.matching_ids[1:]` order.
+        -> dict(disp [B,1,H,W], lowest_cost [B,h/4,w/4], pose [B,4,4] resp. [B,F,4,4]: the relative poses 0 -> frame)."""
+        single = lookups.dim() == 4
+        looks = lookups[:, None] if single else lookups
+        if looks.shape[1] != len(self.lookup_ids):
+            raise PpeaKernelError(f"{looks.shape[1]} lookup frame(s) given, the model matches against {self.lookup_ids}")
         g = self._graphs.get(("multi", tuple(color0.shape)))
         if g is None:
             d = self.device
-            out = self._multi(color0.to(d), color_m1.to(d), K2.to(d), inv_K2.to(d), min_bin, max_bin)
+            out = self._multi(color0.to(d), looks.to(d), K2.to(d), inv_K2.to(d), min_bin, max_bin)
         else:
             mn = torch.as_tensor(min_bin, dtype=torch.float32).reshape(())
             mx = torch.as_tensor(max_bin, dtype=torch.float32).reshape(())
-            for dst, src in zip(g["in"], (color0, color_m1, K2, inv_K2, mn, mx)):
+            for dst, src in zip(g["in"], (color0, looks, K2, inv_K2, mn, mx)):
                 dst.copy_(src)
             g["graph"].replay()
             out = tuple(t.clone() for t in g["out"])
-        return {"disp": out[0], "lowest_cost": out[1], "pose": out[2]}
+        return {"disp": out[0], "lowest_cost": out[1], "pose": out[2][:, 0] if single else out[2]}
 
     def capture(self, B, mono=True, multi=True):
         """torch.cuda.graph over static buffers for batch B at (opt.height, opt.width); predict* then replay."""
@@ -378,7 +413,8 @@ class DepthPredictor:
         if mono:
             jobs.append(("mono", [img()], lambda i: self._mono(i[0])))
         if multi:
-            ins = [img(), img(), eye.clone(), eye.clone(), torch.tensor(0.1, device=d), torch.tensor(10.0, device=d)]
+            looks = torch.rand(B, len(self.lookup_ids), 3, H, W, device=d)
+            ins = [img(), looks, eye.clone(), eye.clone(), torch.tensor(0.1, device=d), torch.tensor(10.0, device=d)]
             jobs.append(("multi", ins, lambda i: self._multi(*i)))
         for name, ins, fn in jobs:
             side = torch.cuda.Stream(d)

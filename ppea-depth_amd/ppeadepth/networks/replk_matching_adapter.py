@@ -2,8 +2,8 @@
 
 `RepLKMatchingAdapter.forward(current_image, lookup_images, poses, K, invK, min_depth_bin,
 max_depth_bin) -> (features, lowest_cost, confidence_mask)` as in the reference (rkm.py:389-476).
-Execution differences: the 96-plane sweep is ONE fused kernel for the whole batch (no per-item
-Python loop, no [96,C,h,w] repeat, no BackprojectDepth/Project3D modules rebuilt per call); depth
+Execution differences: the 96-plane sweep is ONE fused kernel for the whole batch and all lookup
+frames (no per-item or per-frame Python loop, no [96,C,h,w] repeat, no BackprojectDepth/Project3D modules rebuilt per call); depth
 bins are built with one vectorised expression; the argmin -> 1/depth lookup stays on the device.
 """
 import numpy as np
@@ -63,10 +63,7 @@ class RepLKMatchingAdapter(nn.Module):
     def match_features(self, current_feats, lookup_feats, relative_poses, K, invK):
         """current_feats [B,C,h,w]; lookup_feats [B,F,C,h,w]; relative_poses [B,F,4,4] -> cost volume
         and missing mask, both [B,D,h,w] (after the missing -> max fill, as the reference returns)."""
-        if lookup_feats.shape[1] != 1:
-            raise NotImplementedError("hot path uses one lookup frame (num_matching_frames=1)")
-        raw = ops.cost_volume(current_feats, lookup_feats[:, 0], relative_poses[:, 0], K, invK,
-                              self.depth_bins)
+        raw = ops.cost_volume_multi(current_feats, lookup_feats, relative_poses, K, invK, self.depth_bins)
         missing = (raw == 0).float()
         filled = raw * (1 - missing) + raw.max(1, keepdim=True)[0] * missing
         return filled, missing
@@ -92,13 +89,12 @@ class RepLKMatchingAdapter(nn.Module):
         current_feats, self.features = self.feature_extraction(current_image)
         with torch.no_grad():
             B, Fr, ch, H, W = lookup_images.shape
-            if Fr != 1:
-                raise NotImplementedError("hot path uses one lookup frame (num_matching_frames=1)")
             lookup_feats, _ = self.feature_extraction(lookup_images.reshape(B * Fr, ch, H, W))
             if callable(poses):
                 poses = poses()
-            raw = ops.cost_volume(self.features[-1], lookup_feats, poses[:, 0], K, invK,
-                                  self.depth_bins)
+            # all Fr lookup frames in one launch (Fr = 1: the single-frame kernel)
+            raw = ops.cost_volume_multi(self.features[-1], lookup_feats.reshape(B, Fr, *lookup_feats.shape[1:]), poses, K,
+                                        invK, self.depth_bins)
             cost_volume, confidence_mask, argmin, lowest_cost = ops.cost_volume_reduce(raw, self.depth_bins)
         self.argmin = argmin
         feat = self.features[-1]

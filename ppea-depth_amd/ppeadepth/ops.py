@@ -513,6 +513,35 @@ def cost_volume(cur, lookup, poses, K, inv_K, bins, eps=1e-7):
     return cost
 
 
+CV_MAX_FRAMES = 4      # up to three past frames plus the future one
+
+
+@torch.no_grad()
+def cost_volume_multi(cur, lookups, poses, K, inv_K, bins, eps=1e-7):
+    """cur [B,C,h,w]; lookups [B,F,C,h,w]; poses [B,F,4,4] (a zeroed pose = that frame of that item skipped);
+    -> raw cost [B,D,h,w] averaged over the frames that contribute at each (bin, pixel), in ONE launch for F > 1.
+    F = 1 is `cost_volume` (same launches, same bits)."""
+    B, F, C, h, w = lookups.shape
+    if F == 1:
+        return cost_volume(cur, lookups[:, 0], poses[:, 0], K, inv_K, bins, eps)
+    if F > CV_MAX_FRAMES:
+        raise _abi.PpeaKernelError(f"cost_volume_multi serves 1 .. {CV_MAX_FRAMES} lookup frames, got {F}")
+    D = bins.shape[0]
+    P = torch.matmul(K[:, None], poses)[:, :, :3, :].contiguous().float()
+    skip = (poses.reshape(B, F, -1).sum(2) == 0).to(torch.int32)
+    cost = torch.empty(B, D, h, w, device=cur.device, dtype=_F32)
+    inv_K, bins = inv_K.contiguous().float(), bins.contiguous().float()
+    tail = (ptr(P), ptr(inv_K), ptr(bins), ptr(skip), ptr(cost), B, F, C, h, w, D, float(eps), stream_ptr())
+    if CV_BF16 and cur.dtype == _BF16 and lookups.dtype == _BF16 and C % 2 == 0:
+        cur, lookups = cur.contiguous(), lookups.contiguous()
+        pairs = torch.empty((1 + F) * B * (C // 2) * h * w, device=cur.device, dtype=torch.int32)
+        call("ppea_cost_volume_multi_fwd_bf16", ptr(cur), ptr(lookups), ptr(pairs), *tail)
+        return cost
+    cur, lookups = cur.contiguous().float(), lookups.contiguous().float()
+    call("ppea_cost_volume_multi_fwd_f32", ptr(cur), ptr(lookups), *tail)
+    return cost
+
+
 @torch.no_grad()
 def cost_volume_reduce(cost, bins):
     """-> (masked cost [B,D,h,w], confidence [B,h,w], argmin int64 [B,h,w], lowest-cost 1/depth [B,h,w])."""

@@ -161,20 +161,19 @@ def _render_neighbour(tex, depth, K, inv_K, tz):
 
 
 def make_rendered_inputs(batch: int, height: int, width: int, seed: int = 7, tz: float = 1.0, scales=(0, 1, 2, 3),
-                         intrinsics: str = "kitti"):
-    """Row-P input dict whose frames -1 / +1 are RENDERED from the centre frame's texture and a known depth map with the
-    camera moved -tz / +tz metres along its axis (the renderer of the synthetic validation split): smooth textures and a
+                         intrinsics: str = "kitti", frame_ids=(0, -1, 1)):
+    """Row-P input dict whose frames f != 0 are RENDERED from the centre frame's texture and a known depth map with the
+    camera moved f * tz metres along its axis (the renderer of the synthetic validation split): smooth textures and a
     consistent geometry instead of white noise, for fixtures on which a reduced-precision step can be compared tightly."""
     Kf = kitti_K if intrinsics == "kitti" else cityscapes_K
     K, inv_K = Kf(height, width, 0)
-    per = {0: [], -1: [], 1: []}
+    per = {f: [] for f in frame_ids}
     for i in range(batch):
         tex, depth = _scene(i, height, width, seed)
-        per[0].append(tex)
-        per[-1].append(_render_neighbour(tex, depth, K, inv_K, -tz))
-        per[1].append(_render_neighbour(tex, depth, K, inv_K, tz))
+        for f in frame_ids:
+            per[f].append(tex if f == 0 else _render_neighbour(tex, depth, K, inv_K, f * tz))
     inputs = {}
-    for f in (0, -1, 1):
+    for f in frame_ids:
         base = torch.stack(per[f])
         for s in scales:
             img = base if s == 0 else torch.nn.functional.avg_pool2d(base, 2 ** s)
@@ -187,11 +186,12 @@ def make_rendered_inputs(batch: int, height: int, width: int, seed: int = 7, tz:
     return inputs
 
 
-def make_eval_split(root, n=4, height=192, width=640, gt_hw=(375, 1242), seed=7, split="eigen_zhou_synth"):
+def make_eval_split(root, n=4, height=192, width=640, gt_hw=(375, 1242), seed=7, split="eigen_zhou_synth",
+                    frame_ids=(0, -1, 1)):
     """Writes an eigen_zhou-format split under `root`:
          splits/<split>/val_files.txt      lines "<folder> <frame index> <l|r>"   (kitti_dataset.py:46-62)
          splits/<split>/gt_depths.npz      ["data"]: object array of [375,1242] float32 maps, 0 = no LiDAR return
-         <folder>/image_02/data/<%010d>.npy frames t-1, t, t+1 as float32 [3,H,W] in [0,1]
+         <folder>/image_02/data/<%010d>.npy frames t + f for f in frame_ids as float32 [3,H,W] in [0,1]
        and returns the list of split lines."""
     import os
     os.makedirs(os.path.join(root, "splits", split), exist_ok=True)
@@ -205,7 +205,7 @@ def make_eval_split(root, n=4, height=192, width=640, gt_hw=(375, 1242), seed=7,
         tex, depth = _scene(i, height, width, seed)
         d = os.path.join(root, folder, "image_02", "data")
         os.makedirs(d, exist_ok=True)
-        frames = {0: tex, -1: _render_neighbour(tex, depth, K, inv_K, -0.4), 1: _render_neighbour(tex, depth, K, inv_K, 0.4)}
+        frames = {f: tex if f == 0 else _render_neighbour(tex, depth, K, inv_K, 0.4 * f) for f in frame_ids}
         for off, img in frames.items():
             np.save(os.path.join(d, f"{frame + off:010d}.npy"), img.numpy().astype(np.float32))
         gt = torch.nn.functional.interpolate(depth[None, None], gt_hw, mode="bilinear", align_corners=False)[0, 0]

@@ -170,19 +170,25 @@ class Trainer:
     # ---- trainer.py:653-857 -----------------------------------------------------------------------
     @torch.no_grad()
     def predict_disps(self, data, mono=True, predictor=None):
-        """Inference path of `val` for one batch (trainer.py:676-752): pose of the lookup frame from the pose network,
-        cost volume + multi-frame encoder + decoder, optionally the single-frame teacher; model in eval mode.
+        """Inference path of `val` for one batch (trainer.py:676-752): poses of the lookup frames `matching_ids[1:]` from
+        the pose network, chained 0 -> -1 -> -2 ... and 0 -> +1 (eval_depth_ori.py:224-253; upstream's `val` itself stops at
+        frame -1), written to `data[("relative_pose", f)]`; cost volume + multi-frame encoder + decoder, optionally the
+        single-frame teacher; model in eval mode.
         -> (scaled multi-frame disparity [B,H,W], scaled teacher disparity or None), as `disp_to_depth(., 1e-3, 80)`.
         predictor: an `inference.DepthPredictor` of this model -- the same outputs from its fused schedule."""
         from .layers import transformation_from_parameters
         model = self._module()
         dev = self.device
+        ids = [int(f) for f in model.matching_ids[1:]]
         if predictor is not None:
             tracker = self.depth_bin_tracker
             mn, mx = ((tracker.min_depth, tracker.max_depth) if getattr(self.opt, "notadabins", False)
                       else tracker.compute())
-            r = predictor.predict(data[("color", 0, 0)], data[("color", -1, 0)], data[("K", 2)], data[("inv_K", 2)], mn, mx)
-            data[("relative_pose", -1)] = r["pose"]
+            looks = [data[("color", f, 0)] for f in ids]
+            r = predictor.predict(data[("color", 0, 0)], looks[0] if len(ids) == 1 else torch.stack(looks, 1),
+                                  data[("K", 2)], data[("inv_K", 2)], mn, mx)
+            for j, f in enumerate(ids):
+                data[("relative_pose", f)] = r["pose"] if len(ids) == 1 else r["pose"][:, j]
             pred, _ = disp_to_depth(r["disp"], MIN_VAL_EVAL, 80)
             pred_mono = None
             if mono:
@@ -190,19 +196,24 @@ class Trainer:
                 pred_mono = pred_mono[:, 0]
             return pred[:, 0], pred_mono
         ctx = torch.autocast("cuda", dtype=self.amp_dtype) if self.amp_dtype is not None else contextlib.nullcontext()
-        color = {f: data[("color", f, 0)].to(dev) for f in (0, -1)}
+        color = {f: data[("color", f, 0)].to(dev) for f in [0] + ids}
         with ctx:
-            feats = [model.pose_encoder(torch.cat([color[-1], color[0]], 1))]
-            axisangle, translation = model.pose(feats)
-            pose = transformation_from_parameters(axisangle[:, 0].float(), translation[:, 0].float(), invert=True)
-            data[("relative_pose", -1)] = pose
+            for f in ids:                 # (+1,) -1, -2, ...: the neighbour towards frame 0 is done first
+                near = f + 1 if f < 0 else f - 1
+                feats = [model.pose_encoder(torch.cat([color[f], color[near]] if f < 0 else [color[near], color[f]], 1))]
+                axisangle, translation = model.pose(feats)
+                pose = transformation_from_parameters(axisangle[:, 0].float(), translation[:, 0].float(), invert=f < 0)
+                data[("relative_pose", f)] = pose if near == 0 else torch.matmul(pose, data[("relative_pose", near)])
             tracker = self.depth_bin_tracker
             if getattr(self.opt, "notadabins", False):
                 mn, mx = tracker.min_depth, tracker.max_depth
             else:
                 mn, mx = tracker.compute()
-            feats, _lowest, _conf = model.encoder(color[0], color[-1][:, None], pose[:, None],
-                                                  data[("K", 2)].to(dev), data[("inv_K", 2)].to(dev), mn, mx)
+            one = len(ids) == 1
+            feats, _lowest, _conf = model.encoder(
+                color[0], color[ids[0]][:, None] if one else torch.stack([color[f] for f in ids], 1),
+                data[("relative_pose", ids[0])][:, None] if one else torch.stack([data[("relative_pose", f)] for f in ids], 1),
+                data[("K", 2)].to(dev), data[("inv_K", 2)].to(dev), mn, mx)
             disp = model.depth(feats)[("disp", 0)].float()
             pred, _ = disp_to_depth(disp, MIN_VAL_EVAL, 80)
             pred_mono = None
