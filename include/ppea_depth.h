@@ -537,30 +537,21 @@ int ppea_conv_image_wgrad_bf16(const void* dz, const void* x, void* dw, int dw_b
                                int Cin, int Cout, int K, int stride, int pad, int Ho, int Wo, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * A9  match_features (replk_matching_adapter.py:261-340), one lookup frame per item.
- *      cur, lookup [B,C,h,w]; P [B,3,4] = (K @ T)[:, :3, :] at the matching scale;
- *      inv_K [B,4,4]; bins [D]; skip [B] int32 (non-zero = lookup pose was zeroed, item skipped
- *      -> cost 0).  cost [B,D,h,w] = mean_c|warp(lookup) - cur| * edge_mask / (cnt + 1e-7).
+ * A9  match_features (replk_matching_adapter.py:261-340, the loop over the lookups :289-326): F = 1 .. 4 lookup frames per
+ *      item in ONE launch (larger F: PPEA_ERR_UNSUPPORTED).  F = 1 is the former single-frame form: the entry points
+ *      ppea_cost_volume_fwd_{f32,bf16} of ABI <= 15 are these with F = 1 and a required `skip`, same bits.
+ *      cur [B,C,h,w]; lookup [B,F,C,h,w]; P [B,F,3,4] = (K @ T_f)[:, :3, :] at the matching scale; inv_K [B,4,4]; bins [D];
+ *      skip [B,F] int32, required (non-zero = that frame's pose was zeroed: the frame adds nothing; every frame of an item
+ *      skipped -> cost 0).  Per (item, bin, pixel): diff_f = mean_c|warp_f(lookup_f) - cur| for every frame that is not
+ *      skipped and whose sample lies inside the edge mask;
+ *      cost [B,D,h,w] = (((0 + diff_0) + diff_1) + ...) / (#{f: diff_f > 0} + 1e-7) in fp32, frames in order.
+ *      bf16 features (the bf16 step): the kernel is bound by the bytes crossing the L1, so the (1 + F) maps are packed into
+ *      channel-PAIR dwords first (`pairs`: caller-owned workspace of (1 + F) * B * C/2 * h * w uint32) and a corner load
+ *      serves two channels.  Bit-identical to the fp32 form on the features widened to fp32.  C even.
  * A10 cost_volume_reduce (:446-456, :372-387): missing -> per-pixel max; confidence mask;
  *      argmin over bins after 0 -> 100 (int64, first minimum); lowest = 1/bins[argmin];
  *      cost_out = filled cost * confidence.
  * ---------------------------------------------------------------------------------------- */
-int ppea_cost_volume_fwd_f32(const float* cur, const float* lookup, const float* P,
-                             const float* inv_K, const float* bins, const int32_t* skip,
-                             float* cost, int B, int C, int h, int w, int D, float eps,
-                             void* stream);
-/* bf16 features (the bf16 step): the kernel is bound by the bytes crossing the L1, so channel PAIRS are packed into dwords
- * first (`pairs`: caller-owned workspace of 2 * B * C/2 * h * w uint32) and a corner load serves two channels.  Bit-identical
- * to ppea_cost_volume_fwd_f32 on the features widened to fp32.  C even. */
-int ppea_cost_volume_fwd_bf16(const void* cur, const void* lookup, void* pairs, const float* P, const float* inv_K,
-                              const float* bins, const int32_t* skip, float* cost, int B, int C, int h, int w, int D,
-                              float eps, void* stream);
-/* Several lookup frames in ONE launch (match_features' loop over the lookups, :289-326): lookup [B,F,C,h,w], P [B,F,3,4],
- * skip [B,F] int32 (required), F = 1 .. 4 (larger: PPEA_ERR_UNSUPPORTED).  Per (item, bin, pixel): diff_f as the single-frame
- * kernel computes it for every frame that is not skipped and whose sample lies inside the edge mask;
- * cost = (((0 + diff_0) + diff_1) + ...) / (#{f: diff_f > 0} + 1e-7) in fp32, frames in order.  The bf16 form packs the
- * (1 + F) maps into channel-pair dwords first (`pairs`: caller-owned workspace of (1 + F) * B * C/2 * h * w uint32) and is
- * bit-identical to the fp32 form on the widened features.  C even for bf16. */
 int ppea_cost_volume_multi_fwd_f32(const float* cur, const float* lookup, const float* P, const float* inv_K,
                                    const float* bins, const int32_t* skip, float* cost, int B, int F, int C, int h, int w,
                                    int D, float eps, void* stream);

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -162,7 +162,6 @@ SIGNATURES = {
     "ppea_conv2d_bf16_fwd": [_vp] * 6 + [_i] * 9 + [_vp],
     "ppea_conv2d_bf16_dgrad": [_vp] * 5 + [_i] * 11 + [_vp],
     "ppea_conv2d_bf16_wgrad": [_vp] * 6 + [_i] * 11 + [_vp],
-    "ppea_cost_volume_fwd_f32": [_vp] * 7 + [_i] * 5 + [_f, _vp],
     "ppea_nhwc_maxpool3x3s2_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "ppea_nhwc_maxpool3x3s2_fwd_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "ppea_nhwc_maxpool3x3s2_bwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
@@ -170,7 +169,6 @@ SIGNATURES = {
     "ppea_loss_tail_blocks": [_l],
     "ppea_loss_tail_fwd_f32": [_vp] * 10 + [_i] * 4 + [_vp],
     "ppea_loss_tail_bwd_f32": [_vp] * 9 + [_i] * 3 + [_vp],
-    "ppea_cost_volume_fwd_bf16": [_vp] * 8 + [_i] * 5 + [_f, _vp],
     "ppea_cost_volume_reduce_f32": [_vp] * 6 + [_i] * 4 + [_vp],
     "ppea_cost_volume_multi_fwd_f32": [_vp] * 7 + [_i] * 6 + [_f, _vp],
     "ppea_cost_volume_multi_fwd_bf16": [_vp] * 8 + [_i] * 6 + [_f, _vp],

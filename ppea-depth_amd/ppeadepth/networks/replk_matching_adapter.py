@@ -92,7 +92,7 @@ class RepLKMatchingAdapter(nn.Module):
             lookup_feats, _ = self.feature_extraction(lookup_images.reshape(B * Fr, ch, H, W))
             if callable(poses):
                 poses = poses()
-            # all Fr lookup frames in one launch (Fr = 1: the single-frame kernel)
+            # all Fr lookup frames in one launch (Fr = 1: its F = 1 instantiation)
             raw = ops.cost_volume_multi(self.features[-1], lookup_feats.reshape(B, Fr, *lookup_feats.shape[1:]), poses, K,
                                         invK, self.depth_bins)
             cost_volume, confidence_mask, argmin, lowest_cost = ops.cost_volume_reduce(raw, self.depth_bins)

@@ -488,42 +488,20 @@ def loss_tail(reproj, sel, src, auto_idx=None, cons=None, aug=None, multi=None, 
 # ---------------------------------------------------------------------------------------------
 # A9/A10  cost volume (runs under no_grad in the reference, rkm.py:427)
 # ---------------------------------------------------------------------------------------------
-CV_BF16 = True      # bf16 features on the packed-pair kernel (False: widened to fp32 first; bit-identical results)
-
-
-@torch.no_grad()
-def cost_volume(cur, lookup, poses, K, inv_K, bins, eps=1e-7):
-    """cur, lookup [B,C,h,w]; poses [B,4,4] (zeroed pose = skipped item); -> raw cost [B,D,h,w]."""
-    B, C, h, w = cur.shape
-    D = bins.shape[0]
-    P = torch.matmul(K, poses)[:, :3, :].contiguous().float()
-    skip = (poses.reshape(B, -1).sum(1) == 0).to(torch.int32)
-    cost = torch.empty(B, D, h, w, device=cur.device, dtype=_F32)
-    if CV_BF16 and cur.dtype == _BF16 and lookup.dtype == _BF16 and C % 2 == 0:
-        # bf16 features: channel pairs packed into dwords (half the bytes through the L1), same arithmetic
-        pairs = torch.empty(2 * B * (C // 2) * h * w, device=cur.device, dtype=torch.int32)
-        call("ppea_cost_volume_fwd_bf16", ptr(cur.contiguous()), ptr(lookup.contiguous()), ptr(pairs), ptr(P),
-             ptr(inv_K.contiguous().float()), ptr(bins.contiguous().float()), ptr(skip), ptr(cost), B, C, h, w, D, float(eps),
-             stream_ptr())
-        return cost
-    cur = cur.contiguous().float()
-    lookup = lookup.contiguous().float()
-    call("ppea_cost_volume_fwd_f32", ptr(cur), ptr(lookup), ptr(P), ptr(inv_K.contiguous().float()),
-         ptr(bins.contiguous().float()), ptr(skip), ptr(cost), B, C, h, w, D, float(eps), stream_ptr())
-    return cost
-
-
+CV_BF16 = True      # bf16 features on the packed-pair form of the kernel (False: widened to fp32 first; bit-identical results)
 CV_MAX_FRAMES = 4      # up to three past frames plus the future one
+
+
+def cost_volume(cur, lookup, poses, K, inv_K, bins, eps=1e-7):
+    """One lookup frame: cur, lookup [B,C,h,w]; poses [B,4,4] (zeroed pose = skipped item); -> raw cost [B,D,h,w]."""
+    return cost_volume_multi(cur, lookup[:, None], poses[:, None], K, inv_K, bins, eps)
 
 
 @torch.no_grad()
 def cost_volume_multi(cur, lookups, poses, K, inv_K, bins, eps=1e-7):
     """cur [B,C,h,w]; lookups [B,F,C,h,w]; poses [B,F,4,4] (a zeroed pose = that frame of that item skipped);
-    -> raw cost [B,D,h,w] averaged over the frames that contribute at each (bin, pixel), in ONE launch for F > 1.
-    F = 1 is `cost_volume` (same launches, same bits)."""
+    -> raw cost [B,D,h,w] averaged over the frames that contribute at each (bin, pixel), in ONE launch."""
     B, F, C, h, w = lookups.shape
-    if F == 1:
-        return cost_volume(cur, lookups[:, 0], poses[:, 0], K, inv_K, bins, eps)
     if F > CV_MAX_FRAMES:
         raise _abi.PpeaKernelError(f"cost_volume_multi serves 1 .. {CV_MAX_FRAMES} lookup frames, got {F}")
     D = bins.shape[0]
@@ -533,6 +511,7 @@ def cost_volume_multi(cur, lookups, poses, K, inv_K, bins, eps=1e-7):
     inv_K, bins = inv_K.contiguous().float(), bins.contiguous().float()
     tail = (ptr(P), ptr(inv_K), ptr(bins), ptr(skip), ptr(cost), B, F, C, h, w, D, float(eps), stream_ptr())
     if CV_BF16 and cur.dtype == _BF16 and lookups.dtype == _BF16 and C % 2 == 0:
+        # channel pairs packed into dwords (half the bytes through the L1), same arithmetic
         cur, lookups = cur.contiguous(), lookups.contiguous()
         pairs = torch.empty((1 + F) * B * (C // 2) * h * w, device=cur.device, dtype=torch.int32)
         call("ppea_cost_volume_multi_fwd_bf16", ptr(cur), ptr(lookups), ptr(pairs), *tail)

@@ -1,5 +1,6 @@
 """`ops.cost_volume_multi`: F lookup frames in one fused launch, against the reference's own loop over the lookups
-(tests/golden/cost_volume_multi.npz), the single-frame kernel, the bf16 packed form and the CPU composite."""
+(tests/golden/cost_volume_multi.npz), the recorded bits of the former single-frame kernels for F = 1, the bf16 packed
+form and the CPU composite."""
 import pytest
 import torch
 
@@ -54,12 +55,16 @@ def _ragged(F, device, dtype=torch.bfloat16):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-def test_one_lookup_frame_is_the_single_frame_kernel(device, dtype):
+def test_one_lookup_frame_is_the_single_frame_kernel(device, golden, dtype):
+    """F = 1 of the one sweep kernel gives the bits of the dedicated single-frame kernels it replaced, recorded at the last
+    commit that had them (tests/golden/cost_volume_f1_bits.npz, tools/gen_golden_cost_volume_f1.py)."""
     from ppeadepth import ops
     cur, look, T, K, inv_K, bins = _ragged(1, device, dtype)
+    want = golden("cost_volume_f1_bits")["f32" if dtype == torch.float32 else "bf16"].to(device)
     a = ops.cost_volume_multi(cur, look, T, K, inv_K, bins)
     b = ops.cost_volume(cur, look[:, 0], T[:, 0], K, inv_K, bins)
-    assert float((a[0] != 0).float().mean()) > 0.2 and torch.equal(a, b)
+    assert float((a[0] != 0).float().mean()) > 0.2 and float(a[1].abs().max()) == 0.0          # item 1 is skipped
+    assert torch.equal(a, want) and torch.equal(b, want)
 
 
 @pytest.mark.parametrize("F", [2, 3, 4])
@@ -77,7 +82,7 @@ def test_frame_order_skip_and_bf16_pairs(device, F):
     print(f"F = {F}: fp32 kernel vs CPU composite {e:.3e}, non-zero share of item 0 {share:.2f}")
     assert e < FWD_TOL
     assert share > 0.2
-    # item 1's first frame is skipped: the other frames alone give the same bits (F = 2: the single-frame kernel)
+    # item 1's first frame is skipped: the other frames alone give the same bits (F = 2: the F = 1 instantiation)
     rest = ops.cost_volume_multi(cur[1:2].float(), look[1:2, 1:].float().contiguous(), T[1:2, 1:].contiguous(), K[1:2],
                                  inv_K[1:2], bins)
     assert torch.equal(b[1:2], rest)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The fused F-frame cost volume (`ops.cost_volume_multi`) against what the code could do before it existed: F launches of
-the single-frame kernel (`ops.cost_volume`) combined with torch ops (sum, count of `> 0`, divide).
+"""The fused F-frame cost volume (`ops.cost_volume_multi`) against what the code could do before it existed: F launches with
+one lookup frame each (`ops.cost_volume`) combined with torch ops (sum, count of `> 0`, divide).
 
     python tools/bench_cost_volume_multi.py [--calls 50] [--warmup 10] [--runs 3] [--predictor] [--out profiles/cost_volume_multi.json]
 
@@ -79,7 +79,7 @@ def kernel_cells(args, dev):
                 fused = lambda: ops.cost_volume_multi(cur, look, T, K, inv_K, bins)          # noqa: E731
                 comp = lambda: composite(cur, frames, T, K, inv_K, bins)                     # noqa: E731
                 a, b = fused(), comp()
-                # the single-frame kernel divides each frame's difference by 1 + 1e-7 first: a few ulps apart
+                # a single-frame launch divides its frame's difference by 1 + 1e-7 first: a few ulps apart
                 err = float((a - b).abs().max() / b.abs().max())
                 runs = {"fused": [], "composite": []}
                 for _ in range(args.runs):
