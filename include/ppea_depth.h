@@ -390,8 +390,18 @@ int ppea_pose_matrix_fwd_f32(const float* aa, const float* tr, float* T, int B, 
 int ppea_pose_matrix_bwd_f32(const float* aa, const float* tr, const float* dT, float* daa, float* dtr, int B, int invert,
                              void* stream);
 
+/* A14/A15: the relative poses of the F <= 4 lookup frames from P <= 4 pose-network outputs in one launch
+ * (repdepth.py:465-507), forward only (the reference computes them under no_grad).  aa, tr: HOST arrays of P device pointers;
+ * sample b of output p is the three floats at aa[p] + b * stride (stride >= 3, in floats).  pair, invert, pred: HOST arrays
+ * of F ints: frame f uses output pair[f], builds its matrix as ppea_pose_matrix_fwd_f32 does (invert[f]) and multiplies it
+ * from the left onto the relative pose of frame pred[f] < f (-1: no predecessor), each element summed over k = 0, 1, 2, 3 in
+ * that order.  keep [B][F] fp32 or NULL (keep all): 0 writes exact zeros for that (item, frame), and its successors in the chain multiply
+ * with those zeros.  T [B][F][4][4]. */
+int ppea_pose_chain_fwd_f32(const float* const* aa, const float* const* tr, int P, int stride, const int* pair,
+                            const int* invert, const int* pred, const float* keep, float* T, int B, int F, void* stream);
+
 /* ------------------------------------------------------------------------------------------
- * A21+A22  compute_reprojection_loss (trainer.py:995-1007; SSIM layers.py:226-257):
+ * A21+A22 compute_reprojection_loss (trainer.py:995-1007; SSIM layers.py:226-257):
  *      out[b,0,i,j] = alpha * mean_c SSIM(pred,target) + (1-alpha) * mean_c |target-pred|.
  *      pred/target [B,C,H,W] (H,W >= 2); out has batch stride `out_bstride` elements so the
  *      result can be written straight into one channel of a [B,2,H,W] buffer.

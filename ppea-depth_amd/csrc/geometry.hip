@@ -263,12 +263,62 @@ __device__ __forceinline__ float fsqrt(const float& a) { return sqrtf(a); }
 __device__ __forceinline__ float fsin(const float& a) { return sinf(a); }
 __device__ __forceinline__ float fcos(const float& a) { return cosf(a); }
 
+// the fp32 forward of one sample: aa, tr point at its three axis-angle / translation components
+__device__ __forceinline__ void pose_matrix_f32(const float* __restrict__ aa, const float* __restrict__ tr, int invert, float (&M)[16]) {
+    pose_matrix<float>(aa[0], aa[1], aa[2], tr[0], tr[1], tr[2], invert, M, fconst, fsqrt, fsin, fcos);
+}
+
 __global__ void pose_matrix_fwd(const float* __restrict__ aa, const float* __restrict__ tr, float* __restrict__ T, int B, int invert) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     float M[16];
-    pose_matrix<float>(aa[3 * b], aa[3 * b + 1], aa[3 * b + 2], tr[3 * b], tr[3 * b + 1], tr[3 * b + 2], invert, M, fconst, fsqrt, fsin, fcos);
+    pose_matrix_f32(aa + 3 * b, tr + 3 * b, invert, M);
     for (int i = 0; i < 16; ++i) T[16 * b + i] = M[i];
+}
+
+// ---- relative poses of the F lookup frames in one launch (repdepth.py:465-507) -----------------------------------------
+// Frame f takes the pose network's output of pair c.pair[f] (sample b at aa[pair] + b * stride), builds its matrix with
+// pose_matrix_f32 (c.invert[f]), multiplies it from the left onto the relative pose of its predecessor c.pred[f] (-1: none)
+//     T(f)[i][j] = ((A[i][0] P[0][j] + A[i][1] P[1][j]) + A[i][2] P[2][j]) + A[i][3] P[3][j]       (k = 0, 1, 2, 3)
+// and is then masked with keep[b][f] (NULL: keep all): a flagged-off entry is exact zeros, and the MASKED matrix is what its successors
+// multiply with (the reference masks inputs[("relative_pose", f)] before the next frame reads it).  One thread per batch
+// item walks the chain in frame order (pred[f] < f), every matrix in registers.  The chain description travels by value.
+#define POSE_CHAIN_MAX 4
+struct PoseChain {
+    const float* aa[POSE_CHAIN_MAX];
+    const float* tr[POSE_CHAIN_MAX];
+    int pair[POSE_CHAIN_MAX], invert[POSE_CHAIN_MAX], pred[POSE_CHAIN_MAX];
+};
+
+template <int F>
+__global__ void pose_chain_fwd(PoseChain c, const float* __restrict__ keep, float* __restrict__ T, int B, int stride) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    float R[F][16];
+#pragma unroll
+    for (int f = 0; f < F; ++f) {
+        float A[16];
+        pose_matrix_f32(c.aa[c.pair[f]] + (long)b * stride, c.tr[c.pair[f]] + (long)b * stride, c.invert[f], A);
+        const bool on = keep == nullptr || keep[b * F + f] != 0.f;
+#pragma unroll
+        for (int g = 0; g < F; ++g) {
+            if (g < f && c.pred[f] == g) {
+                float P[16];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+                        P[4 * i + j] = ((A[4 * i] * R[g][j] + A[4 * i + 1] * R[g][4 + j]) + A[4 * i + 2] * R[g][8 + j]) + A[4 * i + 3] * R[g][12 + j];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) A[i] = P[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            R[f][i] = on ? A[i] : 0.f;
+            T[((long)b * F + f) * 16 + i] = R[f][i];
+        }
+    }
 }
 __global__ void pose_matrix_bwd(const float* __restrict__ aa, const float* __restrict__ tr, const float* __restrict__ dT,
                                 float* __restrict__ daa, float* __restrict__ dtr, int B, int invert) {
@@ -347,6 +397,36 @@ int ppea_pose_matrix_fwd_f32(const float* aa, const float* tr, float* T, int B, 
     if (B == 0) return 0;
     if (!aa || !tr || !T) return PPEA_ERR_ARG;
     hipLaunchKernelGGL(pose_matrix_fwd, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, aa, tr, T, B, invert);
+    return launch_status();
+}
+// Relative poses of F lookup frames from P pose-network outputs (see pose_chain_fwd).  aa, tr: HOST arrays of P device
+// pointers; pair, invert, pred: HOST arrays of F ints -- everything but keep and T is copied into the launch's arguments.
+int ppea_pose_chain_fwd_f32(const float* const* aa, const float* const* tr, int P, int stride, const int* pair,
+                            const int* invert, const int* pred, const float* keep, float* T, int B, int F, void* stream) {
+    if (B < 0 || F < 1 || F > POSE_CHAIN_MAX || P < 1 || P > POSE_CHAIN_MAX) return PPEA_ERR_UNSUPPORTED;
+    if (!aa || !tr || !pair || !invert || !pred || stride < 3) return PPEA_ERR_ARG;
+    PoseChain c = {};
+    for (int p = 0; p < P; ++p) {
+        if (!aa[p] || !tr[p]) return PPEA_ERR_ARG;
+        c.aa[p] = aa[p];
+        c.tr[p] = tr[p];
+    }
+    for (int f = 0; f < F; ++f) {
+        if (pair[f] < 0 || pair[f] >= P || pred[f] < -1 || pred[f] >= f) return PPEA_ERR_ARG;
+        c.pair[f] = pair[f];
+        c.invert[f] = invert[f] != 0;
+        c.pred[f] = pred[f];
+    }
+    if (B == 0) return 0;
+    if (!T) return PPEA_ERR_ARG;
+    const dim3 g((B + 63) / 64), blk(64);
+    hipStream_t s = (hipStream_t)stream;
+    switch (F) {
+        case 1: hipLaunchKernelGGL(pose_chain_fwd<1>, g, blk, 0, s, c, keep, T, B, stride); break;
+        case 2: hipLaunchKernelGGL(pose_chain_fwd<2>, g, blk, 0, s, c, keep, T, B, stride); break;
+        case 3: hipLaunchKernelGGL(pose_chain_fwd<3>, g, blk, 0, s, c, keep, T, B, stride); break;
+        default: hipLaunchKernelGGL(pose_chain_fwd<4>, g, blk, 0, s, c, keep, T, B, stride); break;
+    }
     return launch_status();
 }
 int ppea_pose_matrix_bwd_f32(const float* aa, const float* tr, const float* dT, float* daa, float* dtr, int B, int invert,

@@ -488,11 +488,21 @@ class TrainEngine:
         so the graph's addresses stay valid) -- the first replay is then step 1 of the run."""
         from . import rng
         from ._abi import PpeaKernelError
-        ids = list(self.trainer._module().matching_ids)
-        if ids != [0, -1]:
-            # the captured step's stream plan (pose network replayed on the adapter stream) is verified for one lookup frame
-            raise PpeaKernelError(f"the captured training step serves matching_ids [0, -1], the model has {ids}: "
+        module = self.trainer._module()
+        ids = list(module.matching_ids)
+        if module.pose_plan() is None:
+            # the captured step's stream plan keeps ALL pose work (gradient passes, replays, the new no_grad passes and the
+            # pose chain) on the adapter side stream, joined once where the cost volume asks for the relative poses: that is
+            # the batched pose path (repdepth.pose_pair_plan); the sequential one is not verified under capture
+            raise PpeaKernelError(f"the captured training step needs the batched pose path (frame_ids [0, -1, 1]); the "
+                                  f"model has frame_ids {list(self.trainer.opt.frame_ids)}, matching_ids {ids}: "
                                   "train with eager steps (TrainEngine.step without capture)")
+        if ids != [0, -1] and world_size() > 1:
+            raise PpeaKernelError(f"the captured step with matching_ids {ids} is verified on one rank only: "
+                                  "train with eager steps on several ranks")
+        missing = [f for f in ids if ("color_aug", f, 0) not in inputs]
+        if missing:
+            raise PpeaKernelError(f"capture: the batch has no ('color_aug', f, 0) for the matching frames {missing}")
         dev = self.params[0].device
         snap = self.snapshot() if restore_state else None
         self.static_inputs = {k: v.clone() for k, v in inputs.items()}

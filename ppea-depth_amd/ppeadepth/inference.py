@@ -27,7 +27,7 @@ import torch.nn.functional as F
 
 from . import ops
 from ._abi import PpeaKernelError
-from .layers import transformation_from_parameters
+from .layers import pose_chain
 from .ops import ACT_GELU, ACT_NONE, ACT_RELU
 
 
@@ -324,13 +324,9 @@ class DepthPredictor:
         pairs = [torch.cat([frames[f], frames[f + 1]] if f < 0 else [frames[f - 1], frames[f]], 1) for f in ids]
         x = self._pose_features(pairs[0] if len(pairs) == 1 else torch.cat(pairs, 0))
         axisangle, translation = self.model.pose([[x]])
-        rel = {}
-        for j, f in enumerate(ids):          # (+1,) -1, -2, ...: the neighbour towards frame 0 comes first
-            T = transformation_from_parameters(axisangle[j * B:(j + 1) * B, 0].float(),
-                                               translation[j * B:(j + 1) * B, 0].float(), invert=f < 0)
-            near = f + 1 if f < 0 else f - 1
-            rel[f] = T if near == 0 else torch.matmul(T, rel[near])
-        return torch.stack([rel[f] for f in ids], 1) if len(ids) > 1 else rel[ids[0]][:, None]
+        # (+1,) -1, -2, ...: the neighbour towards frame 0 comes first; one launch on the device (ops.pose_chain)
+        return pose_chain([(axisangle[j * B:(j + 1) * B, 0], translation[j * B:(j + 1) * B, 0]) for j in range(len(ids))],
+                          [(j, f < 0, -1 if f in (-1, 1) else ids.index(f + 1 if f < 0 else f - 1)) for j, f in enumerate(ids)])
 
     # ---- public ---------------------------------------------------------------------------------------------------
     def _ctx(self):

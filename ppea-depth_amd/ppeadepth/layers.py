@@ -64,6 +64,24 @@ def transformation_from_parameters(axisangle, translation, invert=False):
     return torch.matmul(R, T) if invert else torch.matmul(T, R)
 
 
+@torch.no_grad()
+def pose_chain(pairs, chain, keep=None):
+    """Relative poses [B,F,4,4] of F lookup frames from the pose network's per-pair outputs (repdepth.py:465-507): `pairs`
+    [(axisangle, translation)] each [B,1,3]; `chain` per frame (pair index, invert, position of its predecessor in `chain`
+    or -1); `keep` [B,F], zero = missing frame -> zero pose, which its successors are multiplied onto, as in the reference.
+    On the device: one launch (`ops.pose_chain`); the composite below on the host."""
+    if pairs[0][0].is_cuda:
+        from . import ops
+        return ops.pose_chain(pairs, chain, keep)
+    rel = []
+    for j, (p, invert, pred) in enumerate(chain):
+        T = transformation_from_parameters(pairs[p][0].float(), pairs[p][1].float(), invert=invert)
+        if pred >= 0:
+            T = torch.matmul(T, rel[pred])
+        rel.append(T if keep is None else T * keep[:, j].to(T.dtype)[:, None, None])
+    return torch.stack(rel, 1)
+
+
 def upsample(x):
     """layers.py:204-207.  Nearest-neighbour copy: run it in the tensor's own dtype (autocast would widen a
     bf16 activation to fp32 here and every consumer down to the next conv would move twice the bytes)."""

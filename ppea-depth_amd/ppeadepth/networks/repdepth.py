@@ -6,6 +6,7 @@ reference's.  Host-side differences: no per-item `.sum() == 0` device syncs (don
 the matching augmentation is applied with batched index ops, and BN bookkeeping of the whole
 forward is flushed in a handful of multi-tensor kernels.
 """
+import collections
 import os
 
 import numpy as np
@@ -15,7 +16,7 @@ import torch.nn.functional as F
 
 from .. import ops, rng
 from ..batchnorm import DeferredStats, set_deferred
-from ..layers import transformation_from_parameters
+from ..layers import pose_chain, transformation_from_parameters
 from .depth_decoder_v2 import DepthDecoderV2
 from .pose_decoder import PoseDecoder
 from .replk_matching_adapter import RepLKMatchingAdapter
@@ -29,12 +30,53 @@ TWO_STREAMS = True
 POSE_SIDE = os.environ.get("PPEA_POSE_SIDE", "1") == "1"     # pose network (forward and backward) on the adapter side stream
 POSE_SIDE_INLINE0 = os.environ.get("PPEA_POSE_SIDE_INLINE0", "1") == "1"
 ASYNC_FLUSH = os.environ.get("PPEA_ASYNC_FLUSH", "1") == "1"   # deferred running-statistics update beside the loss
-BATCHED_POSES = True      # third (no_grad) pose pass replayed instead of recomputed (see _predict_poses_batched)
+BATCHED_POSES = True      # no_grad pose passes on a gradient pass's pair replayed instead of recomputed (see _predict_poses_batched)
 POSE_ONE_BATCH = True      # both pairs as one 2B batch with per-pair BN statistics (needs the fused NHWC BN path)
+NEW_PASSES_ONE_BATCH = False   # the no_grad passes on NEW pairs, (-2, -1), (-3, -2), as one groups = n batch (DESIGN: measured)
 
 
 def _g(opt, name, default):
     return getattr(opt, name, default)
+
+
+PoseFrame = collections.namedtuple("PoseFrame", "frame pair invert pred replay")
+PosePlan = collections.namedtuple("PosePlan", "pairs frames updates")
+
+
+def pose_pair_plan(frame_ids, matching_ids):
+    """What `predict_poses` (repdepth.py:443-509) has to compute for the lookup frames `matching_ids[1:]`, as data.
+
+    pairs: the distinct pose-network inputs (first frame, second frame), in temporal order: the gradient passes of
+        `frame_ids[1:]` first -- (f, 0) for f < 0, (0, f) for f > 0 -- then every further pair in `matching_ids[1:]` order.
+    frames: per lookup frame a PoseFrame(frame, pair index, invert, pred, replay).  Frame f < 0 needs pair (f, f + 1)
+        inverted, frame f > 0 pair (f - 1, f); `pred` is the position in `frames` of the neighbour towards frame 0 whose
+        relative pose the pair's matrix is multiplied onto (-1 for f = -1 / +1); `replay` says that the pair is one of the
+        gradient passes: same input, same weights, so its no_grad pass is not run again -- the outputs are the gradient
+        pass's and only its BatchNorm running-statistics update is repeated.
+    updates: every running-statistics update of the pose encoder, in the reference's order, as (kind, pair index): "grad"
+        for the gradient passes in `frame_ids[1:]` order, then per lookup frame in `matching_ids[1:]` order "replay" or
+        "new" (a real no_grad pass).  Running statistics are a momentum chain, so this order is observable.
+    Raises ValueError for what the batched pose path does not serve."""
+    frame_ids, matching_ids = [f for f in frame_ids], [int(f) for f in matching_ids]
+    if frame_ids != [0, -1, 1]:
+        raise ValueError(f"the batched pose path serves frame_ids [0, -1, 1], not {frame_ids}")
+    lookups = matching_ids[1:]
+    if matching_ids[:1] != [0] or not 1 <= len(lookups) <= ops.POSE_CHAIN_MAX or len(set(lookups)) != len(lookups) or 0 in lookups:
+        raise ValueError(f"matching_ids {matching_ids}: frame 0 and 1..{ops.POSE_CHAIN_MAX} distinct lookup frames")
+    pairs = [(f, 0) if f < 0 else (0, f) for f in frame_ids[1:]]
+    n_grad = len(pairs)
+    updates = [("grad", p) for p in range(n_grad)]
+    frames = []
+    for j, f in enumerate(lookups):
+        pair, near = ((f, f + 1), f + 1) if f < 0 else ((f - 1, f), f - 1)
+        if near != 0 and near not in lookups[:j]:
+            raise ValueError(f"matching_ids {matching_ids}: frame {f} is chained onto frame {near}, which must come before it")
+        if pair not in pairs:
+            pairs.append(pair)
+        p = pairs.index(pair)
+        frames.append(PoseFrame(f, p, f < 0, -1 if near == 0 else lookups.index(near), p < n_grad))
+        updates.append(("replay" if p < n_grad else "new", p))
+    return PosePlan(pairs, frames, updates)
 
 
 class RepDepth(nn.Module):
@@ -151,48 +193,79 @@ class RepDepth(nn.Module):
             replknet_adapter.NO_FORK_ON.add(st.cuda_stream)
         return st
 
+    def pose_plan(self):
+        """`pose_pair_plan` of this model, or None where the batched pose path does not serve it (other `frame_ids`)."""
+        key = (tuple(self.opt.frame_ids), tuple(self.matching_ids))
+        if getattr(self, "_pose_plan_key", None) != key:
+            try:
+                self._pose_plan = pose_pair_plan(self.opt.frame_ids, self.matching_ids)
+            except ValueError:
+                self._pose_plan = None
+            self._pose_plan_key = key
+        return self._pose_plan
+
     def predict_poses(self, inputs):
-        if (BATCHED_POSES and self.training and list(self.opt.frame_ids) == [0, -1, 1]
-                and list(self.matching_ids) == [0, -1]):
+        if BATCHED_POSES and self.training and self.pose_plan() is not None:
             return self._predict_poses_batched(inputs)
         return self._predict_poses_sequential(inputs)
 
     def _predict_poses_batched(self, inputs):
-        """The reference runs the pose network three times per step: pairs (-1, 0) and (0, +1) with gradients, then
-        (-1, 0) AGAIN without, for the matching frame (repdepth.py:443-509).  The third pass has the same input and
-        the same weights as the first, so its outputs are the first pass's and the only thing it changes is one more
-        BatchNorm running-statistics update with the first pass's batch statistics: that update is replayed
-        (GroupBN.replay_update) and the pass itself is skipped.  POSE_ONE_BATCH additionally sends both pairs through
-        the network as one 2B batch with per-sub-batch statistics (measured slower: the per-layer concatenations
-        cost more than the halved launch count saves)."""
+        """The reference runs the pose network once per frame of `frame_ids[1:]` with gradients -- pairs (-1, 0) and
+        (0, +1) -- and then once more per lookup frame without (repdepth.py:443-509).  A no_grad pass on (-1, 0) or (0, +1)
+        has the same input and the same weights as a gradient pass, so its outputs are that pass's and the only thing it
+        changes is one more BatchNorm running-statistics update with that pass's batch statistics: the update is replayed
+        (GroupBN.replay_update) and the pass itself is skipped.  Only the pairs (-k - 1, -k), k >= 1, are new passes
+        (`pose_pair_plan`).  Replays and new passes happen in the reference's order.  One `ops.pose_chain` launch then
+        turns the per-pair outputs into every lookup frame's relative pose.  POSE_ONE_BATCH additionally sends both
+        gradient pairs through the network as one 2B batch with per-sub-batch statistics."""
+        plan = self.pose_plan()
         outputs = {}
-        f = {i: inputs[("color_aug", i, 0)] for i in (0, -1, 1)}
+        f = {i: inputs[("color_aug", i, 0)] for i in {i for pr in plan.pairs for i in pr}}
         B = f[0].shape[0]
-        pairs = {-1: torch.cat([f[-1], f[0]], 1), 1: torch.cat([f[0], f[1]], 1)}
+        pairs = [torch.cat([f[a], f[b]], 1) for a, b in plan.pairs]
+        enc = self.pose_encoder
         if POSE_ONE_BATCH:
-            aa2, tt2 = self.pose([self.pose_encoder(torch.cat([pairs[-1], pairs[1]], 0), groups=2, record=True)])
-            res = {-1: (aa2[:B], tt2[:B]), 1: (aa2[B:], tt2[B:])}
-            recorded = self.pose_encoder.recorded
+            aa2, tt2 = self.pose([enc(torch.cat(pairs[:2], 0), groups=2, record=True)])
+            res = [(aa2[:B], tt2[:B]), (aa2[B:], tt2[B:])]
+            recorded, enc.recorded, enc.recorded_groups = enc.recorded_groups, None, None
+            stats = None
         else:
-            snap = self.pose_encoder.snapshot_running()
-            res = {-1: self.pose([self.pose_encoder(pairs[-1])])}
-            stats_a = self.pose_encoder.batch_stats_since(snap)
-            res[1] = self.pose([self.pose_encoder(pairs[1])])
-            recorded = None
-        for f_i in (-1, 1):
-            aa, tt = res[f_i]
+            res, stats = [], []
+            for p in range(2):                                   # (the batch statistics only of a pair that is replayed)
+                snap = enc.snapshot_running() if ("replay", p) in plan.updates else None
+                res.append(self.pose([enc(pairs[p])]))
+                stats.append(enc.batch_stats_since(snap) if snap is not None else None)
+        for p, f_i in enumerate(self.opt.frame_ids[1:]):
+            aa, tt = res[p]
             outputs[("axisangle", 0, f_i)] = aa
             outputs[("translation", 0, f_i)] = tt
             outputs[("cam_T_cam", 0, f_i)] = transformation_from_parameters(aa[:, 0], tt[:, 0], invert=(f_i < 0))
         with torch.no_grad():
-            if recorded is not None:                                          # the no_grad pass on pair (-1, 0)
-                replay_updates(recorded)
-                self.pose_encoder.recorded = None
-            else:
-                self.pose_encoder.replay_pass(stats_a)
-            pose = outputs[("cam_T_cam", 0, -1)].detach()
-            present = (f[-1].flatten(1).sum(1) != 0).to(pose.dtype)
-            inputs[("relative_pose", -1)] = pose * present[:, None, None]
+            new = [p for kind, p in plan.updates if kind == "new"]
+            # one groups = n batch updates the running statistics sub-batch by sub-batch: the reference's order as long as
+            # no replay sits between two new passes
+            grouped = (NEW_PASSES_ONE_BATCH and len(new) > 1 and f[0].is_cuda
+                       and all(kind == "new" for kind, _ in plan.updates[-len(new):]))
+            for kind, p in plan.updates[2:]:
+                if kind == "replay":
+                    if stats is None:
+                        replay_updates(recorded[p])
+                    else:
+                        enc.replay_pass(stats[p])
+                elif not grouped:
+                    res.append(self.pose([enc(pairs[p])]))
+                elif p == new[0]:
+                    aan, ttn = self.pose([enc(torch.cat([pairs[q] for q in new], 0), groups=len(new))])
+                    res += [(aan[i * B:(i + 1) * B], ttn[i * B:(i + 1) * B]) for i in range(len(new))]
+            ids = [fr.frame for fr in plan.frames]
+            looks = f[ids[0]][:, None] if len(ids) == 1 else torch.stack([inputs[("color_aug", i, 0)] for i in ids], 1)
+            # missing (all-zero) lookup image -> zero pose; as a [B,F] mask, without a host sync per item
+            present = (looks.flatten(2).sum(2) != 0).to(torch.float32)
+            used = sorted({fr.pair for fr in plan.frames})
+            rel = pose_chain([(res[p][0][:, 0].detach(), res[p][1][:, 0].detach()) for p in used],
+                                 [(used.index(fr.pair), fr.invert, fr.pred) for fr in plan.frames], present)
+            for j, i in enumerate(ids):
+                inputs[("relative_pose", i)] = rel[:, j]
         return outputs
 
     def _predict_poses_sequential(self, inputs):

@@ -184,7 +184,8 @@ class ResnetEncoder(nn.Module):
 
     def forward(self, input_image, groups=1, record=False):
         """groups > 1: the batch is `groups` consecutive sub-batches with separate BatchNorm statistics (see GroupBN);
-        record: keep the first sub-batch's statistics in `self.recorded` [(bn, mean, invstd, count)]."""
+        record: keep every sub-batch's statistics in `self.recorded_groups` [group][(bn, mean, invstd, count)] (and the
+        first sub-batch's in `self.recorded`)."""
         e = self.encoder
         bns = [m for m in e.modules() if isinstance(m, GroupBN)]
         for m in bns:
@@ -194,7 +195,8 @@ class ResnetEncoder(nn.Module):
             feats = self._forward(input_image)
         finally:
             if record:
-                self.recorded = [(m,) + m.record[0] for m in bns if m.record]
+                self.recorded_groups = [[(m,) + m.record[g] for m in bns if len(m.record) == groups] for g in range(groups)]
+                self.recorded = self.recorded_groups[0]
             for m in bns:
                 m.groups, m.record = 1, None
         return feats

@@ -1528,6 +1528,47 @@ def pose_matrix(axisangle, translation, invert=False):
     return _PoseMatrix.apply(axisangle.reshape(-1, 3).float(), translation.reshape(-1, 3).float(), bool(invert))
 
 
+POSE_CHAIN_MAX = 4        # csrc/geometry.hip POSE_CHAIN_MAX: lookup frames and pose-network outputs per launch
+
+
+@torch.no_grad()
+def pose_chain(pairs, chain, keep=None):
+    """Relative poses of the F lookup frames in one launch (repdepth.py:465-507; no gradient, as in the reference).
+    pairs: P <= 4 pose-network outputs (axisangle, translation), each [B,1,3] or [B,3] on the device (views with a
+    batch stride are read in place); chain: per frame (index into `pairs`, invert, index of the predecessor FRAME in
+    `chain` or -1), predecessors first; keep: [B,F], zero = that (item, frame) is written as exact zeros and so is every
+    frame chained behind it (None: keep all).  -> [B,F,4,4] fp32, T(f) = T_pair(f) @ T(pred(f))."""
+    P, Fr = len(pairs), len(chain)
+    if not (1 <= P <= POSE_CHAIN_MAX and 1 <= Fr <= POSE_CHAIN_MAX):
+        raise PpeaKernelError(f"pose_chain serves 1..{POSE_CHAIN_MAX} pairs and frames, got {P} and {Fr}")
+    for f, (p, _inv, pred) in enumerate(chain):
+        if not (0 <= p < P and -1 <= pred < f):
+            raise PpeaKernelError(f"pose_chain: frame {f} names pair {p} / predecessor {pred}")
+    B = pairs[0][0].shape[0]
+    flat = [t.reshape(B, 3) for pr in pairs for t in pr]          # views: [B,1,3] -> [B,3] keeps the batch stride
+    dev = flat[0].device
+    stride = flat[0].stride(0) if B > 1 else 3
+    in_place = all(t.is_cuda and t.dtype == _F32 and t.stride(1) == 1 and (B <= 1 or t.stride(0) == stride) and stride >= 3
+                   for t in flat)
+    if not in_place:
+        flat = [t.float().contiguous() for t in flat]
+        stride = 3
+    for t in flat:
+        if not t.is_cuda or t.device != dev:
+            raise PpeaKernelError("PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback)")
+    keep = None if keep is None else keep.to(_F32).contiguous()
+    if keep is not None and keep.shape != (B, Fr):
+        raise PpeaKernelError(f"pose_chain: keep {tuple(keep.shape)} for B = {B}, F = {Fr}")
+    if keep is not None and keep.device != dev:
+        raise PpeaKernelError("pose_chain: keep is on another device")
+    T = torch.empty(B, Fr, 4, 4, device=dev, dtype=_F32)
+    vps, ints = _ct.c_void_p * P, _ct.c_int * Fr
+    call("ppea_pose_chain_fwd_f32", vps(*(t.data_ptr() for t in flat[0::2])), vps(*(t.data_ptr() for t in flat[1::2])), P,
+         stride, ints(*(c[0] for c in chain)), ints(*(int(bool(c[1])) for c in chain)), ints(*(c[2] for c in chain)),
+         ptr(keep), ptr(T), B, Fr, stream_ptr())
+    return T
+
+
 def tapsum_fwd(T, bias, Ch):
     B, _, H, W = T.shape
     pre = torch.empty(B, Ch, H, W, device=T.device, dtype=_BF16)

@@ -176,7 +176,7 @@ class Trainer:
         single-frame teacher; model in eval mode.
         -> (scaled multi-frame disparity [B,H,W], scaled teacher disparity or None), as `disp_to_depth(., 1e-3, 80)`.
         predictor: an `inference.DepthPredictor` of this model -- the same outputs from its fused schedule."""
-        from .layers import transformation_from_parameters
+        from .layers import pose_chain
         model = self._module()
         dev = self.device
         ids = [int(f) for f in model.matching_ids[1:]]
@@ -198,12 +198,16 @@ class Trainer:
         ctx = torch.autocast("cuda", dtype=self.amp_dtype) if self.amp_dtype is not None else contextlib.nullcontext()
         color = {f: data[("color", f, 0)].to(dev) for f in [0] + ids}
         with ctx:
+            pairs, chain = [], []
             for f in ids:                 # (+1,) -1, -2, ...: the neighbour towards frame 0 is done first
                 near = f + 1 if f < 0 else f - 1
                 feats = [model.pose_encoder(torch.cat([color[f], color[near]] if f < 0 else [color[near], color[f]], 1))]
                 axisangle, translation = model.pose(feats)
-                pose = transformation_from_parameters(axisangle[:, 0].float(), translation[:, 0].float(), invert=f < 0)
-                data[("relative_pose", f)] = pose if near == 0 else torch.matmul(pose, data[("relative_pose", near)])
+                pairs.append((axisangle[:, 0], translation[:, 0]))
+                chain.append((len(chain), f < 0, -1 if near == 0 else ids.index(near)))
+            rel = pose_chain(pairs, chain)             # [B,F,4,4]: one launch on the device (ops.pose_chain)
+            for j, f in enumerate(ids):
+                data[("relative_pose", f)] = rel[:, j]
             tracker = self.depth_bin_tracker
             if getattr(self.opt, "notadabins", False):
                 mn, mx = tracker.min_depth, tracker.max_depth
@@ -212,8 +216,7 @@ class Trainer:
             one = len(ids) == 1
             feats, _lowest, _conf = model.encoder(
                 color[0], color[ids[0]][:, None] if one else torch.stack([color[f] for f in ids], 1),
-                data[("relative_pose", ids[0])][:, None] if one else torch.stack([data[("relative_pose", f)] for f in ids], 1),
-                data[("K", 2)].to(dev), data[("inv_K", 2)].to(dev), mn, mx)
+                rel, data[("K", 2)].to(dev), data[("inv_K", 2)].to(dev), mn, mx)
             disp = model.depth(feats)[("disp", 0)].float()
             pred, _ = disp_to_depth(disp, MIN_VAL_EVAL, 80)
             pred_mono = None
