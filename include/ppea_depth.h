@@ -400,6 +400,15 @@ int ppea_pose_matrix_bwd_f32(const float* aa, const float* tr, const float* dT, 
 int ppea_pose_chain_fwd_f32(const float* const* aa, const float* const* tr, int P, int stride, const int* pair,
                             const int* invert, const int* pred, const float* keep, float* T, int B, int F, void* stream);
 
+/* The same chain on a video stream: ring [F][B][2][3] fp32 holds the pose decoder's raw (axisangle, translation) of the pairs
+ * of consecutive frames, pair (t-j-1, t-j) at slot (head - j) mod F with head = state[0] (state [1 + B] int32 on the device,
+ * as for ppea_cost_volume_ring_fwd_*).  aa_new / tr_new (sample b at + b * stride floats; both NULL: none) is the newest
+ * pair and is stored into slot head first.  T(0 -> -1) = inv(pair 0), T(0 -> -(j+1)) = inv(pair j) @ T(0 -> -j), the
+ * arithmetic of ppea_pose_chain_fwd_f32; exact zeros and present[b][j] = 0 where state[1 + b] <= j.  T [B][F][4][4],
+ * present [B][F] bytes. */
+int ppea_pose_chain_ring_fwd_f32(const float* aa_new, const float* tr_new, int stride, float* ring, const int32_t* state,
+                                 float* T, uint8_t* present, int B, int F, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * A21+A22 compute_reprojection_loss (trainer.py:995-1007; SSIM layers.py:226-257):
  *      out[b,0,i,j] = alpha * mean_c SSIM(pred,target) + (1-alpha) * mean_c |target-pred|.
@@ -568,6 +577,27 @@ int ppea_cost_volume_multi_fwd_f32(const float* cur, const float* lookup, const 
 int ppea_cost_volume_multi_fwd_bf16(const void* cur, const void* lookup, void* pairs, const float* P, const float* inv_K,
                                     const float* bins, const int32_t* skip, float* cost, int B, int F, int C, int h, int w,
                                     int D, float eps, void* stream);
+/* Video streaming (DepthPredictor.stream): the lookups are the last F frames, kept in a device ring.
+ *      state [1 + B] int32 on the device: state[0] = head slot (taken mod F), state[1 + b] = frames item b has seen since its
+ *      reset, clamped at F.  No entry below reads it on the host.
+ *      ppea_cost_volume_ring_fwd_*: ppea_cost_volume_multi_fwd_* with lookup frame f of item b at slot (head - 1 - f) mod F of
+ *      ring [F,B,C,h,w]; the frame is skipped where seen[b] <= f or skip[b][f] != 0 (skip may be NULL).  Same kernel, same bits
+ *      as the multi entry on the frames gathered in order.  bf16: `cur_pairs` [B,C/2,h,w] and `ring_pairs` [F,B,C/2,h,w] are
+ *      channel-pair dwords already (ppea_cv_ring_store_bf16 writes both).
+ *      ppea_cv_ring_store_*: src [B,C,h,w] -> slot head of dst [F,B,..] (bf16: packed to channel pairs, C even); state NULL:
+ *      dst is a plain [B,..] buffer.
+ *      ppea_cv_ring_advance: head <- (head + 1) mod F, seen[b] <- min(seen[b] + 1, F); enqueue after the sweep and the store. */
+int ppea_cost_volume_ring_fwd_f32(const float* cur, const float* ring, const int32_t* state, const float* P,
+                                  const float* inv_K, const float* bins, const int32_t* skip, float* cost, int B, int F,
+                                  int C, int h, int w, int D, float eps, void* stream);
+int ppea_cost_volume_ring_fwd_bf16(const void* cur_pairs, const void* ring_pairs, const int32_t* state, const float* P,
+                                   const float* inv_K, const float* bins, const int32_t* skip, float* cost, int B, int F,
+                                   int C, int h, int w, int D, float eps, void* stream);
+int ppea_cv_ring_store_f32(const float* src, float* dst, const int32_t* state, int B, int F, int C, int h, int w,
+                           void* stream);
+int ppea_cv_ring_store_bf16(const void* src, void* dst, const int32_t* state, int B, int F, int C, int h, int w,
+                            void* stream);
+int ppea_cv_ring_advance(int32_t* state, int B, int F, void* stream);
 int ppea_cost_volume_reduce_f32(const float* cost, const float* bins, float* cost_out,
                                 float* confidence, int64_t* argmin, float* lowest,
                                 int B, int D, int h, int w, void* stream);

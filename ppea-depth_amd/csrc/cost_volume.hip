@@ -49,13 +49,25 @@ __device__ __forceinline__ void cv_accum(double& acc, T v00, T v01, T v10, T v11
     }
 }
 
-template <int F, int DB, bool PK>
+// Head slot of a feature / pose ring of F slots from the device-side stream state (state[0]; state[1 + b]: frames item b
+// has seen since its reset, clamped at F).  Brought into 0 .. F - 1 whatever the word holds: it becomes an address.
+__device__ __forceinline__ int ring_head(const int32_t* __restrict__ state, int F) {
+    const int hd = state[0] % F;
+    return hd < 0 ? hd + F : hd;
+}
+
+// RING: `lookup` is a ring [F][B][CE][hw] of the last F frames' features and frame f of item b is slot (head - 1 - f) mod F
+// (video streaming: the newest frame sits just behind the head); the frame is skipped where seen[b] <= f, or-ed with the
+// zero-pose flag skip[b][f] (NULL: none).  Otherwise `lookup` is [B][F][CE][hw].  Only where a frame's map starts differs:
+// a block-uniform address per frame, found once before the channel loop.
+template <int F, int DB, bool PK, bool RING>
 __global__ __launch_bounds__(256) void cost_volume_fwd(const typename CvFeat<PK>::T* __restrict__ cur,
                                                        const typename CvFeat<PK>::T* __restrict__ lookup,
                                                        const float* __restrict__ P,       // [B][F][3][4]
                                                        const float* __restrict__ inv_K,
                                                        const float* __restrict__ bins,
                                                        const int32_t* __restrict__ skip,  // [B][F]
+                                                       const int32_t* __restrict__ state, // RING: [1 + B]
                                                        float* __restrict__ cost, int C, int h, int w, int D,
                                                        float eps) {
     using T = typename CvFeat<PK>::T;
@@ -66,9 +78,22 @@ __global__ __launch_bounds__(256) void cost_volume_fwd(const typename CvFeat<PK>
     float* outp = cost + ((long)b * D + d0) * hw + i;
     const int nd = min(DB, D - d0);
     const int py = i / w, px = i - py * w;
-    bool any = false;                                  // same in every lane
+    const T* fb[F];                                    // frame f's map of item b; same in every lane, like fskip and any
+    bool fskip[F];
+    bool any = false;
 #pragma unroll
-    for (int f = 0; f < F; ++f) any = any || skip[b * F + f] == 0;
+    for (int f = 0; f < F; ++f) {
+        if constexpr (RING) {
+            int slot = ring_head(state, F) - 1 - f;
+            if (slot < 0) slot += F;
+            fb[f] = lookup + ((long)slot * gridDim.z + b) * CE * hw;
+            fskip[f] = state[1 + b] <= f || (skip != nullptr && skip[b * F + f] != 0);
+        } else {
+            fb[f] = lookup + ((long)b * F + f) * CE * hw;
+            fskip[f] = skip[b * F + f] != 0;
+        }
+        any = any || !fskip[f];
+    }
     if (!any || px < 2 || px >= w - 2 || py < 2 || py >= h - 2) {
         for (int k = 0; k < nd; ++k) outp[(long)k * hw] = 0.f;
         return;
@@ -86,12 +111,11 @@ __global__ __launch_bounds__(256) void cost_volume_fwd(const typename CvFeat<PK>
 #pragma unroll
     for (int f = 0; f < F; ++f) {
         const float* pm = P + ((long)b * F + f) * 12;
-        const bool fskip = skip[b * F + f] != 0;
 #pragma unroll
         for (int k = 0; k < DB; ++k) {
             off[f][k] = -1;
             w00[f][k] = w01[f][k] = w10[f][k] = w11[f][k] = 0.f;
-            if (fskip || k >= nd) continue;
+            if (fskip[f] || k >= nd) continue;
             const float depth = bins[d0 + k];
             float X[3], cam[3];
 #pragma unroll
@@ -114,7 +138,7 @@ __global__ __launch_bounds__(256) void cost_volume_fwd(const typename CvFeat<PK>
             off[f][k] = y0 * w + x0;
             if (!(x0 + 1 < w && y0 + 1 < h)) {
                 // rare: the footprint touches the last column / row.  Corner by corner with zero fill, as grid_sample does
-                const T* lk = lookup + ((long)b * F + f) * CE * hw + off[f][k];
+                const T* lk = fb[f] + off[f][k];
                 double acc = 0.0;
                 for (int c = 0; c < CE; ++c) {
                     const T* l = lk + (long)c * hw;
@@ -132,12 +156,11 @@ __global__ __launch_bounds__(256) void cost_volume_fwd(const typename CvFeat<PK>
     for (int f = 0; f < F; ++f)
 #pragma unroll
         for (int k = 0; k < DB; ++k) acc[f][k] = 0.0;
-    const T* lkb = lookup + (long)b * F * CE * hw;
     for (int c = 0; c < CE; ++c) {
         const T cv = cu[(long)c * hw];
 #pragma unroll
         for (int f = 0; f < F; ++f) {
-            const T* lc = lkb + ((long)f * CE + c) * hw;
+            const T* lc = fb[f] + (long)c * hw;
 #pragma unroll
             for (int k = 0; k < DB; ++k) {
                 if (off[f][k] < 0) continue;
@@ -174,16 +197,41 @@ __global__ __launch_bounds__(256) void cv_pack_pairs(const uint16_t* __restrict_
     out[i] = (uint32_t)src[s] | ((uint32_t)src[s + hw] << 16);
 }
 
+// One map [B][CE (x2 for PK)][hw] -> slot `head` of a ring [F][B][CE][hw] (state == NULL: slot 0 of a plain buffer); PK:
+// bf16 source, written as the channel-pair dwords of cv_pack_pairs.  n = B * CE * hw elements per slot.
+template <bool PK>
+__global__ __launch_bounds__(256) void cv_ring_store(const void* __restrict__ src, void* __restrict__ dst,
+                                                     const int32_t* __restrict__ state, int F, int CE, int hw, long n) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const long base = state == nullptr ? 0 : (long)ring_head(state, F) * n;
+    if constexpr (PK) {
+        const uint16_t* s16 = (const uint16_t*)src;
+        const long p = i % hw, c2 = (i / hw) % CE, nb = i / ((long)hw * CE);
+        const long s = (nb * 2 * CE + 2 * c2) * hw + p;
+        ((uint32_t*)dst)[base + i] = (uint32_t)s16[s] | ((uint32_t)s16[s + hw] << 16);
+    } else {
+        ((float*)dst)[base + i] = ((const float*)src)[i];
+    }
+}
+
+// thread 0: the head; thread 1 + b: item b's count of frames seen.  Every thread owns its word.
+__global__ void cv_ring_advance(int32_t* __restrict__ state, int B, int F) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > B) return;
+    state[i] = i == 0 ? (ring_head(state, F) + 1) % F : min(max(state[i], 0) + 1, F);
+}
+
 // Bins per thread for F lookup frames: the F * DB samples of a thread each hold a double sum, an offset and four weights.
 // 3 - 4 samples per thread keep the kernel at 8 waves / SIMD (<= 62 VGPRs), where one frame with DB = 4 was measured best
 // ("Several lookup frames": registers and occupancy per F and DB).
-template <bool PK, typename T>
+template <bool PK, bool RING, typename T>
 int cost_volume_launch(const T* cur, const T* lookup, const float* P, const float* inv_K, const float* bins,
-                       const int32_t* skip, float* cost, int B, int F, int C, int h, int w, int D, float eps,
-                       hipStream_t stream) {
+                       const int32_t* skip, const int32_t* state, float* cost, int B, int F, int C, int h, int w, int D,
+                       float eps, hipStream_t stream) {
 #define CV_LAUNCH(F_, DB_)                                                                                           \
-    hipLaunchKernelGGL((cost_volume_fwd<F_, DB_, PK>), dim3((h * w + 255) / 256, (D + DB_ - 1) / DB_, B), dim3(256), 0, \
-                       stream, cur, lookup, P, inv_K, bins, skip, cost, C, h, w, D, eps)
+    hipLaunchKernelGGL((cost_volume_fwd<F_, DB_, PK, RING>), dim3((h * w + 255) / 256, (D + DB_ - 1) / DB_, B),       \
+                       dim3(256), 0, stream, cur, lookup, P, inv_K, bins, skip, state, cost, C, h, w, D, eps)
     if (F == 1) CV_LAUNCH(1, 4); else if (F == 2) CV_LAUNCH(2, 2); else if (F == 3) CV_LAUNCH(3, 1); else CV_LAUNCH(4, 1);
 #undef CV_LAUNCH
     return launch_status();
@@ -234,7 +282,8 @@ int ppea_cost_volume_multi_fwd_f32(const float* cur, const float* lookup, const 
     if (B < 0 || F < 1 || F > 4 || C <= 0 || h < 5 || w < 5 || D <= 0 || D > 65535) return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
     if (skip == nullptr) return PPEA_ERR_ARG;
-    return cost_volume_launch<false>(cur, lookup, P, inv_K, bins, skip, cost, B, F, C, h, w, D, eps, (hipStream_t)stream);
+    return cost_volume_launch<false, false>(cur, lookup, P, inv_K, bins, skip, nullptr, cost, B, F, C, h, w, D, eps,
+                                            (hipStream_t)stream);
 }
 
 // bf16 features (C even); `pairs`: caller-owned workspace of (1 + F) * B * C/2 * h * w uint32 (= the inputs' bytes).
@@ -249,8 +298,66 @@ int ppea_cost_volume_multi_fwd_bf16(const void* cur, const void* lookup, void* p
     uint32_t* pc = (uint32_t*)pairs;
     hipLaunchKernelGGL(cv_pack_pairs, dim3((unsigned)((n * (1 + F) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const uint16_t*)cur, (const uint16_t*)lookup, pc, C / 2, h * w, n, n * (1 + F));
-    return cost_volume_launch<true>((const uint32_t*)pc, (const uint32_t*)(pc + n), P, inv_K, bins, skip, cost, B, F, C, h,
-                                    w, D, eps, (hipStream_t)stream);
+    return cost_volume_launch<true, false>((const uint32_t*)pc, (const uint32_t*)(pc + n), P, inv_K, bins, skip, nullptr,
+                                           cost, B, F, C, h, w, D, eps, (hipStream_t)stream);
+}
+
+// Video streaming: the lookups are the last F frames in a device ring [F][B][C][h][w] (bf16: channel-pair dwords
+// [F][B][C/2][h][w], as is `cur` [B][C/2][h][w]: ppea_cv_ring_store_bf16 writes both), frame f = slot (head - 1 - f) mod F.
+// state [1 + B] int32 on the device: head, then per item the frames seen since its reset; frame f of item b is skipped where
+// seen[b] <= f or skip[b][f] != 0 (skip may be NULL).  Same kernel and bits as the entries above on the gathered frames.
+int ppea_cost_volume_ring_fwd_f32(const float* cur, const float* ring, const int32_t* state, const float* P,
+                                  const float* inv_K, const float* bins, const int32_t* skip, float* cost, int B, int F,
+                                  int C, int h, int w, int D, float eps, void* stream) {
+    if (B < 0 || B > 65535 || F < 1 || F > 4 || C <= 0 || h < 5 || w < 5 || D <= 0 || D > 65535) return PPEA_ERR_UNSUPPORTED;
+    if (B == 0) return 0;
+    if (!cur || !ring || !state || !P || !inv_K || !bins || !cost) return PPEA_ERR_ARG;
+    return cost_volume_launch<false, true>(cur, ring, P, inv_K, bins, skip, state, cost, B, F, C, h, w, D, eps,
+                                           (hipStream_t)stream);
+}
+
+int ppea_cost_volume_ring_fwd_bf16(const void* cur_pairs, const void* ring_pairs, const int32_t* state, const float* P,
+                                   const float* inv_K, const float* bins, const int32_t* skip, float* cost, int B, int F,
+                                   int C, int h, int w, int D, float eps, void* stream) {
+    if (B < 0 || B > 65535 || F < 1 || F > 4 || C <= 0 || (C & 1) || h < 5 || w < 5 || D <= 0 || D > 65535)
+        return PPEA_ERR_UNSUPPORTED;
+    if (B == 0) return 0;
+    if (!cur_pairs || !ring_pairs || !state || !P || !inv_K || !bins || !cost) return PPEA_ERR_ARG;
+    return cost_volume_launch<true, true>((const uint32_t*)cur_pairs, (const uint32_t*)ring_pairs, P, inv_K, bins, skip,
+                                          state, cost, B, F, C, h, w, D, eps, (hipStream_t)stream);
+}
+
+// One feature map [B][C][h][w] into the slot the device-side head names of a ring [F][B][C][h][w] (bf16: as channel-pair
+// dwords into [F][B][C/2][h][w], C even).  state NULL: `dst` is a plain [B][..] buffer (the current frame's packed feature).
+int ppea_cv_ring_store_f32(const float* src, float* dst, const int32_t* state, int B, int F, int C, int h, int w,
+                           void* stream) {
+    if (B < 0 || F < 1 || F > 4 || C <= 0 || h <= 0 || w <= 0) return PPEA_ERR_UNSUPPORTED;
+    if (B == 0) return 0;
+    if (!src || !dst) return PPEA_ERR_ARG;
+    const long n = (long)B * C * h * w;
+    hipLaunchKernelGGL(cv_ring_store<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const void*)src, (void*)dst, state, F, C, h * w, n);
+    return launch_status();
+}
+
+int ppea_cv_ring_store_bf16(const void* src, void* dst, const int32_t* state, int B, int F, int C, int h, int w,
+                            void* stream) {
+    if (B < 0 || F < 1 || F > 4 || C <= 0 || (C & 1) || h <= 0 || w <= 0) return PPEA_ERR_UNSUPPORTED;
+    if (B == 0) return 0;
+    if (!src || !dst) return PPEA_ERR_ARG;
+    const long n = (long)B * (C / 2) * h * w;
+    hipLaunchKernelGGL(cv_ring_store<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, dst,
+                       state, F, C / 2, h * w, n);
+    return launch_status();
+}
+
+// A frame has been pushed: head <- (head + 1) mod F, seen[b] <- min(seen[b] + 1, F).  Stream-ordered after the sweep that
+// read the slot the store overwrote.
+int ppea_cv_ring_advance(int32_t* state, int B, int F, void* stream) {
+    if (B < 0 || F < 1 || F > 4) return PPEA_ERR_UNSUPPORTED;
+    if (!state) return PPEA_ERR_ARG;
+    hipLaunchKernelGGL(cv_ring_advance, dim3((B + 1 + 63) / 64), dim3(64), 0, (hipStream_t)stream, state, B, F);
+    return launch_status();
 }
 
 int ppea_cost_volume_reduce_f32(const float* cost, const float* bins, float* cost_out, float* confidence,

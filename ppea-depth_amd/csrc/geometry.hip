@@ -320,6 +320,70 @@ __global__ void pose_chain_fwd(PoseChain c, const float* __restrict__ keep, floa
         }
     }
 }
+
+// ---- the same chain on a video stream: the pairs come from a device ring ------------------------------------------------
+// ring [F][B][2][3]: slot s holds the pose decoder's raw (axisangle, translation) of one pair of consecutive frames.  With
+// head = state[0] (brought into 0 .. F - 1) the pair (t - j - 1, t - j) is slot (head - j) mod F; `aa_new` / `tr_new`
+// (sample b at + b * stride; NULL: the ring already holds it) is the newest pair (t - 1, t) and is written into slot head
+// first.  T(0 -> -1) = inv(pair 0), T(0 -> -(j + 1)) = inv(pair j) @ T(0 -> -j), each built by pose_matrix_f32 and
+// multiplied in pose_chain_fwd's order.  seen = state[1 + b] frames came before this one: frame j of item b is present iff
+// seen > j; an absent frame is exact zeros (so is everything behind it: seen <= j implies seen <= j + 1) and its slot is
+// never read.  present [B][F] bytes.  One thread per item; a thread touches only its own item's words of the ring.
+template <int F>
+__global__ void pose_chain_ring_fwd(const float* __restrict__ aa_new, const float* __restrict__ tr_new, int stride,
+                                    float* ring, const int32_t* __restrict__ state, float* __restrict__ T,
+                                    uint8_t* __restrict__ present, int B) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    int head = state[0] % F;
+    if (head < 0) head += F;
+    const int seen = state[1 + b];
+    float R[16];
+#pragma unroll
+    for (int j = 0; j < F; ++j) {
+        int slot = head - j;
+        if (slot < 0) slot += F;
+        float* pr = ring + ((long)slot * B + b) * 6;
+        float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (j == 0 && aa_new != nullptr) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                v[k] = aa_new[(long)b * stride + k];
+                v[3 + k] = tr_new[(long)b * stride + k];
+            }
+#pragma unroll
+            for (int k = 0; k < 6; ++k) pr[k] = v[k];
+        }
+        const bool on = seen > j;
+        float A[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) A[i] = 0.f;
+        if (on) {
+            if (!(j == 0 && aa_new != nullptr)) {
+#pragma unroll
+                for (int k = 0; k < 6; ++k) v[k] = pr[k];
+            }
+            pose_matrix_f32(v, v + 3, 1, A);
+            if (j > 0) {
+                float P[16];
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        P[4 * i + q] = ((A[4 * i] * R[q] + A[4 * i + 1] * R[4 + q]) + A[4 * i + 2] * R[8 + q]) + A[4 * i + 3] * R[12 + q];
+#pragma unroll
+                for (int i = 0; i < 16; ++i) A[i] = P[i];
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            R[i] = A[i];
+            T[((long)b * F + j) * 16 + i] = A[i];
+        }
+        present[b * F + j] = on ? 1 : 0;
+    }
+}
+
 __global__ void pose_matrix_bwd(const float* __restrict__ aa, const float* __restrict__ tr, const float* __restrict__ dT,
                                 float* __restrict__ daa, float* __restrict__ dtr, int B, int invert) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -426,6 +490,25 @@ int ppea_pose_chain_fwd_f32(const float* const* aa, const float* const* tr, int 
         case 2: hipLaunchKernelGGL(pose_chain_fwd<2>, g, blk, 0, s, c, keep, T, B, stride); break;
         case 3: hipLaunchKernelGGL(pose_chain_fwd<3>, g, blk, 0, s, c, keep, T, B, stride); break;
         default: hipLaunchKernelGGL(pose_chain_fwd<4>, g, blk, 0, s, c, keep, T, B, stride); break;
+    }
+    return launch_status();
+}
+// The chain of a video stream (see pose_chain_ring_fwd): ring [F][B][2][3] fp32 and state [1 + B] int32 on the device;
+// aa_new, tr_new: the newest pair's decoder output, sample b at + b * stride floats (both NULL: slot head already holds it),
+// stored into slot head by this launch.  T [B][F][4][4]; present [B][F] bytes, 1 where seen[b] > j.
+int ppea_pose_chain_ring_fwd_f32(const float* aa_new, const float* tr_new, int stride, float* ring, const int32_t* state,
+                                 float* T, uint8_t* present, int B, int F, void* stream) {
+    if (B < 0 || F < 1 || F > POSE_CHAIN_MAX) return PPEA_ERR_UNSUPPORTED;
+    if ((aa_new == nullptr) != (tr_new == nullptr) || (aa_new != nullptr && stride < 3)) return PPEA_ERR_ARG;
+    if (B == 0) return 0;
+    if (!ring || !state || !T || !present) return PPEA_ERR_ARG;
+    const dim3 g((B + 63) / 64), blk(64);
+    hipStream_t s = (hipStream_t)stream;
+    switch (F) {
+        case 1: hipLaunchKernelGGL(pose_chain_ring_fwd<1>, g, blk, 0, s, aa_new, tr_new, stride, ring, state, T, present, B); break;
+        case 2: hipLaunchKernelGGL(pose_chain_ring_fwd<2>, g, blk, 0, s, aa_new, tr_new, stride, ring, state, T, present, B); break;
+        case 3: hipLaunchKernelGGL(pose_chain_ring_fwd<3>, g, blk, 0, s, aa_new, tr_new, stride, ring, state, T, present, B); break;
+        default: hipLaunchKernelGGL(pose_chain_ring_fwd<4>, g, blk, 0, s, aa_new, tr_new, stride, ring, state, T, present, B); break;
     }
     return launch_status();
 }

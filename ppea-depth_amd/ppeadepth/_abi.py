@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -114,6 +114,7 @@ SIGNATURES = {
     "ppea_pose_matrix_fwd_f32": [_vp, _vp, _vp, _i, _i, _vp],
     "ppea_pose_matrix_bwd_f32": [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "ppea_pose_chain_fwd_f32": [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp],
+    "ppea_pose_chain_ring_fwd_f32": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _vp],
     "ppea_ssim_l1_fwd_f32": [_vp, _vp, _vp, _l] + [_i] * 4 + [_f, _vp],
     "ppea_ssim_l1_bwd_f32": [_vp, _vp, _vp, _l, _vp] + [_i] * 4 + [_f, _vp],
     "ppea_smooth_num_partials": [],
@@ -173,6 +174,11 @@ SIGNATURES = {
     "ppea_cost_volume_reduce_f32": [_vp] * 6 + [_i] * 4 + [_vp],
     "ppea_cost_volume_multi_fwd_f32": [_vp] * 7 + [_i] * 6 + [_f, _vp],
     "ppea_cost_volume_multi_fwd_bf16": [_vp] * 8 + [_i] * 6 + [_f, _vp],
+    "ppea_cost_volume_ring_fwd_f32": [_vp] * 8 + [_i] * 6 + [_f, _vp],
+    "ppea_cost_volume_ring_fwd_bf16": [_vp] * 8 + [_i] * 6 + [_f, _vp],
+    "ppea_cv_ring_store_f32": [_vp] * 3 + [_i] * 5 + [_vp],
+    "ppea_cv_ring_store_bf16": [_vp] * 3 + [_i] * 5 + [_vp],
+    "ppea_cv_ring_advance": [_vp, _i, _i, _vp],
     "ppea_depth_errors_workspace_bytes": [_i, _l],
     "ppea_depth_errors_f32": [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _i, _i, _f, _vp],
     "ppea_depth_errors_mean_f64": [_vp, _vp, _i, _vp],

@@ -20,6 +20,7 @@ BatchNorm, dropout or DropPath (adapters, depth decoders, pose decoder, reduce_c
 modes and are called as they are.  `device="cpu"` runs the same schedule and the same tables with torch ops.
 """
 import contextlib
+import weakref
 
 import torch
 import torch.nn as nn
@@ -138,6 +139,7 @@ class DepthPredictor:
                         raise PpeaKernelError("large-kernel branch is not a depthwise k x k conv with k > 5")
         self.tab, self.lk, self.pose_ab = {}, {}, {}
         self._graphs = {}
+        self._streams = weakref.WeakSet()
         self.refresh()
 
     # ---- tables ---------------------------------------------------------------------------------------------------
@@ -170,6 +172,8 @@ class DepthPredictor:
         for m in self.model.pose_encoder.modules():
             if isinstance(m, nn.BatchNorm2d):
                 put(self.pose_ab, id(m), bn_table(m))
+        for s in list(self._streams):     # features and poses computed under the old weights are never matched
+            s.reset()
 
     # ---- primitives -----------------------------------------------------------------------------------------------
     def affine(self, x, tab, act=ACT_NONE, x2=None, tab2=None, r1=None, r2=None, r2_scale=1.0):
@@ -316,9 +320,10 @@ class DepthPredictor:
                 x = self._pose_bn(conv(blk.conv2, out), blk.bn2, ACT_RELU, idt)
         return x
 
-    def _poses(self, color0, looks):
+    def _poses(self, color0, looks, keep=None):
         """Relative poses 0 -> f of the lookup frames, [B,F,4,4] in `lookup_ids` order: the pairs (f, f + 1), inverted, for
-        f < 0 and (f - 1, f) for f > 0 through the pose network as one F * B batch, then chained (repdepth.py:471-500)."""
+        f < 0 and (f - 1, f) for f > 0 through the pose network as one F * B batch, then chained (repdepth.py:471-500).
+        keep [B,F]: zero = that lookup frame is missing, its pose and every pose chained behind it are exact zeros."""
         B, ids = color0.shape[0], self.lookup_ids
         frames = {0: color0, **{f: looks[:, j] for j, f in enumerate(ids)}}
         pairs = [torch.cat([frames[f], frames[f + 1]] if f < 0 else [frames[f - 1], frames[f]], 1) for f in ids]
@@ -326,7 +331,8 @@ class DepthPredictor:
         axisangle, translation = self.model.pose([[x]])
         # (+1,) -1, -2, ...: the neighbour towards frame 0 comes first; one launch on the device (ops.pose_chain)
         return pose_chain([(axisangle[j * B:(j + 1) * B, 0], translation[j * B:(j + 1) * B, 0]) for j in range(len(ids))],
-                          [(j, f < 0, -1 if f in (-1, 1) else ids.index(f + 1 if f < 0 else f - 1)) for j, f in enumerate(ids)])
+                          [(j, f < 0, -1 if f in (-1, 1) else ids.index(f + 1 if f < 0 else f - 1)) for j, f in enumerate(ids)],
+                          keep)
 
     # ---- public ---------------------------------------------------------------------------------------------------
     def _ctx(self):
@@ -340,13 +346,13 @@ class DepthPredictor:
             return self.model.mono_depth(feats)[("disp", 0)].float()
 
     @torch.no_grad()
-    def _multi(self, color0, looks, K2, inv_K2, min_bin, max_bin):
+    def _multi(self, color0, looks, K2, inv_K2, min_bin, max_bin, keep=None):
         """looks [B,F,3,H,W] in `lookup_ids` order -> (disp, lowest_cost, poses [B,F,4,4])."""
         with self._ctx():
             enc = self.model.encoder
             net = enc.replk
             B, Fr = looks.shape[:2]
-            pose = self._poses(color0, looks)
+            pose = self._poses(color0, looks, keep)
             mn = torch.as_tensor(min_bin, dtype=torch.float32, device=self.device).reshape(())
             mx = torch.as_tensor(max_bin, dtype=torch.float32, device=self.device).reshape(())
             bins = enc.compute_depth_bins(mn, mx, self.device)
@@ -355,18 +361,26 @@ class DepthPredictor:
             feat0, look = self._norm(net, 0, x[:B]), x[B:].reshape(B, Fr, *x.shape[1:])
             if self.cpu:
                 raw = cost_volume_cpu(feat0, look, pose, K2.float(), inv_K2.float(), bins)
-                cost, _conf, _idx, lowest = cost_volume_reduce_cpu(raw, bins)
-                xr = enc.reduce_conv(torch.cat([feat0, cost], 1))
             else:
                 raw = ops.cost_volume_multi(feat0.contiguous(), look.contiguous(), pose, K2, inv_K2, bins)
-                cost, _conf, _idx, lowest = ops.cost_volume_reduce(raw, bins)
-                cat = torch.cat([feat0, cost.to(feat0.dtype)], 1)
-                xr = ops.conv_module(enc.reduce_conv[0], cat, "relu", out_nchw=True)
-                if xr is None:
-                    xr = F.relu(enc.reduce_conv[0](cat))
-            feats = self._rest(net, self._transition(net, 0, xr), [feat0], 1)
-            disp = self.model.depth(feats)[("disp", 0)].float()
+            disp, lowest = self._after_sweep(feat0, raw, bins)
             return disp, lowest, pose
+
+    def _after_sweep(self, feat0, raw, bins):
+        """Raw cost [B,D,h,w] -> reduce, reduce_conv, stages 1 .. 3, decoder -> (disp, lowest_cost)."""
+        enc = self.model.encoder
+        net = enc.replk
+        if self.cpu:
+            cost, _conf, _idx, lowest = cost_volume_reduce_cpu(raw, bins)
+            xr = enc.reduce_conv(torch.cat([feat0, cost], 1))
+        else:
+            cost, _conf, _idx, lowest = ops.cost_volume_reduce(raw, bins)
+            cat = torch.cat([feat0, cost.to(feat0.dtype)], 1)
+            xr = ops.conv_module(enc.reduce_conv[0], cat, "relu", out_nchw=True)
+            if xr is None:
+                xr = F.relu(enc.reduce_conv[0](cat))
+        feats = self._rest(net, self._transition(net, 0, xr), [feat0], 1)
+        return self.model.depth(feats)[("disp", 0)].float(), lowest
 
     def predict_mono(self, color):
         """Teacher: color [B,3,H,W] in [0,1] -> disparity [B,1,H,W] fp32."""
@@ -377,18 +391,25 @@ class DepthPredictor:
         g["graph"].replay()
         return g["out"].clone()
 
-    def predict(self, color0, lookups, K2, inv_K2, min_bin, max_bin):
+    def predict(self, color0, lookups, K2, inv_K2, min_bin, max_bin, keep=None):
         """Pose network -> cost volume -> multi-frame encoder -> decoder (as `Trainer.predict_disps`).
         lookups: [B,3,H,W] for a model with one lookup frame, or [B,F,3,H,W] in `model.matching_ids[1:]` order.
+        keep: [B,F] (None: all present), zero = that lookup frame of that item is missing, the reference's rule for a missing
+        image (repdepth.py:502-505): its relative pose and every pose chained behind it are exact zeros, the plane sweep skips
+        it, and whatever image sits in the slot does not reach the result.  A call with `keep` runs eagerly: the captured
+        graph is the call without it.
         -> dict(disp [B,1,H,W], lowest_cost [B,h/4,w/4], pose [B,4,4] resp. [B,F,4,4]: the relative poses 0 -> frame)."""
         single = lookups.dim() == 4
         looks = lookups[:, None] if single else lookups
         if looks.shape[1] != len(self.lookup_ids):
             raise PpeaKernelError(f"{looks.shape[1]} lookup frame(s) given, the model matches against {self.lookup_ids}")
-        g = self._graphs.get(("multi", tuple(color0.shape)))
+        if keep is not None and tuple(keep.shape) != tuple(looks.shape[:2]):
+            raise PpeaKernelError(f"keep {tuple(keep.shape)} for lookups {tuple(looks.shape[:2])}")
+        g = self._graphs.get(("multi", tuple(color0.shape))) if keep is None else None
         if g is None:
             d = self.device
-            out = self._multi(color0.to(d), looks.to(d), K2.to(d), inv_K2.to(d), min_bin, max_bin)
+            out = self._multi(color0.to(d), looks.to(d), K2.to(d), inv_K2.to(d), min_bin, max_bin,
+                              None if keep is None else keep.to(d))
         else:
             mn = torch.as_tensor(min_bin, dtype=torch.float32).reshape(())
             mx = torch.as_tensor(max_bin, dtype=torch.float32).reshape(())
@@ -425,3 +446,143 @@ class DepthPredictor:
                 out = fn(ins)
             self._graphs[(name, (B, 3, H, W))] = {"graph": graph, "in": ins, "out": out}
         return self
+
+    def stream(self, B):
+        """State for B parallel cameras at (opt.height, opt.width): see `DepthStream`."""
+        return DepthStream(self, B)
+
+
+class DepthStream:
+    """Video streaming on a `DepthPredictor`: `push` takes the NEXT frame of each of B cameras and matches it against the last
+    F frames, whose stage-0 features, pose pairs and images it kept from the earlier pushes -- stem + stage 0 run on B items
+    instead of (1 + F) B, the pose trunk on one pair batch instead of F.
+
+    State (on the predictor's device; a replayed push reads no host value):
+      ring       the un-normalised stage-0 output x of the last F frames, [F,B,C,h,w] fp32, or for bf16 features the plane
+                 sweep's channel-pair dwords [F,B,C/2,h,w] (the reference matches `stages[0].norm(x)` of the current frame
+                 against the RAW x of the lookups, replk_matching_adapter.py:357-369, 433-445);
+      pose_ring  the pose decoder's raw (axisangle, translation) of the pairs (t-k-1, t-k), [F,B,2,3] fp32;
+      prev       the previous frame [B,3,H,W], for the one new pair (t-1, t);
+      state      int32 [1 + B]: the head slot, then per item the frames seen since its reset, clamped at F.
+    Lookup j (frame t-1-j) is ring slot (head - 1 - j) mod F, pair j is pose slot (head - j) mod F.  After a reset fewer than F
+    earlier frames exist: a missing lookup frame has an exact-zero pose and is skipped by the sweep (`predict`'s `keep`), and
+    with none present the cost is the all-skipped volume.  `present [B,F]` says which lookups existed."""
+
+    def __init__(self, predictor, B):
+        p = self.p = predictor
+        self.F = len(p.lookup_ids)
+        if p.lookup_ids != [-k for k in range(1, self.F + 1)]:
+            raise PpeaKernelError(f"a stream matches against the past frames -1 .. -F; the model's lookup frames are "
+                                  f"{p.lookup_ids} (a future frame means a frame of latency: not served)")
+        if int(B) < 1:
+            raise PpeaKernelError(f"a stream needs B >= 1 cameras, got {B}")
+        self.B, self.H, self.W = int(B), p.opt.height, p.opt.width
+        d = p.device
+        self.state = torch.zeros(1 + self.B, device=d, dtype=torch.int32)
+        self.prev = torch.zeros(self.B, 3, self.H, self.W, device=d)
+        self.pose_ring = torch.zeros(self.F, self.B, 2, 3, device=d)
+        self.ring = None                  # allocated by the first push, from stage 0's output
+        self._graph = None
+        p._streams.add(self)
+
+    def reset(self, mask=None):
+        """All cameras (mask [B] bool: only those) start a new clip: their next frame has no lookup frame."""
+        if mask is None:
+            self.state.zero_()
+        else:
+            if tuple(mask.shape) != (self.B,):
+                raise PpeaKernelError(f"reset: mask {tuple(mask.shape)} for {self.B} cameras")
+            self.state[1:].masked_fill_(mask.to(self.state.device, torch.bool), 0)
+        return self
+
+    def _host_chain(self, aa, tr):
+        """The host-side ring with the torch composites: (poses [B,F,4,4], present [B,F], lookups [B,F,C,h,w])."""
+        Fr, head = self.F, int(self.state[0])
+        self.pose_ring[head, :, 0], self.pose_ring[head, :, 1] = aa.reshape(-1, 3).float(), tr.reshape(-1, 3).float()
+        present = self.state[1:, None] > torch.arange(Fr)[None]
+        slots = [self.pose_ring[(head - j) % Fr] for j in range(Fr)]
+        pose = pose_chain([(sl[:, None, 0], sl[:, None, 1]) for sl in slots], [(j, True, j - 1) for j in range(Fr)],
+                          present.float())
+        look = torch.stack([self.ring[(head - 1 - j) % Fr] for j in range(Fr)], 1)
+        return pose, present, look
+
+    @torch.no_grad()
+    def _step(self, color, K2, inv_K2, mn, mx):
+        p, Fr = self.p, self.F
+        with p._ctx():
+            enc = p.model.encoder
+            net = enc.replk
+            x = p._stage(net, 0, p._stem(net, color))
+            feat0 = p._norm(net, 0, x)
+            axisangle, translation = p.model.pose([[p._pose_features(torch.cat([self.prev, color], 1))]])
+            aa, tr = axisangle[:, 0], translation[:, 0]
+            bins = enc.compute_depth_bins(mn, mx, p.device)
+            pairs = p.bf16 and ops.CV_BF16 and x.dtype == torch.bfloat16 and x.shape[1] % 2 == 0
+            if self.ring is None:
+                B, C, h, w = x.shape
+                self.ring = (torch.zeros(Fr, B, C // 2, h, w, device=p.device, dtype=torch.int32) if pairs else
+                             torch.zeros(Fr, B, C, h, w, device=p.device))
+            if p.cpu:
+                pose, present, look = self._host_chain(aa, tr)
+                raw = cost_volume_cpu(feat0, look, pose, K2.float(), inv_K2.float(), bins)
+            else:
+                pose, present = ops.pose_chain_ring(self.pose_ring, self.state, (aa, tr))
+                # the chain wrote zeros exactly where seen[b] <= j, which the sweep tests itself: no zero-pose flags
+                raw = ops.cost_volume_ring(feat0.contiguous() if pairs else feat0.float().contiguous(), self.ring, self.state,
+                                           pose, K2, inv_K2, bins, zero_pose_skip=False)
+            disp, lowest = p._after_sweep(feat0, raw, bins)
+            # the sweep has read the slot that holds frame t - F: it is overwritten now
+            if p.cpu:
+                head = int(self.state[0])
+                self.ring[head] = x.float()
+                self.state[0] = (head + 1) % Fr
+                self.state[1:] = (self.state[1:] + 1).clamp(max=Fr)
+            else:
+                ops.ring_store(x.contiguous() if pairs else x.float().contiguous(), self.ring, self.state)
+                ops.ring_advance(self.state, Fr)
+            self.prev.copy_(color)
+            return disp, lowest, pose, present
+
+    def push(self, color, K2, inv_K2, min_bin, max_bin):
+        """color [B,3,H,W] in [0,1]: the next frame of each camera; K2, inv_K2 [B,4,4] at the matching scale.
+        -> dict(disp [B,1,H,W] fp32, lowest_cost [B,h/4,w/4], pose [B,F,4,4] relative poses 0 -> -1 .. -F (zeros where the
+        frame is missing), present [B,F] bool)."""
+        if tuple(color.shape) != (self.B, 3, self.H, self.W):
+            raise PpeaKernelError(f"push: color {tuple(color.shape)}, the stream was opened for {(self.B, 3, self.H, self.W)}")
+        d = self.p.device
+        g = self._graph
+        if g is None:
+            mn = torch.as_tensor(min_bin, dtype=torch.float32, device=d).reshape(())
+            mx = torch.as_tensor(max_bin, dtype=torch.float32, device=d).reshape(())
+            out = self._step(color.to(d), K2.to(d), inv_K2.to(d), mn, mx)
+        else:
+            mn = torch.as_tensor(min_bin, dtype=torch.float32).reshape(())
+            mx = torch.as_tensor(max_bin, dtype=torch.float32).reshape(())
+            for dst, src in zip(g["in"], (color, K2, inv_K2, mn, mx)):
+                dst.copy_(src)
+            g["graph"].replay()
+            out = tuple(t.clone() for t in g["out"])
+        return {"disp": out[0], "lowest_cost": out[1], "pose": out[2], "present": out[3]}
+
+    def capture(self):
+        """One torch.cuda.graph over static buffers for a whole push, state update included (single stream, no parallel
+        branches); every later push replays it.  The stream is reset: the warm-up frames are not part of any clip."""
+        p = self.p
+        if p.cpu:
+            raise PpeaKernelError("capture needs a HIP device")
+        d = p.device
+        eye = torch.eye(4, device=d).repeat(self.B, 1, 1)
+        ins = [torch.rand(self.B, 3, self.H, self.W, device=d), eye.clone(), eye.clone(), torch.tensor(0.1, device=d),
+               torch.tensor(10.0, device=d)]
+        side = torch.cuda.Stream(d)
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(2):                                      # warm-up: caches, lazy kernel attributes, the ring
+                self._step(*ins)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            out = self._step(*ins)
+        self._graph = {"graph": graph, "in": ins, "out": out}
+        return self.reset()

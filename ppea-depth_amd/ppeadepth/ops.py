@@ -8,7 +8,7 @@ import weakref
 import torch
 
 from . import _abi
-from ._abi import call, ptr, stream_ptr, try_call
+from ._abi import PpeaKernelError, call, ptr, stream_ptr, try_call
 
 _F32 = torch.float32
 _BF16 = torch.bfloat16
@@ -533,6 +533,89 @@ def cost_volume_reduce(cost, bins):
     call("ppea_cost_volume_reduce_f32", ptr(cost.contiguous()), ptr(bins.contiguous().float()), ptr(out),
          ptr(conf), ptr(idx), ptr(low), B, D, h, w, stream_ptr())
     return out, conf, idx, low
+
+
+# ---- video streaming: the lookups are the last F frames, kept in a device ring (inference.DepthStream) ----------------
+# `state`: a stream's counters on the device, int32 [1 + B]: [0] the head slot, [1 + b] the frames item b has seen since its
+# reset (clamped at F).  The ring kernels read them; nothing reads them on the host.
+def _ring_dims(ring, state):
+    F, B = ring.shape[:2]
+    if not 1 <= F <= CV_MAX_FRAMES:
+        raise _abi.PpeaKernelError(f"a feature ring holds 1 .. {CV_MAX_FRAMES} frames, got {F}")
+    if state is not None and (state.dtype != torch.int32 or state.shape != (1 + B,) or state.device != ring.device):
+        raise _abi.PpeaKernelError(f"stream state must be int32 [1 + {B}] on {ring.device}")
+    if ring.dtype not in (_F32, torch.int32):
+        raise _abi.PpeaKernelError(f"a feature ring is fp32 or int32 channel pairs, got {ring.dtype}")
+    return F, B
+
+
+@torch.no_grad()
+def pack_pairs(x):
+    """bf16 [B,C,h,w], C even -> the plane sweep's channel-pair dwords, int32 [B,C/2,h,w] (cv_pack_pairs layout)."""
+    B, C, h, w = x.shape
+    if x.dtype != _BF16 or C % 2:
+        raise _abi.PpeaKernelError(f"pack_pairs takes bf16 maps with an even channel count, got {x.dtype} C = {C}")
+    out = torch.empty(B, C // 2, h, w, device=x.device, dtype=torch.int32)
+    call("ppea_cv_ring_store_bf16", ptr(x.contiguous()), ptr(out), None, B, 1, C, h, w, stream_ptr())
+    return out
+
+
+@torch.no_grad()
+def ring_store(x, ring, state):
+    """x [B,C,h,w] into the slot the device-side head names: fp32 into an fp32 ring [F,B,C,h,w], bf16 as channel pairs into
+    an int32 ring [F,B,C/2,h,w]."""
+    F, B = _ring_dims(ring, state)
+    C, h, w = x.shape[1:]
+    if ring.dtype == _F32:
+        if x.dtype != _F32 or tuple(ring.shape[1:]) != tuple(x.shape):
+            raise _abi.PpeaKernelError(f"ring_store: {x.dtype} {tuple(x.shape)} into an fp32 ring {tuple(ring.shape)}")
+        call("ppea_cv_ring_store_f32", ptr(x.contiguous()), ptr(ring), ptr(state), B, F, C, h, w, stream_ptr())
+    else:
+        if x.dtype != _BF16 or C % 2 or tuple(ring.shape[1:]) != (x.shape[0], C // 2, h, w):
+            raise _abi.PpeaKernelError(f"ring_store: {x.dtype} {tuple(x.shape)} into a pair ring {tuple(ring.shape)}")
+        call("ppea_cv_ring_store_bf16", ptr(x.contiguous()), ptr(ring), ptr(state), B, F, C, h, w, stream_ptr())
+    return ring
+
+
+@torch.no_grad()
+def ring_advance(state, F):
+    """A frame has been pushed: head <- (head + 1) mod F, seen <- min(seen + 1, F).  Call it after the sweep and the store."""
+    call("ppea_cv_ring_advance", ptr(state, torch.int32), state.shape[0] - 1, int(F), stream_ptr())
+    return state
+
+
+@torch.no_grad()
+def cost_volume_ring(cur, ring, state, poses, K, inv_K, bins, eps=1e-7, zero_pose_skip=True):
+    """`cost_volume_multi` with lookup frame f of item b read from slot (head - 1 - f) mod F of `ring` (`ring_store`'s
+    layout); a frame is skipped where seen[b] <= f or, with `zero_pose_skip`, where its pose is zeroed.  cur: fp32 [B,C,h,w]
+    for an fp32 ring; bf16 [B,C,h,w] (packed here, one launch) or already packed int32 [B,C/2,h,w] for a pair ring.  Same
+    bits as `cost_volume_multi` on the frames gathered in order.  (`zero_pose_skip=False`: the caller's poses are zero exactly
+    where seen says so, e.g. `pose_chain_ring`'s -- three small launches less.)"""
+    F, B = _ring_dims(ring, state)
+    if state is None:
+        raise _abi.PpeaKernelError("cost_volume_ring needs the stream state")
+    D = bins.shape[0]
+    if tuple(poses.shape) != (B, F, 4, 4):
+        raise _abi.PpeaKernelError(f"cost_volume_ring: poses {tuple(poses.shape)} for a ring of {F} frames, B = {B}")
+    P = torch.matmul(K[:, None], poses)[:, :, :3, :].contiguous().float()
+    skip = (poses.reshape(B, F, -1).sum(2) == 0).to(torch.int32) if zero_pose_skip else None
+    inv_K, bins = inv_K.contiguous().float(), bins.contiguous().float()
+    if ring.dtype == _F32:
+        C, h, w = ring.shape[2:]
+        if cur.dtype != _F32 or tuple(cur.shape) != (B, C, h, w):
+            raise _abi.PpeaKernelError(f"cost_volume_ring: cur {cur.dtype} {tuple(cur.shape)}, fp32 ring {tuple(ring.shape)}")
+        name = "ppea_cost_volume_ring_fwd_f32"
+    else:
+        if cur.dtype == _BF16:
+            cur = pack_pairs(cur)
+        C, h, w = 2 * ring.shape[2], ring.shape[3], ring.shape[4]
+        if cur.dtype != torch.int32 or tuple(cur.shape) != (B, C // 2, h, w):
+            raise _abi.PpeaKernelError(f"cost_volume_ring: cur {cur.dtype} {tuple(cur.shape)}, pair ring {tuple(ring.shape)}")
+        name = "ppea_cost_volume_ring_fwd_bf16"
+    cost = torch.empty(B, D, h, w, device=ring.device, dtype=_F32)
+    call(name, ptr(cur.contiguous()), ptr(ring), ptr(state), ptr(P), ptr(inv_K), ptr(bins), ptr(skip), ptr(cost), B, F, C, h,
+         w, D, float(eps), stream_ptr())
+    return cost
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1567,6 +1650,35 @@ def pose_chain(pairs, chain, keep=None):
          stride, ints(*(c[0] for c in chain)), ints(*(int(bool(c[1])) for c in chain)), ints(*(c[2] for c in chain)),
          ptr(keep), ptr(T), B, Fr, stream_ptr())
     return T
+
+
+@torch.no_grad()
+def pose_chain_ring(ring, state, new=None):
+    """The relative poses of a video stream's lookup frames -1 .. -F from the pose ring [F,B,2,3] fp32 (slot (head - j) mod F:
+    the pose decoder's raw (axisangle, translation) of the pair (t-j-1, t-j)) in one launch.  new = (axisangle, translation)
+    [B,1,3] or [B,3] of the pair (t-1, t): stored into slot head by the same launch (None: it is there already).
+    -> (T [B,F,4,4] = `pose_chain`'s on those pairs, exact zeros where seen[b] <= j; present [B,F] bool)."""
+    Fr, B = ring.shape[:2]
+    if ring.dtype != _F32 or tuple(ring.shape[2:]) != (2, 3) or not 1 <= Fr <= POSE_CHAIN_MAX:
+        raise PpeaKernelError(f"pose_chain_ring: ring {ring.dtype} {tuple(ring.shape)}, expected fp32 [1..{POSE_CHAIN_MAX},B,2,3]")
+    if state.dtype != torch.int32 or state.shape != (1 + B,) or state.device != ring.device:
+        raise PpeaKernelError(f"stream state must be int32 [1 + {B}] on {ring.device}")
+    aa = tr = None
+    stride = 3
+    if new is not None:
+        aa, tr = (t.reshape(B, 3) for t in new)
+        stride = aa.stride(0) if B > 1 else 3
+        if not all(t.is_cuda and t.dtype == _F32 and t.stride(1) == 1 and (B <= 1 or t.stride(0) == stride) and stride >= 3
+                   for t in (aa, tr)):
+            aa, tr, stride = aa.float().contiguous(), tr.float().contiguous(), 3
+        if aa.device != ring.device or tr.device != ring.device:
+            raise PpeaKernelError("pose_chain_ring: the new pair is on another device")
+    T = torch.empty(B, Fr, 4, 4, device=ring.device, dtype=_F32)
+    present = torch.empty(B, Fr, device=ring.device, dtype=torch.uint8)
+    call("ppea_pose_chain_ring_fwd_f32", None if aa is None else _ct.c_void_p(aa.data_ptr()),
+         None if tr is None else _ct.c_void_p(tr.data_ptr()), stride, ptr(ring), ptr(state), ptr(T), ptr(present), B, Fr,
+         stream_ptr())
+    return T, present.view(torch.bool)
 
 
 def tapsum_fwd(T, bias, Ch):
