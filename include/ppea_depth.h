@@ -372,6 +372,31 @@ int ppea_backproject_project_bwd_f32(const float* depth, const float* inv_K, con
                                      int B, int H, int W, float eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * A18, A19 as separate launches (layers.py:138-168 BackprojectDepth, 171-199 Project3D), for callers that keep the
+ * reference's two modules or need the point cloud / the projected depth.  All fp32, one thread per pixel, no atomics.
+ *   backproject: points [B,4,HW]: rows 0-2 = depth * (inv_K[:3,:3] @ (x, y, 1)), row 3 = 1; x, y from the thread index.
+ *     bwd: d_depth [B,1,H,W] overwritten; d_inv_K [B,4,4] (NULL: not wanted, workspace unused) gets the 9 sums
+ *     d_points[i] * depth * (x, y, 1)[j] in its upper-left 3x3 and zeros elsewhere.  Either may be NULL, not both.
+ *   project3d: P is the whole [B,4,4] product K @ T, of which rows 0-2 are read in place (the reference's `[:, :3, :]`
+ *     without a copy); cam = P[:3] @ points over all four rows (row 3 need not be 1); grid [B,H,W,2] as the fused kernel
+ *     writes it; z [B,1,H,W] = cam[2] (NULL: not wanted).  bwd: d_z NULL = no gradient into z; d_points [B,4,HW] and
+ *     dP [B,4,4] (12 sums, row 3 zeros) are overwritten, either may be NULL (not wanted), not both.
+ *   Both backward passes sum per-block partials from a caller-owned workspace of *_bwd_workspace_bytes(B, H, W) bytes in a
+ *   fixed order.  Where row 3 of `points` is 1, project3d(backproject(.)) and its gradients carry the fused kernels' bits.
+ *   B is the grid's y extent: B > 65535 is PPEA_ERR_UNSUPPORTED.  Note that `P` / `dP` here are [B,4,4], unlike the
+ *   [B,3,4] `P` / `dP` of ppea_backproject_project_* above.
+ * ---------------------------------------------------------------------------------------- */
+int ppea_backproject_fwd_f32(const float* depth, const float* inv_K, float* points, int B, int H, int W, void* stream);
+long ppea_backproject_bwd_workspace_bytes(int B, int H, int W);
+int ppea_backproject_bwd_f32(const float* depth, const float* inv_K, const float* d_points, float* d_depth, float* d_inv_K,
+                             void* workspace, int B, int H, int W, void* stream);
+int ppea_project3d_fwd_f32(const float* points, const float* P, float* grid, float* z, int B, int H, int W, float eps,
+                           void* stream);
+long ppea_project3d_bwd_workspace_bytes(int B, int H, int W);
+int ppea_project3d_bwd_f32(const float* points, const float* P, const float* d_grid, const float* d_z, float* d_points,
+                           float* dP, void* workspace, int B, int H, int W, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * A20  F.grid_sample(bilinear, align_corners=True)  (trainer.py:911-914 border;
  *      replk_matching_adapter.py:299 zeros).  src [B,C,Hi,Wi]; grid [B,Ho,Wo,2];
  *      out [B,C,Ho,Wo].  padding: 0 = zeros, 1 = border.

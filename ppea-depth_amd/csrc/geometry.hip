@@ -1,5 +1,6 @@
 // Geometry of the photometric warp, gfx950:
 //   A18+A19  BackprojectDepth -> Project3D fused        (layers.py:138-199)
+//   A18, A19 the same two modules as one launch each, for callers that keep them apart or need the points
 //   A20      F.grid_sample bilinear, align_corners=True  (trainer.py:911-914, rkm.py:299)
 // All HBM-bound streaming kernels: one thread per output pixel, coalesced NCHW rows,
 // no intermediate [B,4,HW] point cloud (the reference writes ~5 MB/img for 1.5 MB
@@ -129,6 +130,174 @@ __global__ __launch_bounds__(64) void bp_reduce_dP(const float* __restrict__ par
         const float s = wave_sum(acc[k]);
         if (lane == 0) dP[b * 12 + k] = s;
     }
+}
+
+// ---- the same geometry split at the point cloud (layers.py:138-199 as two modules) ---------------------------------------
+// BackprojectDepth and Project3D for callers that keep the reference's two-module form or need the [B,4,HW] points / the
+// projected depth themselves.  Same expression shapes as the fused kernels above: where row 3 of the points is 1 the grid,
+// d_depth and dP carry the fused kernels' bits (p * 1.f and dc * 1.f are exact).
+__device__ __forceinline__ Cam load_ik(const float* __restrict__ inv_K, int b) {
+    Cam c;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c.ik[i * 3 + j] = inv_K[b * 16 + i * 4 + j];
+    return c;
+}
+
+// N per-thread terms -> one partial per block and entry in partial [B][blocks][N] (wave shuffle -> LDS -> fixed tree)
+template <int N>
+__device__ __forceinline__ void block_partials(const float (&g)[N], float (&red)[4][N], float* __restrict__ partial, int b) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const float s = wave_sum(g[k]);
+        if (lane == 0) red[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < N) {
+        const float s = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
+        partial[((long)b * gridDim.x + blockIdx.x) * N + threadIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(256) void backproject_fwd(const float* __restrict__ depth, const float* __restrict__ inv_K,
+                                                       float* __restrict__ points, int H, int W) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const long HW = (long)H * W;
+    if (i >= HW) return;
+    const Cam c = load_ik(inv_K, b);
+    const int py = i / W, px = i - py * W;
+    float r[3];
+    pixel_ray(c, (float)px, (float)py, r);
+    const float d = depth[b * HW + i];
+    float* o = points + (long)b * 4 * HW + i;
+    o[0] = d * r[0];
+    o[HW] = d * r[1];
+    o[2 * HW] = d * r[2];
+    o[3 * HW] = 1.f;
+}
+
+// d_depth (NULL: not wanted) = d_points[:3] . ray; partial != NULL: the 9 sums of d inv_K[:3,:3], entry (i, j) = d_points[i] * depth * (x, y, 1)[j]
+__global__ __launch_bounds__(256) void backproject_bwd(const float* __restrict__ depth, const float* __restrict__ inv_K,
+                                                       const float* __restrict__ d_points, float* __restrict__ d_depth,
+                                                       float* __restrict__ partial, int H, int W) {
+    __shared__ float red[4][9];
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const long HW = (long)H * W;
+    const Cam c = load_ik(inv_K, b);
+    float g[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) g[k] = 0.f;
+    if (i < HW) {
+        const int py = i / W, px = i - py * W;
+        const float xy[3] = {(float)px, (float)py, 1.f};
+        float r[3];
+        pixel_ray(c, xy[0], xy[1], r);
+        const float* dp = d_points + (long)b * 4 * HW + i;
+        const float dX[3] = {dp[0], dp[HW], dp[2 * HW]};
+        if (d_depth != nullptr) d_depth[b * HW + i] = dX[0] * r[0] + dX[1] * r[1] + dX[2] * r[2];
+        if (partial != nullptr) {
+            const float d = depth[b * HW + i];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) g[k * 3 + j] = (dX[k] * d) * xy[j];
+        }
+    }
+    if (partial != nullptr) block_partials<9>(g, red, partial, b);      // uniform over the launch
+}
+
+// out [B][4][4]: the R x C sums in the upper-left corner, added in bp_reduce_dP's fixed order, zeros elsewhere
+template <int R, int C>
+__global__ __launch_bounds__(64) void bp_reduce_4x4(const float* __restrict__ partial, float* __restrict__ out, int blocks) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    float acc[R * C];
+#pragma unroll
+    for (int k = 0; k < R * C; ++k) acc[k] = 0.f;
+    for (int i = lane; i < blocks; i += 64) {
+        const float* p = partial + ((long)b * blocks + i) * (R * C);
+#pragma unroll
+        for (int k = 0; k < R * C; ++k) acc[k] += p[k];
+    }
+    float v = 0.f;
+#pragma unroll
+    for (int k = 0; k < R * C; ++k) {
+        const float s = wave_sum(acc[k]);
+        if (lane == (k / C) * 4 + k % C) v = s;
+    }
+    if (lane < 16) out[b * 16 + lane] = v;
+}
+
+__global__ __launch_bounds__(256) void project3d_fwd(const float* __restrict__ points, const float* __restrict__ P,
+                                                     float* __restrict__ grid, float* __restrict__ z, int H, int W, float eps) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const long HW = (long)H * W;
+    if (i >= HW) return;
+    float p[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) p[k] = P[b * 16 + k];
+    const float* x = points + (long)b * 4 * HW + i;
+    const float Xh[4] = {x[0], x[HW], x[2 * HW], x[3 * HW]};
+    float cam[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        cam[k] = ((p[k * 4] * Xh[0] + p[k * 4 + 1] * Xh[1]) + p[k * 4 + 2] * Xh[2]) + p[k * 4 + 3] * Xh[3];
+    const float iz = cam[2] + eps;
+    float u = cam[0] / iz, v = cam[1] / iz;
+    u = u / (float)(W - 1);
+    v = v / (float)(H - 1);
+    float2 o;
+    o.x = (u - 0.5f) * 2.f;
+    o.y = (v - 0.5f) * 2.f;
+    reinterpret_cast<float2*>(grid)[b * HW + i] = o;
+    if (z != nullptr) z[b * HW + i] = cam[2];
+}
+
+// P: the [B,4,4] product K @ T, rows 0-2 read in place (the reference's `[:, :3, :]` without a copy).
+// d_points [B,4,HW] (NULL: not wanted) and, with partial != NULL, the 12 per-block sums of dP; d_z (NULL: none) is the
+// gradient of the projected depth cam[2]
+__global__ __launch_bounds__(256) void project3d_bwd(const float* __restrict__ points, const float* __restrict__ P,
+                                                     const float* __restrict__ d_grid, const float* __restrict__ d_z,
+                                                     float* __restrict__ d_points, float* __restrict__ partial, int H, int W,
+                                                     float eps) {
+    __shared__ float red[4][12];
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const long HW = (long)H * W;
+    float p[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) p[k] = P[b * 16 + k];
+    float g[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) g[k] = 0.f;
+    if (i < HW) {
+        const float* x = points + (long)b * 4 * HW + i;
+        const float Xh[4] = {x[0], x[HW], x[2 * HW], x[3 * HW]};
+        float cam[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            cam[k] = ((p[k * 4] * Xh[0] + p[k * 4 + 1] * Xh[1]) + p[k * 4 + 2] * Xh[2]) + p[k * 4 + 3] * Xh[3];
+        const float iz = 1.f / (cam[2] + eps);
+        const float u = cam[0] * iz, v = cam[1] * iz;
+        const float2 dg = reinterpret_cast<const float2*>(d_grid)[b * HW + i];
+        const float du = dg.x * 2.f / (float)(W - 1), dv = dg.y * 2.f / (float)(H - 1);
+        float dc[3] = {du * iz, dv * iz, -(du * u + dv * v) * iz};
+        if (d_z != nullptr) dc[2] = dc[2] + d_z[b * HW + i];
+        if (d_points != nullptr) {
+            float* o = d_points + (long)b * 4 * HW + i;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j * HW] = p[j] * dc[0] + p[4 + j] * dc[1] + p[8 + j] * dc[2];
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g[k * 4 + j] = dc[k] * Xh[j];
+    }
+    if (partial != nullptr) block_partials<12>(g, red, partial, b);     // uniform over the launch
 }
 
 // ---- grid_sample -----------------------------------------------------------------------
@@ -428,6 +597,64 @@ int ppea_backproject_project_bwd_f32(const float* depth, const float* inv_K, con
     hipLaunchKernelGGL(backproject_project_bwd, g, dim3(256), 0, (hipStream_t)stream, depth, inv_K, P,
                        d_grid, d_depth, (float*)workspace, H, W, eps);
     hipLaunchKernelGGL(bp_reduce_dP, dim3(B), dim3(64), 0, (hipStream_t)stream, (const float*)workspace, dP, (int)g.x);
+    return launch_status();
+}
+
+// BackprojectDepth / Project3D as separate launches (see backproject_fwd ... project3d_bwd above)
+int ppea_backproject_fwd_f32(const float* depth, const float* inv_K, float* points, int B, int H, int W, void* stream) {
+    if (B < 0 || H < 1 || W < 1 || (long)H * W > 0x7fffff00L || B > 65535) return PPEA_ERR_UNSUPPORTED;   // B is gridDim.y
+    if (B == 0) return 0;
+    if (!depth || !inv_K || !points) return PPEA_ERR_ARG;
+    dim3 g((H * W + 255) / 256, B);
+    hipLaunchKernelGGL(backproject_fwd, g, dim3(256), 0, (hipStream_t)stream, depth, inv_K, points, H, W);
+    return launch_status();
+}
+
+long ppea_backproject_bwd_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H < 1 || W < 1) return 0;
+    return (long)B * (((long)H * W + 255) / 256) * 9 * (long)sizeof(float);
+}
+
+int ppea_backproject_bwd_f32(const float* depth, const float* inv_K, const float* d_points, float* d_depth, float* d_inv_K,
+                             void* workspace, int B, int H, int W, void* stream) {
+    if (B < 0 || H < 1 || W < 1 || (long)H * W > 0x7fffff00L || B > 65535) return PPEA_ERR_UNSUPPORTED;   // B is gridDim.y
+    if (B == 0) return 0;
+    if (!depth || !inv_K || !d_points || (d_depth == nullptr && d_inv_K == nullptr) || (d_inv_K != nullptr && workspace == nullptr))
+        return PPEA_ERR_ARG;
+    dim3 g((H * W + 255) / 256, B);
+    float* partial = d_inv_K != nullptr ? (float*)workspace : nullptr;
+    hipLaunchKernelGGL(backproject_bwd, g, dim3(256), 0, (hipStream_t)stream, depth, inv_K, d_points, d_depth, partial, H, W);
+    if (d_inv_K != nullptr)
+        hipLaunchKernelGGL((bp_reduce_4x4<3, 3>), dim3(B), dim3(64), 0, (hipStream_t)stream, (const float*)partial, d_inv_K, (int)g.x);
+    return launch_status();
+}
+
+int ppea_project3d_fwd_f32(const float* points, const float* P, float* grid, float* z, int B, int H, int W, float eps,
+                           void* stream) {
+    if (B < 0 || H < 2 || W < 2 || (long)H * W > 0x7fffff00L || B > 65535) return PPEA_ERR_UNSUPPORTED;   // B is gridDim.y
+    if (B == 0) return 0;
+    if (!points || !P || !grid) return PPEA_ERR_ARG;
+    dim3 g((H * W + 255) / 256, B);
+    hipLaunchKernelGGL(project3d_fwd, g, dim3(256), 0, (hipStream_t)stream, points, P, grid, z, H, W, eps);
+    return launch_status();
+}
+
+long ppea_project3d_bwd_workspace_bytes(int B, int H, int W) {
+    if (B <= 0 || H < 2 || W < 2) return 0;
+    return (long)B * (((long)H * W + 255) / 256) * 12 * (long)sizeof(float);
+}
+
+int ppea_project3d_bwd_f32(const float* points, const float* P, const float* d_grid, const float* d_z, float* d_points,
+                           float* dP, void* workspace, int B, int H, int W, float eps, void* stream) {
+    if (B < 0 || H < 2 || W < 2 || (long)H * W > 0x7fffff00L || B > 65535) return PPEA_ERR_UNSUPPORTED;   // B is gridDim.y
+    if (B == 0) return 0;
+    if (!points || !P || !d_grid || (d_points == nullptr && dP == nullptr) || (dP != nullptr && workspace == nullptr))
+        return PPEA_ERR_ARG;
+    dim3 g((H * W + 255) / 256, B);
+    float* partial = dP != nullptr ? (float*)workspace : nullptr;
+    hipLaunchKernelGGL(project3d_bwd, g, dim3(256), 0, (hipStream_t)stream, points, P, d_grid, d_z, d_points, partial, H, W, eps);
+    if (dP != nullptr)
+        hipLaunchKernelGGL((bp_reduce_4x4<3, 4>), dim3(B), dim3(64), 0, (hipStream_t)stream, (const float*)partial, dP, (int)g.x);
     return launch_status();
 }
 

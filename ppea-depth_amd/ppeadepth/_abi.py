@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -109,6 +109,12 @@ SIGNATURES = {
     "ppea_backproject_project_fwd_f32": [_vp] * 4 + [_i] * 3 + [_f, _vp],
     "ppea_backproject_project_bwd_workspace_bytes": [_i] * 3,
     "ppea_backproject_project_bwd_f32": [_vp] * 7 + [_i] * 3 + [_f, _vp],
+    "ppea_backproject_fwd_f32": [_vp] * 3 + [_i] * 3 + [_vp],
+    "ppea_backproject_bwd_workspace_bytes": [_i] * 3,
+    "ppea_backproject_bwd_f32": [_vp] * 6 + [_i] * 3 + [_vp],
+    "ppea_project3d_fwd_f32": [_vp] * 4 + [_i] * 3 + [_f, _vp],
+    "ppea_project3d_bwd_workspace_bytes": [_i] * 3,
+    "ppea_project3d_bwd_f32": [_vp] * 7 + [_i] * 3 + [_f, _vp],
     "ppea_grid_sample_fwd_f32": [_vp] * 3 + [_i] * 7 + [_vp],
     "ppea_grid_sample_bwd_grid_f32": [_vp] * 4 + [_i] * 7 + [_vp],
     "ppea_pose_matrix_fwd_f32": [_vp, _vp, _vp, _i, _i, _vp],

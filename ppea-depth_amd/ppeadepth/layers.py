@@ -149,32 +149,55 @@ class ConvBlock(nn.Module):
 
 class BackprojectDepth(nn.Module):
     """layers.py:138-168: depth [B,1,H,W], inv_K [B,4,4] -> homogeneous points [B,4,HW].
-    Kept for API compatibility; the training step uses the fused `backproject_project` kernel and
-    never materialises the point cloud."""
+    On the device one launch (`ops.backproject`, csrc/geometry.hip backproject_*): fp32 also under autocast, pixel
+    coordinates from the thread index, so a device-side instance holds no [B,3,HW] buffer.  inv_K [1,4,4] serves all B
+    items (the matching encoders' `batch_size=num_depth_bins` use), as in the composite's broadcasting matmul.  On the host
+    the reference's composite.  `pix_coords` / `ones` keep their names but are no longer buffers that follow `.to(device)`:
+    they are properties that build the host tensors (B*4*HW floats) on first read and always return HOST tensors, also on
+    an instance that was moved to the device; only the host path reads them.  The training step uses the fused
+    `backproject_project` kernel and never materialises the point cloud."""
 
     def __init__(self, batch_size, height, width):
         super().__init__()
         self.batch_size, self.height, self.width = batch_size, height, width
-        ys, xs = torch.meshgrid(torch.arange(height, dtype=torch.float32),
-                                torch.arange(width, dtype=torch.float32), indexing="ij")
-        pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(height * width)], 0)
-        self.register_buffer("pix_coords", pix[None].repeat(batch_size, 1, 1), persistent=False)
-        self.register_buffer("ones", torch.ones(batch_size, 1, height * width), persistent=False)
+        self._host = None
+
+    def _host_buffers(self):
+        if self._host is None:
+            ys, xs = torch.meshgrid(torch.arange(self.height, dtype=torch.float32),
+                                    torch.arange(self.width, dtype=torch.float32), indexing="ij")
+            pix = torch.stack([xs.reshape(-1), ys.reshape(-1), torch.ones(self.height * self.width)], 0)
+            self._host = (pix[None].repeat(self.batch_size, 1, 1), torch.ones(self.batch_size, 1, self.height * self.width))
+        return self._host
+
+    @property
+    def pix_coords(self):
+        return self._host_buffers()[0]
+
+    @property
+    def ones(self):
+        return self._host_buffers()[1]
 
     def forward(self, depth, inv_K):
+        if depth.is_cuda:
+            return ops.backproject(depth.reshape(self.batch_size, 1, self.height, self.width), inv_K)
         cam_points = torch.matmul(inv_K[:, :3, :3], self.pix_coords)
         cam_points = depth.view(self.batch_size, 1, -1) * cam_points
         return torch.cat([cam_points, self.ones], 1)
 
 
 class Project3D(nn.Module):
-    """layers.py:171-199: points [B,4,HW], K, T -> sampling grid [B,H,W,2]."""
+    """layers.py:171-199: points [B,4,HW], K, T -> sampling grid [B,H,W,2] (and with `dc` the projected depth
+    [B,1,H,W]).  On the device one launch after the 4x4 product K @ T (`ops.project3d`, csrc/geometry.hip project3d_*),
+    fp32 also under autocast; K and T may each be [1,4,4] for all B items.  On the host the reference's composite."""
 
     def __init__(self, batch_size, height, width, dc=False, eps=1e-7):
         super().__init__()
         self.batch_size, self.height, self.width, self.eps, self.dc = batch_size, height, width, eps, dc
 
     def forward(self, points, K, T):
+        if points.is_cuda:
+            return ops.project3d(points.reshape(self.batch_size, 4, -1), K, T, self.height, self.width, self.eps, self.dc)
         P = torch.matmul(K, T)[:, :3, :]
         cam_points = torch.matmul(P, points)
         pix = cam_points[:, :2, :] / (cam_points[:, 2, :].unsqueeze(1) + self.eps)

@@ -302,6 +302,105 @@ def backproject_project(depth, inv_K, K, T, eps=1e-7):
     return _BackprojectProject.apply(depth, inv_K, P, eps)
 
 
+# The two halves on their own (layers.BackprojectDepth / layers.Project3D): the same arithmetic split at the point cloud.
+def _device_f32(name, *ts):
+    """fp32 contiguous views of device tensors; a host tensor is refused (no CPU path behind an op)."""
+    for t in ts:
+        if not t.is_cuda:
+            raise PpeaKernelError(f"{name}: PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback)")
+    return [t.contiguous().float() for t in ts]
+
+
+def _per_item(m, B):
+    """[1,4,4] -> [B,4,4] as the kernels index it (one small copy; autograd sums the gradient back); [B,4,4] as it is."""
+    return m if m.shape[0] == B else m.expand(B, 4, 4).contiguous()
+
+
+class _Backproject(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, depth, inv_K):
+        B, _, H, W = depth.shape
+        points = torch.empty(B, 4, H * W, device=depth.device, dtype=_F32)
+        call("ppea_backproject_fwd_f32", ptr(depth), ptr(inv_K), ptr(points), B, H, W, stream_ptr())
+        ctx.save_for_backward(depth, inv_K)
+        return points
+
+    @staticmethod
+    def backward(ctx, d_points):
+        depth, inv_K = ctx.saved_tensors
+        B, _, H, W = depth.shape
+        d_depth = torch.empty_like(depth) if ctx.needs_input_grad[0] else None
+        d_inv_K = ws = None
+        if ctx.needs_input_grad[1]:
+            d_inv_K = torch.empty_like(inv_K)
+            ws = torch.empty(_abi.lib.ppea_backproject_bwd_workspace_bytes(B, H, W) // 4, device=depth.device, dtype=_F32)
+        call("ppea_backproject_bwd_f32", ptr(depth), ptr(inv_K), ptr(d_points.contiguous().float()), ptr(d_depth),
+             ptr(d_inv_K), ptr(ws), B, H, W, stream_ptr())
+        return d_depth, d_inv_K
+
+
+def backproject(depth, inv_K):
+    """depth [B,1,H,W], inv_K [B,4,4] -> homogeneous points [B,4,HW] fp32 (row 3 = 1), one launch; fp32 under autocast.
+    inv_K [1,4,4] serves every item, as it does in the composite's broadcasting matmul (the reference's matching encoders
+    back-project D depth planes with one camera); its gradient is then the sum over the items."""
+    depth, inv_K = _device_f32("backproject", depth, inv_K)
+    B = depth.shape[0]
+    if depth.dim() != 4 or depth.shape[1] != 1 or inv_K.dim() != 3 or inv_K.shape[0] not in (1, B) or inv_K.shape[1:] != (4, 4):
+        raise PpeaKernelError(f"backproject: depth {tuple(depth.shape)}, inv_K {tuple(inv_K.shape)}")
+    with torch.autocast("cuda", enabled=False):
+        return _Backproject.apply(depth, _per_item(inv_K, B))
+
+
+class _Project3D(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, P, H, W, eps, with_depth):
+        B = points.shape[0]
+        grid = torch.empty(B, H, W, 2, device=points.device, dtype=_F32)
+        z = torch.empty(B, 1, H, W, device=points.device, dtype=_F32) if with_depth else None
+        call("ppea_project3d_fwd_f32", ptr(points), ptr(P), ptr(grid), ptr(z), B, H, W, float(eps), stream_ptr())
+        ctx.save_for_backward(points, P)
+        ctx.set_materialize_grads(False)         # an unused output of the (grid, z) pair costs no zero fill
+        ctx.dims = (H, W, float(eps), with_depth)
+        return (grid, z) if with_depth else grid
+
+    @staticmethod
+    def backward(ctx, d_grid, d_z=None):
+        points, P = ctx.saved_tensors
+        H, W, eps, with_depth = ctx.dims
+        B = points.shape[0]
+        want_points, want_P = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if d_grid is None and d_z is None:
+            return (None,) * 6
+        if d_grid is None:                       # only the projected depth was used downstream
+            d_grid = torch.zeros(B, H, W, 2, device=points.device, dtype=_F32)
+        if d_z is not None:
+            d_z = d_z.contiguous().float()
+        d_points = torch.empty_like(points) if want_points else None
+        dP = ws = None
+        if want_P:
+            dP = torch.empty_like(P)
+            ws = torch.empty(_abi.lib.ppea_project3d_bwd_workspace_bytes(B, H, W) // 4, device=points.device, dtype=_F32)
+        call("ppea_project3d_bwd_f32", ptr(points), ptr(P), ptr(d_grid.contiguous().float()), ptr(d_z), ptr(d_points),
+             ptr(dP), ptr(ws), B, H, W, eps, stream_ptr())
+        return d_points, dP, None, None, None, None
+
+
+def project3d(points, K, T, H, W, eps=1e-7, with_depth=False):
+    """points [B,4,HW] (row 3 need not be 1), K, T [B,4,4] -> sampling grid [B,H,W,2] fp32, and with `with_depth` the
+    projected depth cam[2] as [B,1,H,W] (Project3D's `dc=True` pair).  K @ T is one 4x4 product as in
+    `backproject_project` and hands K and T their gradients; the kernels read its rows 0-2 in place (no copy of the
+    `[:, :3, :]` slice, no padding of its gradient).  K and T may each be [1,4,4] for all items, as in the composite's
+    broadcasting matmul: the product is still formed once.  fp32 under autocast."""
+    points, K, T = _device_f32("project3d", points, K, T)
+    B = points.shape[0]
+    if tuple(points.shape) != (B, 4, H * W) or any(m.dim() != 3 or m.shape[0] not in (1, B) or m.shape[1:] != (4, 4)
+                                                   for m in (K, T)):
+        raise PpeaKernelError(f"project3d: points {tuple(points.shape)}, K {tuple(K.shape)}, T {tuple(T.shape)} "
+                              f"for {H} x {W}")
+    with torch.autocast("cuda", enabled=False):
+        return _Project3D.apply(points, _per_item(torch.matmul(K, T), B), int(H), int(W), eps, bool(with_depth))
+
+
 # ---------------------------------------------------------------------------------------------
 # A20  grid_sample (bilinear, align_corners=True)            trainer.py:911-914, rkm.py:299
 # ---------------------------------------------------------------------------------------------

@@ -17,7 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops, rng
-from .layers import disp_to_depth
+from .layers import BackprojectDepth, Project3D, disp_to_depth
 
 
 MIN_VAL_EVAL = 1e-3          # trainer.py:657
@@ -103,6 +103,14 @@ class Trainer:
         self.step = 0
         self.is_main = True
         self._identity_cache = None
+        # trainer.py:233-244: the two-module form of the warp geometry, for a `generate_images_pred` written against the
+        # reference (trainer.py:904-909, 955-958); built as the reference builds them, Project3D with its default dc=False
+        # for `--dc` too.  `generate_images_pred` below stays on the fused kernel.
+        self.backproject_depth, self.project_3d = {}, {}
+        for scale in range(self.opt.sclm + 1):
+            h, w = self.opt.height // (2 ** scale), self.opt.width // (2 ** scale)
+            self.backproject_depth[scale] = BackprojectDepth(self.opt.batch_size, h, w).to(self.device)
+            self.project_3d[scale] = Project3D(self.opt.batch_size, h, w).to(self.device)
 
     def _module(self):
         return getattr(self.model, "module", self.model)
