@@ -647,6 +647,36 @@ int ppea_depth_errors_f32(const float* pred_disp, const float* gt, long gt_len, 
 int ppea_depth_errors_mean_f64(const double* errors, double* mean, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Input pipeline on uint8 frames (datasets/mono_dataset.py:89-112, 143-190 through PIL / torchvision), bit for bit:
+ * Pillow's LANCZOS resize of 8-bit images (Resample.c) and torchvision's PIL-path ColorJitter (ImageEnhance blends,
+ * Convert.c RGB <-> HSV).  ppeadepth/input_pipeline.py holds the readable restatement and builds the tables.
+ *   taps [out][2 + kmax] int32: per output column / row (first input index, tap count n <= kmax, n 22-bit fixed-point
+ *   coefficients).  Accumulator int32 from 1 << 21, >> 22 (arithmetic), clip to 0..255.
+ * ppea_lanczos_h_u8: rows.  srcs = HOST array of nsrc <= 8 device pointers, each planes_per_src planes [H][Win]; the planes
+ *   of all sources are numbered through and planes_per_item consecutive planes form an image.  flip [images] int32 or NULL:
+ *   non-zero = the image is read mirrored (the flipped frame is never written); nonzero [images] int32 or NULL: set to
+ *   whether the image holds a non-zero byte (one memset).  dst [planes][H][Wout].  One launch.
+ * ppea_lanczos_v_u8: columns of src [planes][Hin][W] -> dst [planes][Hout][W], planes <= 65535.  One launch.
+ * ppea_color_jitter_u8: img [N][3][H][W] uint8 -> color = img / 255 and color_aug = jitter(img) / 255, both [N][3][H][W]
+ *   fp32 (one correctly rounded division, as ToTensor).  params [N][10] int32: the order of the four operations
+ *   (0 brightness, 1 contrast, 2 saturation, 3 hue), the brightness / contrast / saturation factors as fp32 bit patterns,
+ *   trunc(hue * 255) & 255, apply, one unused word.  An image with apply == 0, or with nonzero[n] == 0 (nonzero may be
+ *   NULL), gets color_aug = color.  workspace: ppea_color_jitter_workspace_bytes(N, H, W) bytes, contents free before and
+ *   after the call.  Two launches for any N: the operations that precede contrast and an exact integer sum of Pillow's L
+ *   per image, then the whole chain with int(mean(L) + 0.5) known.  H * W <= 2^32 / 255, N <= 65535.
+ * ppea_repeat_rows_f32: dst [rows][reps][len] = src [rows][len] (the per-scale K / inv_K of a batch in one launch).
+ * ---------------------------------------------------------------------------------------- */
+int ppea_lanczos_h_u8(const void* const* srcs, int nsrc, long planes_per_src, const int32_t* taps, int kmax,
+                      const int32_t* flip, int planes_per_item, int32_t* nonzero, uint8_t* dst, int H, int Win, int Wout,
+                      void* stream);
+int ppea_lanczos_v_u8(const uint8_t* src, const int32_t* taps, int kmax, uint8_t* dst, long planes, int Hin, int Hout,
+                      int W, void* stream);
+long ppea_color_jitter_workspace_bytes(int N, int H, int W);
+int ppea_color_jitter_u8(const uint8_t* img, const int32_t* params, const int32_t* nonzero, void* workspace, float* color,
+                         float* color_aug, int N, int H, int W, void* stream);
+int ppea_repeat_rows_f32(const float* src, float* dst, int rows, int reps, int len, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training-mode BatchNorm (+ReLU, + residual added before the activation) on channels_last data: the ResNet-18 pose
  * trunk (networks/resnet_encoder.py:25-72).  The tensor is G consecutive sub-batches [G][P][C] (C contiguous,
  * C / 8 a power of two <= 256), each normalised with its own statistics (per-pair statistics of a 2B pose batch).

@@ -1,0 +1,417 @@
+// Input pipeline on uint8 frames, gfx950: Pillow's LANCZOS resize (Resample.c, 8-bit images) and torchvision's PIL-path
+// ColorJitter (ImageEnhance blends, Convert.c RGB <-> HSV), bit for bit (ppeadepth/input_pipeline.py is the readable
+// restatement; tests/test_input_pipeline_gpu.py compares every byte).
+//
+//   lanczos_h   one workgroup stages `rpb` whole input rows in LDS (mirrored when the item is flipped, so a flipped frame is
+//               never materialised), then one thread per output pixel: int32 accumulator from 1 << 21 over the row's
+//               (xmin, n, coeffs[n]) entry of the tap table, >> 22, clip.  Every input byte is read exactly once, so the
+//               same pass marks the images that hold a non-zero byte (a missing neighbour frame is all zeros).
+//   lanczos_v   the same arithmetic down the columns of the 8-bit intermediate, 4 columns per thread through 32-bit words
+//               when the row length allows.
+//   jitter_sum  the item's pointwise operations that precede contrast, then Pillow's RGB -> L; an exact integer sum per
+//               2048- or 4096-pixel chunk (no atomics: the partial sums are added again, in order, by every workgroup of
+//               the second launch).
+//   jitter_out  reads the resized uint8 image once, recomputes the chain with int(mean(L) + 0.5) known and writes `color`
+//               and `color_aug` as fp32 x / 255 (one IEEE division, as ToTensor).
+// Arithmetic rules: integer where Pillow is integer; fp32 / fp64 operations one at a time in Pillow's order (the file is
+// built with -ffp-contract=off), true divisions, no fast-math intrinsic.  All operations of an item are uniform over a
+// workgroup (one image per blockIdx.y), so the order switch does not diverge.
+#include "common.h"
+
+namespace {
+
+constexpr int THREADS = 256;
+constexpr int PRECISION_BITS = 32 - 8 - 2;      // Pillow Resample.c
+constexpr int MAX_SRCS = 8;
+constexpr int MAX_RPB = 32;                     // rows per workgroup of the horizontal pass
+constexpr int LDS_LIMIT = 60 * 1024;
+constexpr int PARAM_WORDS = 10;                 // order[4], brightness, contrast, saturation (fp32 bits), hue shift, apply, pad
+constexpr int JITTER_ITERS = 4;                 // pixel groups per thread and chunk
+
+struct Srcs {
+    const uint8_t* p[MAX_SRCS];
+};
+
+__host__ __device__ __forceinline__ int clip8(int acc) {
+    acc >>= PRECISION_BITS;                     // arithmetic shift, as Pillow's
+    return acc < 0 ? 0 : (acc > 255 ? 255 : acc);
+}
+
+// One tap-table row, clamped to the input so that a malformed table cannot index outside it.
+struct Taps {
+    const int* c;
+    int lo, n;
+};
+__device__ __forceinline__ Taps taps_of(const int* __restrict__ table, int kmax, int i, int insize) {
+    const int* t = table + (long)i * (2 + kmax);
+    Taps r;
+    r.lo = min(max(t[0], 0), insize);
+    r.n = min(min(max(t[1], 0), kmax), insize - r.lo);
+    r.c = t + 2;
+    return r;
+}
+
+__global__ __launch_bounds__(THREADS) void lanczos_h(Srcs srcs, long rows_per_src, const int* __restrict__ table, int kmax,
+                                                     const int* __restrict__ flip, int rows_per_item,
+                                                     int* __restrict__ nonzero, uint8_t* __restrict__ dst, long rows,
+                                                     int Win, int Wout, int rpb) {
+    extern __shared__ uint8_t line[];           // [rpb][Win]
+    __shared__ const uint8_t* row_src[MAX_RPB];
+    __shared__ int row_flip[MAX_RPB], row_nz[MAX_RPB];
+    const long row0 = (long)blockIdx.x * rpb;
+    const int nr = (int)min((long)rpb, rows - row0);
+    if (threadIdx.x < nr) {
+        const long g = row0 + threadIdx.x;
+        const int s = (int)(g / rows_per_src);
+        const uint8_t* base = nullptr;
+#pragma unroll
+        for (int k = 0; k < MAX_SRCS; ++k) base = k == s ? srcs.p[k] : base;
+        row_src[threadIdx.x] = base + (g - s * rows_per_src) * Win;
+        row_flip[threadIdx.x] = flip && flip[g / rows_per_item] != 0;
+        row_nz[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nr * Win; i += THREADS) {
+        const int r = i / Win, x = i - r * Win;
+        const uint8_t v = row_src[r][x];
+        line[r * Win + (row_flip[r] ? Win - 1 - x : x)] = v;
+        if (v) row_nz[r] = 1;                   // every writer stores the same value
+    }
+    __syncthreads();
+    if (nonzero && threadIdx.x < nr && row_nz[threadIdx.x]) {
+        int* flag = nonzero + (row0 + threadIdx.x) / rows_per_item;
+        if (__atomic_load_n(flag, __ATOMIC_RELAXED) == 0) atomicOr(flag, 1);
+    }
+    for (int i = threadIdx.x; i < nr * Wout; i += THREADS) {
+        const int r = i / Wout, x = i - r * Wout;
+        const Taps t = taps_of(table, kmax, x, Win);
+        const uint8_t* in = line + r * Win + t.lo;
+        int acc = 1 << (PRECISION_BITS - 1);
+        for (int k = 0; k < t.n; ++k) acc += (int)in[k] * t.c[k];
+        dst[(row0 + r) * Wout + x] = (uint8_t)clip8(acc);
+    }
+}
+
+// grid (ceil(Hout * W / VEC / THREADS), planes); VEC = 4 needs W % 4 == 0 (then every row starts on a 32-bit word)
+template <int VEC>
+__global__ __launch_bounds__(THREADS) void lanczos_v(const uint8_t* __restrict__ src, const int* __restrict__ table, int kmax,
+                                                     uint8_t* __restrict__ dst, int Hin, int Hout, int W) {
+    const int Wv = W / VEC;
+    const int i = blockIdx.x * THREADS + threadIdx.x;
+    if (i >= Hout * Wv) return;
+    const int y = i / Wv, x = (i - y * Wv) * VEC;
+    const Taps t = taps_of(table, kmax, y, Hin);
+    const uint8_t* in = src + ((long)blockIdx.y * Hin + t.lo) * W + x;
+    int acc[VEC];
+#pragma unroll
+    for (int v = 0; v < VEC; ++v) acc[v] = 1 << (PRECISION_BITS - 1);
+    for (int k = 0; k < t.n; ++k) {
+        const int c = t.c[k];
+        if (VEC == 4) {
+            const uint32_t w = *(const uint32_t*)(in + (long)k * W);
+#pragma unroll
+            for (int v = 0; v < VEC; ++v) acc[v] += (int)((w >> (8 * v)) & 255u) * c;
+        } else {
+            acc[0] += (int)in[(long)k * W] * c;
+        }
+    }
+    uint8_t* out = dst + ((long)blockIdx.y * Hout + y) * W + x;
+    if (VEC == 4) {
+        uint32_t w = 0;
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) w |= (uint32_t)clip8(acc[v]) << (8 * v);
+        *(uint32_t*)out = w;
+    } else {
+        out[0] = (uint8_t)clip8(acc[0]);
+    }
+}
+
+// ---- ColorJitter ---------------------------------------------------------------------------------------------------
+struct Jitter {
+    int order[4];
+    float factor[3];        // brightness, contrast, saturation
+    int hue;                // trunc(h * 255) & 255
+    bool apply;
+};
+__device__ __forceinline__ Jitter jitter_of(const int* __restrict__ params, const int* __restrict__ nonzero, int n) {
+    const int* p = params + (long)n * PARAM_WORDS;
+    Jitter j;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) j.order[k] = p[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) j.factor[k] = __int_as_float(p[4 + k]);
+    j.hue = p[7] & 255;
+    j.apply = p[8] != 0 && (!nonzero || nonzero[n] != 0);
+    return j;
+}
+
+// Pillow RGB -> L
+__host__ __device__ __forceinline__ int gray_u8(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
+
+// PIL.Image.blend(degenerate, image, f): fp32, one rounding per operation, truncated, clipped
+__host__ __device__ __forceinline__ int blend_u8(int deg, int x, float f) {
+    const float d = (float)deg;
+    const float diff = (float)x - d;
+    const float prod = f * diff;
+    const float t = truncf(d + prod);
+    return (int)fminf(fmaxf(t, 0.f), 255.f);
+}
+
+// C round() of a non-negative value, clipped to 8 bits
+__host__ __device__ __forceinline__ int round_u8(double x) { return (int)fmin(fmax(floor(x + 0.5), 0.0), 255.0); }
+
+// Convert.c rgb2hsv, the 8-bit hue shift, hsv2rgb
+__host__ __device__ __forceinline__ void hue_u8(int& r, int& g, int& b, int shift) {
+    const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
+    int uh = 0, us = 0;
+    if (maxc != minc) {
+        const float cr = (float)(maxc - minc);
+        const float s = cr / (float)maxc;
+        const float rc = (float)(maxc - r) / cr, gc = (float)(maxc - g) / cr, bc = (float)(maxc - b) / cr;
+        float h;
+        if (r == maxc) h = bc - gc;
+        else if (g == maxc) h = (float)(2.0 + (double)rc - (double)bc);
+        else h = (float)(4.0 + (double)gc - (double)rc);
+        const double t = (double)h / 6.0 + 1.0;             // in [5/6, 11/6]: fmod(t, 1) = t - floor(t), exactly
+        h = (float)(t - floor(t));
+        uh = min(max((int)((double)h * 255.0), 0), 255);
+        us = min(max((int)((double)s * 255.0), 0), 255);
+    }
+    const int v = maxc;
+    uh = (uh + shift) & 255;
+    if (us == 0) {
+        r = g = b = v;
+        return;
+    }
+    const double hf = (double)(float)uh * 6.0 / 255.0;
+    const double fl = floor(hf);
+    const double f = (double)(float)(hf - fl);
+    const double fs = (double)(float)((double)(float)us / 255.0);
+    const double vv = (double)v;
+    const int p = round_u8(vv * (1.0 - fs));
+    const int q = round_u8(vv * (1.0 - fs * f));
+    const int t = round_u8(vv * (1.0 - fs * (1.0 - f)));
+    switch ((int)fl % 6) {
+    case 0: r = v, g = t, b = p; break;
+    case 1: r = q, g = v, b = p; break;
+    case 2: r = p, g = v, b = t; break;
+    case 3: r = p, g = q, b = v; break;
+    case 4: r = t, g = p, b = v; break;
+    default: r = v, g = p, b = q; break;
+    }
+}
+
+// operation 0 brightness, 1 contrast (needs the image's gray mean), 2 saturation, 3 hue
+__host__ __device__ __forceinline__ void jitter_op(int op, const Jitter& j, int mean, int& r, int& g, int& b) {
+    if (op == 0) {
+        r = blend_u8(0, r, j.factor[0]), g = blend_u8(0, g, j.factor[0]), b = blend_u8(0, b, j.factor[0]);
+    } else if (op == 1) {
+        r = blend_u8(mean, r, j.factor[1]), g = blend_u8(mean, g, j.factor[1]), b = blend_u8(mean, b, j.factor[1]);
+    } else if (op == 2) {
+        const int l = gray_u8(r, g, b);
+        r = blend_u8(l, r, j.factor[2]), g = blend_u8(l, g, j.factor[2]), b = blend_u8(l, b, j.factor[2]);
+    } else if (op == 3) {
+        hue_u8(r, g, b, j.hue);
+    }
+}
+
+template <int VEC> struct Pixels {
+    int r[VEC], g[VEC], b[VEC];
+};
+template <int VEC> __device__ __forceinline__ Pixels<VEC> load_pixels(const uint8_t* __restrict__ img, long HW, long i) {
+    Pixels<VEC> p;
+    if (VEC == 4) {
+        const uint32_t wr = *(const uint32_t*)(img + i), wg = *(const uint32_t*)(img + HW + i),
+                       wb = *(const uint32_t*)(img + 2 * HW + i);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v)
+            p.r[v] = (wr >> (8 * v)) & 255u, p.g[v] = (wg >> (8 * v)) & 255u, p.b[v] = (wb >> (8 * v)) & 255u;
+    } else {
+        p.r[0] = img[i], p.g[0] = img[HW + i], p.b[0] = img[2 * HW + i];
+    }
+    return p;
+}
+template <int VEC> __device__ __forceinline__ void store_unit(float* __restrict__ out, const int* c) {
+    if (VEC == 4) {
+        float4 f;
+        f.x = (float)c[0] / 255.0f, f.y = (float)c[1] / 255.0f, f.z = (float)c[2] / 255.0f, f.w = (float)c[3] / 255.0f;
+        *(float4*)out = f;
+    } else {
+        out[0] = (float)c[0] / 255.0f;
+    }
+}
+
+__device__ __forceinline__ uint32_t wave_sum_u(uint32_t v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
+    return v;
+}
+
+// grid (chunks, N); HW % VEC == 0.  partial [N][chunks]: sum of L over the chunk after the operations preceding contrast
+template <int VEC>
+__global__ __launch_bounds__(THREADS) void jitter_sum(const uint8_t* __restrict__ img, const int* __restrict__ params,
+                                                      const int* __restrict__ nonzero, uint32_t* __restrict__ partial,
+                                                      long HW) {
+    const int n = blockIdx.y;
+    const Jitter j = jitter_of(params, nonzero, n);
+    if (!j.apply) return;                       // its partial sums are never read
+    const uint8_t* im = img + (long)n * 3 * HW;
+    const long base = (long)blockIdx.x * (THREADS * VEC * JITTER_ITERS);
+    uint32_t sum = 0;
+#pragma unroll
+    for (int it = 0; it < JITTER_ITERS; ++it) {
+        const long i = base + ((long)it * THREADS + threadIdx.x) * VEC;
+        if (i >= HW) break;
+        Pixels<VEC> p = load_pixels<VEC>(im, HW, i);
+#pragma unroll
+        for (int v = 0; v < VEC; ++v) {
+            for (int k = 0; k < 4 && j.order[k] != 1; ++k) jitter_op(j.order[k], j, 0, p.r[v], p.g[v], p.b[v]);
+            sum += (uint32_t)gray_u8(p.r[v], p.g[v], p.b[v]);
+        }
+    }
+    __shared__ uint32_t part[THREADS / WAVE];
+    sum = wave_sum_u(sum);
+    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int k = 0; k < THREADS / WAVE; ++k) s += part[k];
+        partial[(long)n * gridDim.x + blockIdx.x] = s;
+    }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(THREADS) void jitter_out(const uint8_t* __restrict__ img, const int* __restrict__ params,
+                                                      const int* __restrict__ nonzero, const uint32_t* __restrict__ partial,
+                                                      float* __restrict__ color, float* __restrict__ color_aug, long HW) {
+    const int n = blockIdx.y;
+    const Jitter j = jitter_of(params, nonzero, n);
+    __shared__ int mean_s;
+    int mean = 0;
+    if (j.apply) {                              // uniform over the workgroup
+        if (threadIdx.x < WAVE) {
+            uint32_t s = 0;
+            for (int c = threadIdx.x; c < (int)gridDim.x; c += WAVE) s += partial[(long)n * gridDim.x + c];
+            s = wave_sum_u(s);
+            if (threadIdx.x == 0) mean_s = (int)floor((double)s / (double)HW + 0.5);      // int(mean(L) + 0.5)
+        }
+        __syncthreads();
+        mean = mean_s;
+    }
+    const uint8_t* im = img + (long)n * 3 * HW;
+    float* oc = color + (long)n * 3 * HW;
+    float* oa = color_aug + (long)n * 3 * HW;
+    const long base = (long)blockIdx.x * (THREADS * VEC * JITTER_ITERS);
+#pragma unroll
+    for (int it = 0; it < JITTER_ITERS; ++it) {
+        const long i = base + ((long)it * THREADS + threadIdx.x) * VEC;
+        if (i >= HW) break;
+        Pixels<VEC> p = load_pixels<VEC>(im, HW, i);
+        store_unit<VEC>(oc + i, p.r);
+        store_unit<VEC>(oc + HW + i, p.g);
+        store_unit<VEC>(oc + 2 * HW + i, p.b);
+        if (j.apply) {
+#pragma unroll
+            for (int v = 0; v < VEC; ++v)
+                for (int k = 0; k < 4; ++k) jitter_op(j.order[k], j, mean, p.r[v], p.g[v], p.b[v]);
+        }
+        store_unit<VEC>(oa + i, p.r);
+        store_unit<VEC>(oa + HW + i, p.g);
+        store_unit<VEC>(oa + 2 * HW + i, p.b);
+    }
+}
+
+__global__ __launch_bounds__(THREADS) void repeat_rows(const float* __restrict__ src, float* __restrict__ dst, int reps,
+                                                       int len, long total) {
+    const long i = (long)blockIdx.x * THREADS + threadIdx.x;
+    if (i >= total) return;
+    const long row = i / ((long)reps * len);
+    dst[i] = src[row * len + i % len];
+}
+
+inline long jitter_chunks(long HW, int vec) {
+    const long chunk = (long)THREADS * vec * JITTER_ITERS;
+    return (HW + chunk - 1) / chunk;
+}
+inline int jitter_vec(long HW) { return HW % 4 == 0 ? 4 : 1; }
+
+}  // namespace
+
+// srcs: HOST array of nsrc device pointers, each `planes_per_src` planes of [H][Win]; the planes of all sources are
+// numbered through, `planes_per_item` consecutive planes form an image (flip / nonzero index).
+extern "C" int ppea_lanczos_h_u8(const void* const* srcs, int nsrc, long planes_per_src, const int32_t* taps, int kmax,
+                                 const int32_t* flip, int planes_per_item, int32_t* nonzero, uint8_t* dst, int H, int Win,
+                                 int Wout, void* stream) {
+    if (!srcs || !taps || !dst) return PPEA_ERR_ARG;
+    if (nsrc <= 0 || planes_per_src <= 0 || planes_per_item <= 0 || kmax <= 0 || H <= 0 || Win <= 0 || Wout <= 0)
+        return PPEA_ERR_ARG;
+    if (nsrc > MAX_SRCS || Win > LDS_LIMIT) return PPEA_ERR_UNSUPPORTED;
+    const long planes = planes_per_src * nsrc;
+    if (planes % planes_per_item != 0 || planes > 0x7fffffffL / H) return PPEA_ERR_ARG;
+    Srcs s;
+    for (int i = 0; i < MAX_SRCS; ++i) {
+        s.p[i] = i < nsrc ? (const uint8_t*)srcs[i] : nullptr;
+        if (i < nsrc && !s.p[i]) return PPEA_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    if (nonzero) {
+        hipError_t e = hipMemsetAsync(nonzero, 0, (size_t)(planes / planes_per_item) * sizeof(int32_t), st);
+        if (e != hipSuccess) return (int)e;
+    }
+    const long rows = planes * H;
+    int rpb = THREADS / Wout;
+    rpb = rpb < 1 ? 1 : (rpb > MAX_RPB ? MAX_RPB : rpb);
+    if (rpb > LDS_LIMIT / Win) rpb = LDS_LIMIT / Win;
+    const long blocks = (rows + rpb - 1) / rpb;
+    if (blocks > 0x7fffffffL) return PPEA_ERR_UNSUPPORTED;
+    lanczos_h<<<(unsigned)blocks, THREADS, (size_t)rpb * Win, st>>>(s, planes_per_src * H, taps, kmax, flip,
+                                                                  planes_per_item * H, nonzero, dst, rows, Win, Wout, rpb);
+    return launch_status();
+}
+
+extern "C" int ppea_lanczos_v_u8(const uint8_t* src, const int32_t* taps, int kmax, uint8_t* dst, long planes, int Hin,
+                                 int Hout, int W, void* stream) {
+    if (!src || !taps || !dst || planes <= 0 || kmax <= 0 || Hin <= 0 || Hout <= 0 || W <= 0) return PPEA_ERR_ARG;
+    if (planes > 65535 || (long)Hout * W > 0x7fffffffL || (long)Hin * W > 0x7fffffffL) return PPEA_ERR_UNSUPPORTED;
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = W % 4 == 0 && ((uintptr_t)src | (uintptr_t)dst) % 4 == 0;
+    const long work = (long)Hout * (vec ? W / 4 : W);
+    const dim3 grid((unsigned)((work + THREADS - 1) / THREADS), (unsigned)planes);
+    if (vec) lanczos_v<4><<<grid, THREADS, 0, st>>>(src, taps, kmax, dst, Hin, Hout, W);
+    else lanczos_v<1><<<grid, THREADS, 0, st>>>(src, taps, kmax, dst, Hin, Hout, W);
+    return launch_status();
+}
+
+extern "C" long ppea_color_jitter_workspace_bytes(int N, int H, int W) {
+    if (N <= 0 || H <= 0 || W <= 0) return PPEA_ERR_ARG;
+    return (long)N * jitter_chunks((long)H * W, 1) * (long)sizeof(uint32_t);      // the scalar path's chunk count: the larger
+}
+
+// img [N][3][H][W] uint8; params [N][10] int32; nonzero [N] int32 or NULL (0: the image is never jittered);
+// color, color_aug [N][3][H][W] fp32.  Two launches for any N.
+extern "C" int ppea_color_jitter_u8(const uint8_t* img, const int32_t* params, const int32_t* nonzero, void* workspace,
+                                    float* color, float* color_aug, int N, int H, int W, void* stream) {
+    if (!img || !params || !workspace || !color || !color_aug || N <= 0 || H <= 0 || W <= 0) return PPEA_ERR_ARG;
+    const long HW = (long)H * W;
+    if (N > 65535 || HW > 0xffffffffL / 255) return PPEA_ERR_UNSUPPORTED;      // the gray sum of an image fits 32 bits
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = jitter_vec(HW) == 4 && ((uintptr_t)img | (uintptr_t)color | (uintptr_t)color_aug) % 16 == 0;
+    const dim3 grid((unsigned)jitter_chunks(HW, vec ? 4 : 1), (unsigned)N);
+    uint32_t* partial = (uint32_t*)workspace;
+    if (vec) {
+        jitter_sum<4><<<grid, THREADS, 0, st>>>(img, params, nonzero, partial, HW);
+        jitter_out<4><<<grid, THREADS, 0, st>>>(img, params, nonzero, partial, color, color_aug, HW);
+    } else {
+        jitter_sum<1><<<grid, THREADS, 0, st>>>(img, params, nonzero, partial, HW);
+        jitter_out<1><<<grid, THREADS, 0, st>>>(img, params, nonzero, partial, color, color_aug, HW);
+    }
+    return launch_status();
+}
+
+// dst [rows][reps][len] = src [rows][len] repeated: the per-scale K / inv_K of a batch in one launch
+extern "C" int ppea_repeat_rows_f32(const float* src, float* dst, int rows, int reps, int len, void* stream) {
+    if (!src || !dst || rows <= 0 || reps <= 0 || len <= 0) return PPEA_ERR_ARG;
+    const long total = (long)rows * reps * len;
+    repeat_rows<<<(unsigned)((total + THREADS - 1) / THREADS), THREADS, 0, (hipStream_t)stream>>>(src, dst, reps, len, total);
+    return launch_status();
+}

@@ -13,6 +13,9 @@ draw per item shared by all its frames, `ToTensor`, and the per-scale intrinsics
   on uint8 batches -- ImageEnhance blends, Pillow's RGB <-> HSV integer conversions, 8-bit quantisation after every
   operation, a fresh parameter draw for every frame and scale -- BIT-EXACT with Pillow (tests/test_host_cpu.py against
   a Pillow-based restatement kept with the test infrastructure).
+* On a GPU the pipeline runs in HIP kernels (csrc/input_pipeline.hip through ops.lanczos_resize_u8 / ops.color_jitter_u8):
+  the same integer / IEEE arithmetic on uint8, every byte of output equal.  The torch formulation below stays as the CPU
+  path, as `backend="torch"` on a GPU, and as the comparison target of tests/test_input_pipeline_gpu.py.
 """
 import math
 
@@ -52,19 +55,59 @@ def lanczos_matrix(insize, outsize):
     return m
 
 
-class LanczosResize:
-    """uint8 [.., Hin, Win] -> uint8 [.., Hout, Wout], bit-exact with PIL's LANCZOS resize of an 8-bit image."""
+def compact_taps(matrix):
+    """Dense [outsize, insize] coefficient matrix -> int32 [outsize, 2 + kmax]: per output (first input index, tap count n,
+    the n coefficients, zero-padded to the longest row): the form the HIP kernels read (Pillow's own `bounds` / `kk`)."""
+    out = []
+    for row in np.asarray(matrix):
+        nz = np.flatnonzero(row)
+        out.append((int(nz[0]), row[nz[0]:nz[-1] + 1].astype(np.int64)))
+    kmax = max(len(c) for _, c in out)
+    table = np.zeros((len(out), 2 + kmax), dtype=np.int32)
+    for i, (lo, c) in enumerate(out):
+        table[i, 0], table[i, 1], table[i, 2:2 + len(c)] = lo, len(c), c
+    return table
 
-    def __init__(self, in_hw, out_hw, device):
-        self.in_hw, self.out_hw = tuple(in_hw), tuple(out_hw)
-        self.mh = torch.from_numpy(lanczos_matrix(in_hw[1], out_hw[1])).to(device)      # horizontal: [Wout, Win]
-        self.mv = torch.from_numpy(lanczos_matrix(in_hw[0], out_hw[0])).to(device)      # vertical:   [Hout, Hin]
+
+def dense_taps(table, insize):
+    """Inverse of compact_taps: the dense [outsize, insize] fp64 matrix."""
+    m = np.zeros((len(table), insize), dtype=np.float64)
+    for i, row in enumerate(np.asarray(table)):
+        m[i, row[0]:row[0] + row[1]] = row[2:2 + row[1]]
+    return m
+
+
+def identity_taps(size):
+    """One tap of weight 1.0 per output: a pass that changes no byte (the flip-only first horizontal pass)."""
+    return np.stack([np.arange(size), np.ones(size, np.int64), np.full(size, 1 << PRECISION_BITS)], 1).astype(np.int32)
+
+
+class LanczosResize:
+    """uint8 [.., Hin, Win] -> uint8 [.., Hout, Wout], bit-exact with PIL's LANCZOS resize of an 8-bit image.
+    backend "torch": fp64 GEMMs over the dense coefficient matrices; "hip": ops.lanczos_resize_u8 over the compact tables
+    ([N,C,Hin,Win] input, or a list of such tensors; `flip` / `nonzero` as there; `first` = this is the pipeline's first
+    level, whose horizontal pass always runs because it carries the flip and the blank-frame mark)."""
+
+    def __init__(self, in_hw, out_hw, device, backend="torch", first=False):
+        self.in_hw, self.out_hw, self.backend = tuple(in_hw), tuple(out_hw), backend
+        mh, mv = lanczos_matrix(in_hw[1], out_hw[1]), lanczos_matrix(in_hw[0], out_hw[0])
+        if backend == "hip":
+            th = compact_taps(mh) if in_hw[1] != out_hw[1] else (identity_taps(in_hw[1]) if first else None)
+            tv = compact_taps(mv) if in_hw[0] != out_hw[0] else None
+            self.taps_h = None if th is None else torch.from_numpy(th).to(device)
+            self.taps_v = None if tv is None else torch.from_numpy(tv).to(device)
+            return
+        self.mh = torch.from_numpy(mh).to(device)      # horizontal: [Wout, Win]
+        self.mv = torch.from_numpy(mv).to(device)      # vertical:   [Hout, Hin]
 
     @staticmethod
     def _clip8(acc):
         return torch.floor((acc + float(1 << (PRECISION_BITS - 1))) / float(1 << PRECISION_BITS)).clamp_(0, 255)
 
-    def __call__(self, img_u8):
+    def __call__(self, img_u8, flip=None, nonzero=None):
+        if self.backend == "hip":
+            from ppeadepth import ops
+            return ops.lanczos_resize_u8(img_u8, self.out_hw, self.taps_h, self.taps_v, flip, nonzero)
         x = img_u8.to(torch.float64)
         if self.in_hw[1] != self.out_hw[1]:
             x = self._clip8(x @ self.mh.t())                        # rows stay, columns resampled; 8-bit intermediate
@@ -188,15 +231,51 @@ def color_jitter(img_u8, params, apply):
     return torch.where(apply.to(dev).reshape(-1, 1, 1, 1), out, img).to(torch.uint8)
 
 
+def pack_jitter_params(params, apply):
+    """Host side of ops.color_jitter_u8: `draw_jitter_params` dicts (one, or a list that is concatenated along the items)
+    and apply [items] bool -> int32 [items, 10]: order[4], brightness / contrast / saturation as fp32 bit patterns,
+    trunc(hue * 255) & 255, apply, one unused word."""
+    ps = list(params) if isinstance(params, (list, tuple)) else [params]
+    cat = lambda k: torch.cat([p[k].cpu() for p in ps])       # noqa: E731
+    order = cat("order").to(torch.int32)
+    fac = torch.stack([cat("brightness"), cat("contrast"), cat("saturation")], 1).to(torch.float32).contiguous()
+    shift = torch.trunc(cat("hue").to(torch.float64) * 255.0).to(torch.int64) & 255
+    tail = torch.stack([shift, apply.cpu().to(torch.int64), torch.zeros_like(shift)], 1).to(torch.int32)
+    return torch.cat([order, fac.view(torch.int32), tail], 1)
+
+
+def _jitter_of(jitter, f, s, B, generator):
+    """The parameters of frame f at scale s.  `jitter`: one `draw_jitter_params` dict for the whole call (tests), or
+    {(frame, scale): dict}, or None: a fresh draw, like the reference's transform object on every call.  Both backends ask
+    in the same order (frame outer, scale inner), which is the order of the draws."""
+    if jitter is None:
+        return draw_jitter_params(B, generator)
+    return jitter[(f, s)] if (f, s) in jitter else jitter
+
+
 class DeviceInputPipeline:
-    def __init__(self, raw_hw, height, width, device, num_scales=4, frame_idxs=(0, -1, 1), K=KITTI_K, is_train=True):
+    """backend "hip" (the default on a GPU device; refused on the CPU) runs the whole call in HIP kernels, "torch" (the
+    default on the CPU) in the torch formulation above; both return the same bytes.
+
+    A "hip" call launches, whatever the batch size: per pyramid level the horizontal and the vertical resize pass and the
+    two ColorJitter launches, all frames stacked (4 kernels per level, 16 for the 4 levels), plus one launch that
+    repeats K / inv_K over the batch: 17 kernels, one memset (the blank-frame marks) and one host-to-device copy (flip flags
+    and the jitter parameters of every frame and scale in one table).  Nothing is copied back to the host."""
+
+    def __init__(self, raw_hw, height, width, device, num_scales=4, frame_idxs=(0, -1, 1), K=KITTI_K, is_train=True,
+                 backend=None):
         self.device = torch.device(device)
+        self.backend = backend or ("hip" if self.device.type == "cuda" else "torch")
+        if self.backend not in ("hip", "torch"):
+            raise ValueError(f"backend {backend!r}: expected 'hip' or 'torch'")
+        if self.backend == "hip" and self.device.type != "cuda":
+            raise ValueError("backend 'hip' needs a GPU device; the CPU path is backend 'torch'")
         self.height, self.width, self.num_scales = height, width, num_scales
         self.frame_idxs, self.is_train = tuple(frame_idxs), is_train
         self.resize, prev = [], tuple(raw_hw)
         for s in range(num_scales):
             hw = (height // 2 ** s, width // 2 ** s)
-            self.resize.append(LanczosResize(prev, hw, self.device))
+            self.resize.append(LanczosResize(prev, hw, self.device, self.backend, first=(s == 0)))
             prev = hw
         self.K, self.inv_K = [], []
         for s in range(num_scales):                        # mono_dataset.py:173-182
@@ -205,16 +284,24 @@ class DeviceInputPipeline:
             k[1, :] *= height // (2 ** s)
             self.K.append(torch.from_numpy(k).to(self.device))
             self.inv_K.append(torch.from_numpy(np.linalg.pinv(k)).to(self.device))
+        # ToTensor's divisor as a tensor: a true division on every device (the GPU folds a Python scalar into a multiplication
+        # by its reciprocal, which is not the same fp32 value for 126 of the 256 levels)
+        self.unit = torch.full((), 255.0, device=self.device)
+        self.K_rows = torch.stack(self.K + self.inv_K)          # [2 * scales, 4, 4]: repeated over the batch in one launch
 
     @torch.no_grad()
     def __call__(self, raw, do_color_aug=None, do_flip=None, jitter=None, generator=None):
         """raw: {frame id: uint8 [B,3,Hraw,Wraw]} (a missing neighbour = all zeros, mono_dataset.py:160-164).
-        do_color_aug / do_flip: [B] bool (default: drawn with p = 0.5 each when is_train, mono_dataset.py:143-144)."""
+        do_color_aug / do_flip: [B] bool (default: drawn with p = 0.5 each when is_train, mono_dataset.py:143-144).
+        backend "hip": these flags and the jitter parameters are host tensors (as draw_jitter_params returns them); they go
+        to the device in one table, and a device tensor is refused rather than copied back."""
         B = raw[self.frame_idxs[0]].shape[0]
         if do_color_aug is None:
             do_color_aug = (torch.rand(B, generator=generator) > 0.5) if self.is_train else torch.zeros(B, dtype=torch.bool)
         if do_flip is None:
             do_flip = (torch.rand(B, generator=generator) > 0.5) if self.is_train else torch.zeros(B, dtype=torch.bool)
+        if self.backend == "hip":
+            return self._call_hip(raw, B, do_color_aug, do_flip, jitter, generator)
         flip = do_flip.to(self.device).reshape(-1, 1, 1, 1)
         inputs = {}
         for f in self.frame_idxs:
@@ -223,15 +310,45 @@ class DeviceInputPipeline:
             blank = (img.reshape(B, -1).sum(1) == 0)
             for s in range(self.num_scales):
                 img = self.resize[s](img)                               # uint8, chained from the previous scale
-                # `jitter`: a dict (one draw for every call: tests) or {(frame, scale): dict}; default: a fresh draw per
-                # frame and scale, like the reference's transform object (see draw_jitter_params)
-                prm = jitter.get((f, s), jitter) if isinstance(jitter, dict) and (f, s) in jitter else jitter
-                if prm is None:
-                    prm = draw_jitter_params(B, generator)
+                prm = _jitter_of(jitter, f, s, B, generator)
                 aug = color_jitter(img, prm, do_color_aug.to(self.device) & ~blank)
-                inputs[("color", f, s)] = img.to(torch.float32) / 255.0          # ToTensor
-                inputs[("color_aug", f, s)] = aug.to(torch.float32) / 255.0
+                inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
+                inputs[("color_aug", f, s)] = aug.to(torch.float32) / self.unit
         for s in range(self.num_scales):
             inputs[("K", s)] = self.K[s][None].repeat(B, 1, 1)
             inputs[("inv_K", s)] = self.inv_K[s][None].repeat(B, 1, 1)
+        return inputs
+
+    def _call_hip(self, raw, B, do_color_aug, do_flip, jitter, generator):
+        from ppeadepth import ops
+        F, S = len(self.frame_idxs), self.num_scales
+        N = F * B                                                   # all frames stacked, frame-major: image n = fi * B + b
+        # parameters in the torch path's order (frame outer, scale inner), then one table and one copy for the whole call
+        prms = []
+        for f in self.frame_idxs:
+            for s in range(S):
+                prms.append(_jitter_of(jitter, f, s, B, generator))
+        by_scale = [p for s in range(S) for fi in range(F) for p in [prms[fi * S + s]]]
+        for t in [do_color_aug, do_flip] + [v for p in prms for v in p.values()]:
+            if t.device.type != "cpu":             # a device tensor would cost a device-to-host copy inside the call
+                raise ValueError("backend 'hip' takes do_color_aug, do_flip and the jitter parameters as host tensors")
+        table = pack_jitter_params(by_scale, do_color_aug.repeat(S * F))                  # [S * N, 10]
+        host = torch.cat([do_flip.to(torch.int32).repeat(F), table.reshape(-1)])
+        dev = host.to(self.device)
+        flip, params = dev[:N], dev[N:].view(S, N, table.shape[1])
+        nonzero = torch.empty(N, device=self.device, dtype=torch.int32)      # 0: a blank (missing) frame, never jittered
+        img = [raw[f].to(self.device).contiguous() for f in self.frame_idxs]
+        levels = []
+        for s in range(S):
+            img = self.resize[s](img, flip, nonzero) if s == 0 else self.resize[s](img)
+            levels.append(ops.color_jitter_u8(img, params[s], nonzero))
+        inputs = {}
+        for fi, f in enumerate(self.frame_idxs):
+            for s, (color, aug) in enumerate(levels):
+                inputs[("color", f, s)] = color[fi * B:(fi + 1) * B]
+                inputs[("color_aug", f, s)] = aug[fi * B:(fi + 1) * B]
+        KK = ops.repeat_rows(self.K_rows, B)
+        for s in range(S):
+            inputs[("K", s)] = KK[s]
+            inputs[("inv_K", s)] = KK[S + s]
         return inputs

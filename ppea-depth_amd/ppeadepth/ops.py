@@ -762,6 +762,85 @@ def depth_errors_mean(errors):
 
 
 # ---------------------------------------------------------------------------------------------
+# Input pipeline on uint8 frames: Pillow's LANCZOS resize and the PIL-path ColorJitter   (csrc/input_pipeline.hip)
+# ---------------------------------------------------------------------------------------------
+JITTER_PARAM_WORDS = 10
+
+
+def _taps(table, outsize, what):
+    if table.dim() != 2 or table.shape[0] != outsize or table.shape[1] < 3:
+        raise _abi.PpeaKernelError(f"{what} tap table {tuple(table.shape)} does not describe {outsize} outputs")
+    return ptr(table, torch.int32), table.shape[1] - 2
+
+
+@torch.no_grad()
+def lanczos_resize_u8(src, out_hw, taps_h=None, taps_v=None, flip=None, nonzero=None):
+    """src: uint8 [N,C,Hin,Win], or a list of such tensors of one shape (read as if concatenated along N, without the
+    copy) -> uint8 [N,C,Hout,Wout].  taps_h [Wout, 2+k] / taps_v [Hout, 2+k] int32 (input_pipeline.compact_taps); None
+    skips that pass (its input and output sizes are then equal).  Horizontal pass first, 8-bit intermediate.
+    flip [N] int32: non-zero = image n is mirrored left-right first (needs taps_h); nonzero [N] int32: written,
+    1 where image n holds a non-zero byte (needs taps_h)."""
+    srcs = list(src) if isinstance(src, (list, tuple)) else [src]
+    if not srcs or any(s.dim() != 4 or s.shape != srcs[0].shape for s in srcs):
+        raise _abi.PpeaKernelError("expected uint8 [N,C,H,W] images of one shape")
+    n, C, Hin, Win = srcs[0].shape
+    N, (Hout, Wout) = n * len(srcs), out_hw
+    dev = srcs[0].device
+    if taps_h is None and (Win != Wout or flip is not None or nonzero is not None):
+        raise _abi.PpeaKernelError("the flip, the non-zero mark and a change of width need the horizontal pass")
+    if taps_v is None and Hin != Hout:
+        raise _abi.PpeaKernelError("a change of height needs the vertical pass")
+    for t in (flip, nonzero):
+        if t is not None and tuple(t.shape) != (N,):
+            raise _abi.PpeaKernelError(f"expected one flag per image ({N}), got {tuple(t.shape)}")
+    cur = None
+    if taps_h is not None:
+        tp, kmax = _taps(taps_h, Wout, "horizontal")
+        ptrs = (_ct.c_void_p * len(srcs))(*[ptr(s, torch.uint8).value for s in srcs])
+        cur = torch.empty(N, C, Hin, Wout, device=dev, dtype=torch.uint8)
+        call("ppea_lanczos_h_u8", ptrs, len(srcs), n * C, tp, kmax, ptr(flip, torch.int32), C, ptr(nonzero, torch.int32),
+             ptr(cur), Hin, Win, Wout, stream_ptr())
+    elif len(srcs) != 1:
+        raise _abi.PpeaKernelError("several sources are read by the horizontal pass only")
+    else:
+        cur = srcs[0]
+    if taps_v is not None:
+        tp, kmax = _taps(taps_v, Hout, "vertical")
+        out = torch.empty(N, C, Hout, Wout, device=dev, dtype=torch.uint8)
+        call("ppea_lanczos_v_u8", ptr(cur, torch.uint8), tp, kmax, ptr(out), N * C, Hin, Hout, Wout, stream_ptr())
+        cur = out
+    return cur
+
+
+@torch.no_grad()
+def color_jitter_u8(img, params, nonzero=None):
+    """img uint8 [N,3,H,W]; params int32 [N,10] (input_pipeline.pack_jitter_params); nonzero [N] int32 or None (0 = the
+    image is blank and is never jittered) -> (color, color_aug) fp32 [N,3,H,W] = img / 255, jitter(img) / 255."""
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise _abi.PpeaKernelError(f"expected uint8 [N,3,H,W], got {tuple(img.shape)}")
+    N, _, H, W = img.shape
+    if tuple(params.shape) != (N, JITTER_PARAM_WORDS) or (nonzero is not None and tuple(nonzero.shape) != (N,)):
+        raise _abi.PpeaKernelError(f"parameter table {tuple(params.shape)} does not describe {N} images")
+    im, pp, nz = ptr(img, torch.uint8), ptr(params, torch.int32), ptr(nonzero, torch.int32)
+    nbytes = _abi.lib.ppea_color_jitter_workspace_bytes(N, H, W)
+    if nbytes < 0:
+        _abi.check(int(nbytes), "ppea_color_jitter_workspace_bytes")
+    ws = torch.empty(nbytes, device=img.device, dtype=torch.uint8)
+    color = torch.empty(N, 3, H, W, device=img.device, dtype=_F32)
+    aug = torch.empty_like(color)
+    call("ppea_color_jitter_u8", im, pp, nz, ptr(ws), ptr(color), ptr(aug), N, H, W, stream_ptr())
+    return color, aug
+
+
+@torch.no_grad()
+def repeat_rows(src, reps):
+    """src fp32 [R, ...] -> [R, reps, ...]: every row repeated `reps` times, one launch."""
+    out = torch.empty((src.shape[0], reps) + tuple(src.shape[1:]), device=src.device, dtype=_F32)
+    call("ppea_repeat_rows_f32", ptr(src, _F32), ptr(out), src.shape[0], reps, src[0].numel(), stream_ptr())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # A2 + block glue: y = act(BN_a(z1) [+ BN_b(z2)]) [* mask[n]] [+ r1] [+ s * r2]   (csrc/bn_fused.hip)
 # ---------------------------------------------------------------------------------------------
 import ctypes as _ct
