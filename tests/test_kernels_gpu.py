@@ -198,10 +198,10 @@ def test_backproject_project_golden(device, golden):
     assert (grid.cpu() - g["grid"]).abs().max() < 2e-5
 
 
-def test_backproject_project_grad(device):
+@pytest.mark.parametrize("B,H,W", [(2, 24, 40), (1, 5, 7), (3, 3, 300)])
+def test_backproject_project_grad(device, B, H, W):
     ops = _ops()
     from oracle import synth
-    B, H, W = 2, 24, 40
     depth = 0.5 + 5 * torch.rand(B, 1, H, W, generator=_g(1))
     K, inv_K = synth.kitti_K(H, W, 0)
     K, inv_K = K[None].repeat(B, 1, 1), inv_K[None].repeat(B, 1, 1)
