@@ -1462,7 +1462,9 @@ class _MaxPoolNhwc(torch.autograd.Function):
 def maxpool3x3s2(x):
     """nn.MaxPool2d(3, 2, 1)(x) for a channels_last HIP tensor (C % 8 == 0, fp32 / bf16) on the gather kernels; None when
     this call is not served."""
-    if not (x.is_cuda and x.dim() == 4 and x.dtype in (_F32, _BF16) and x.shape[1] % 8 == 0 and _is_nhwc(x)):
+    # (a 1 x 1 map is channels_last and NCHW-contiguous at once: same bytes, served)
+    if not (x.is_cuda and x.dim() == 4 and x.dtype in (_F32, _BF16) and x.shape[1] % 8 == 0
+            and x.is_contiguous(memory_format=torch.channels_last)):
         return None
     return _MaxPoolNhwc.apply(x)
 
