@@ -633,6 +633,9 @@ int ppea_cost_volume_reduce_f32(const float* cost, const float* bins, float* cos
  *   pred_disp [B,h,w] fp32 = disp_to_depth-scaled disparity; gt = flat fp32 buffer of gt_len values holding ragged
  *   ground-truth maps; table [B][3] int64 = (offset into gt, H_gt, W_gt) of each image of the batch;
  *   mode 0: range test only, 1: eigen (Garg/Eigen crop), 2: cityscapes (first round(0.75 H) rows, window [256:, 192:1856]);
+ *   mode 3: Trainer.val_ddad (trainer.py:583-623): the DEPTH is resized (the reciprocals of the four source disparities are
+ *   interpolated with the same weights), the range test is 1e-3 < gt < 200, the clamp [1e-3, 200], the whole map is scored;
+ *   any other mode: PPEA_ERR_UNSUPPORTED;
  *   max_region >= the largest scored rectangle (rows x columns after the crop) of the batch: the workspace stride.  An image
  *   whose table row does not fit gt_len / max_region, or with no valid pixel, gives NaN errors and count 0;
  *   workspace: ppea_depth_errors_workspace_bytes(B, max_region) bytes, contents free before and after the call;

@@ -1,4 +1,6 @@
-// Depth-error protocol of Trainer.val on the device, gfx950 (trainer.py:780-843, evaluate_depth.py:35-54).
+// Depth-error protocol of Trainer.val on the device, gfx950 (trainer.py:780-843, evaluate_depth.py:35-54), and of
+// Trainer.val_ddad (trainer.py:583-623) as MODE_DDAD: the depth 1 / disparity is what is resized (the reciprocals of the four
+// source disparities are interpolated), the range test and the clamp end at 200 m, the whole map is scored.
 //
 // One scored batch = one memset + 7 launches, whatever B is; images sit on grid axis y, fixed 2048-pixel chunks of an image's
 // crop rectangle ("region") on axis x:
@@ -22,9 +24,13 @@ constexpr int CHUNK = THREADS * ITEMS;      // region pixels per workgroup
 constexpr int NSEL = 4;                     // selection s: array (s >> 1: 0 pred, 1 gt), rank (s & 1: (n-1)/2, n/2)
 constexpr int PASSES = 4;
 constexpr int BINS = 256;
-constexpr float MIN_DEPTH = 1e-3f, MAX_DEPTH = 80.f;
+constexpr float MIN_DEPTH = 1e-3f;
 
-enum { MODE_RANGE = 0, MODE_EIGEN = 1, MODE_CITYSCAPES = 2 };
+enum { MODE_RANGE = 0, MODE_EIGEN = 1, MODE_CITYSCAPES = 2, MODE_DDAD = 3 };
+
+// The range constants are a property of the mode, fixed at compile time: the kernels that read them are instantiated once
+// for val's protocol and once for val_ddad's.
+template <bool DDAD> struct Protocol { static constexpr float MAX_DEPTH = DDAD ? 200.f : 80.f; };
 
 struct Region {
     long off;              // first ground-truth value of the image in the flat buffer
@@ -80,6 +86,7 @@ __device__ __forceinline__ void source(float scale, int dst, int in, int& i0, in
     l0 = 1.f - l1;
 }
 
+template <bool DDAD>
 __global__ __launch_bounds__(THREADS) void eval_gather(const float* __restrict__ pred, const float* __restrict__ gt,
                                                        long gt_len, const int64_t* __restrict__ table,
                                                        float* __restrict__ pred_ws, float* __restrict__ gt_ws,
@@ -100,15 +107,17 @@ __global__ __launch_bounds__(THREADS) void eval_gather(const float* __restrict__
         const int y = r.y0 + ry, x = r.x0 + rx;
         const float g = gt[r.off + (long)y * r.W + x];
         float d = 0.f, gv = 0.f;
-        if (g > MIN_DEPTH && g < MAX_DEPTH) {
+        if (g > MIN_DEPTH && g < Protocol<DDAD>::MAX_DEPTH) {
             int yi, yp, xi, xp;
             float ly0, ly1, lx0, lx1;
             source(sy, y, h, yi, yp, ly0, ly1);
             source(sx, x, w, xi, xp, lx0, lx1);
             const float* row0 = p + (long)yi * w;
             const float* row1 = row0 + (long)yp * w;
-            const float v = ly0 * (lx0 * row0[xi] + lx1 * row0[xi + xp]) + ly1 * (lx0 * row1[xi] + lx1 * row1[xi + xp]);
-            d = (1.f / v) * factor;
+            float a = row0[xi], c = row0[xi + xp], e = row1[xi], f = row1[xi + xp];
+            if (DDAD) a = 1.f / a, c = 1.f / c, e = 1.f / e, f = 1.f / f;      // val_ddad resizes the depth
+            const float v = ly0 * (lx0 * a + lx1 * c) + ly1 * (lx0 * e + lx1 * f);
+            d = (DDAD ? v : 1.f / v) * factor;
             gv = g;
             ++valid;
         }
@@ -215,6 +224,7 @@ __device__ __forceinline__ float log_f32(float x) { return (float)log((double)x)
 
 constexpr int NSUM = 7;      // abs_rel, sq_rel, squared error, squared log error, thresh < 1.25, < 1.25^2, < 1.25^3
 
+template <bool DDAD>
 __global__ __launch_bounds__(THREADS) void eval_errors_partial(const float* __restrict__ pred_ws,
                                                                const float* __restrict__ gt_ws,
                                                                const int64_t* __restrict__ table,
@@ -245,7 +255,7 @@ __global__ __launch_bounds__(THREADS) void eval_errors_partial(const float* __re
             float p = pred_ws[(long)b * stride + i];
             if (median_scaling) p = p * ratio;
             p = p < MIN_DEPTH ? MIN_DEPTH : p;
-            p = p > MAX_DEPTH ? MAX_DEPTH : p;
+            p = p > Protocol<DDAD>::MAX_DEPTH ? Protocol<DDAD>::MAX_DEPTH : p;
             const float th = fmaxf(g / p, p / g);
             const float d = g - p, sq = d * d;
             const float l = log_f32(g) - log_f32(p);
@@ -346,7 +356,7 @@ extern "C" int ppea_depth_errors_f32(const float* pred_disp, const float* gt, lo
                                      long max_region, int mode, int median_scaling, float scale, void* stream) {
     if (!pred_disp || !gt || !table || !workspace || !errors || !ratio || !count) return PPEA_ERR_ARG;
     if (B <= 0 || B > 65535 || h <= 0 || w <= 0 || gt_len <= 0 || max_region < 0) return PPEA_ERR_ARG;
-    if (mode < MODE_RANGE || mode > MODE_CITYSCAPES) return PPEA_ERR_UNSUPPORTED;
+    if (mode < MODE_RANGE || mode > MODE_DDAD) return PPEA_ERR_UNSUPPORTED;
     const long stride = max_region > 0 ? max_region : 1;
     if (chunks_of(stride) > 0x7fffffffL) return PPEA_ERR_UNSUPPORTED;
     const Workspace L = layout(B, stride);
@@ -361,11 +371,21 @@ extern "C" int ppea_depth_errors_f32(const float* pred_disp, const float* gt, lo
     if (e != hipSuccess) return (int)e;
     const int chunks = (int)chunks_of(stride);
     const dim3 grid(chunks, B);
-    eval_gather<<<grid, THREADS, 0, st>>>(pred_disp, gt, gt_len, table, pred_ws, gt_ws, cnt, h, w, stride, mode, scale);
+    const bool ddad = mode == MODE_DDAD;
+    if (ddad)
+        eval_gather<true><<<grid, THREADS, 0, st>>>(pred_disp, gt, gt_len, table, pred_ws, gt_ws, cnt, h, w, stride, mode,
+                                                    scale);
+    else
+        eval_gather<false><<<grid, THREADS, 0, st>>>(pred_disp, gt, gt_len, table, pred_ws, gt_ws, cnt, h, w, stride, mode,
+                                                     scale);
     for (int pass = 0; pass < PASSES; ++pass)
         eval_select_pass<<<grid, THREADS, 0, st>>>(pred_ws, gt_ws, table, cnt, hist, gt_len, stride, mode, B, pass);
-    eval_errors_partial<<<grid, THREADS, 0, st>>>(pred_ws, gt_ws, table, cnt, hist, partial, gt_len, stride, mode, B,
-                                                  median_scaling);
+    if (ddad)
+        eval_errors_partial<true><<<grid, THREADS, 0, st>>>(pred_ws, gt_ws, table, cnt, hist, partial, gt_len, stride, mode, B,
+                                                            median_scaling);
+    else
+        eval_errors_partial<false><<<grid, THREADS, 0, st>>>(pred_ws, gt_ws, table, cnt, hist, partial, gt_len, stride, mode, B,
+                                                             median_scaling);
     eval_errors_final<<<B, THREADS, 0, st>>>(partial, cnt, hist, errors, ratio, count, chunks, B);
     return launch_status();
 }

@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 MIN_VAL, MAX_VAL = 1e-3, 80.0          # trainer.py:657-658
+MAX_VAL_DDAD = 200.0                   # trainer.py:605, :621: val_ddad's range test and clamp
 
 ERROR_NAMES = ("abs_rel", "sq_rel", "rmse", "rmse_log", "a1", "a2", "a3")
 
@@ -84,6 +85,35 @@ def evaluate_disps(pred_disps, gt_depths, eval_split="eigen", median_scaling=Tru
     return np.array(errors).mean(0)
 
 
+def evaluate_image_ddad(pred_disp, gt_depth, median_scaling=True, pred_depth_scale_factor=1.0):
+    """One image of `Trainer.val_ddad` (trainer.py:583-623), not `val`'s protocol with another crop: the scaled disparity
+    `disp_to_depth(disp, 1e-3, 80)` [h,w] is inverted FIRST and the depth is resized with `F.interpolate(mode="bilinear")`;
+    every pixel with 1e-3 < gt < 200 is scored, no crop; the clamp is [1e-3, 200].  Returns (the 7 errors, ratio or None).
+    The name "ddad" in `evaluate_image` stays `val`'s 80 m range test (trainer.py:786-815)."""
+    gt_depth = np.asarray(gt_depth)
+    gt_height, gt_width = gt_depth.shape[-2:]
+    pred_depth = 1. / torch.from_numpy(np.ascontiguousarray(pred_disp, dtype=np.float32))[None, None]
+    pred_depth = F.interpolate(pred_depth, (gt_height, gt_width), mode="bilinear", align_corners=False)[0, 0].numpy()
+    mask = np.logical_and(gt_depth > MIN_VAL, gt_depth < MAX_VAL_DDAD)
+    pred_depth = pred_depth[mask]
+    gt_depth = gt_depth[mask]
+    pred_depth = pred_depth * pred_depth_scale_factor
+    ratio = None
+    if median_scaling:
+        ratio = np.median(gt_depth) / np.median(pred_depth)
+        pred_depth = pred_depth * ratio
+    pred_depth[pred_depth < MIN_VAL] = MIN_VAL
+    pred_depth[pred_depth > MAX_VAL_DDAD] = MAX_VAL_DDAD
+    return compute_errors(gt_depth, pred_depth), ratio
+
+
+def evaluate_disps_ddad(pred_disps, gt_depths, median_scaling=True, pred_depth_scale_factor=1.0):
+    """Mean of the 7 errors of `evaluate_image_ddad` over the images (trainer.py:641)."""
+    errors = [evaluate_image_ddad(pred_disps[i], gt_depths[i], median_scaling, pred_depth_scale_factor)[0]
+              for i in range(len(pred_disps))]
+    return np.array(errors).mean(0)
+
+
 # ---- device path ---------------------------------------------------------------------------------------------------
 def region_size(eval_split, gt_height, gt_width):
     """Rows x columns of the rectangle `evaluate_image` scores in a [gt_height, gt_width] map (the crop before the range
@@ -94,7 +124,7 @@ def region_size(eval_split, gt_height, gt_width):
         return max(int(crop[1] - crop[0]), 0) * max(int(crop[3] - crop[2]), 0)
     if eval_split == "cityscapes":
         return max(int(round(gt_height * 0.75)) - 256, 0) * max(min(1856, gt_width) - 192, 0)
-    return gt_height * gt_width
+    return gt_height * gt_width          # the range-test splits and "val_ddad": the whole map
 
 
 class DeviceGroundTruth:
@@ -105,12 +135,33 @@ class DeviceGroundTruth:
         maps = [np.ascontiguousarray(g, dtype=np.float32) for g in gt_depths]
         if not maps or any(m.ndim != 2 for m in maps):
             raise ValueError("gt_depths: a non-empty sequence of [H,W] depth maps")
-        self.shapes = [m.shape for m in maps]
+        shapes = [m.shape for m in maps]
         offsets = np.concatenate([[0], np.cumsum([m.size for m in maps])])
-        self.device = torch.device(device)
-        self.flat = torch.from_numpy(np.concatenate([m.reshape(-1) for m in maps])).to(self.device)
-        self.table = torch.tensor([[int(offsets[i]), h, w] for i, (h, w) in enumerate(self.shapes)],
-                                  dtype=torch.int64).to(self.device)
+        device = torch.device(device)
+        self._set(torch.from_numpy(np.concatenate([m.reshape(-1) for m in maps])).to(device),
+                  torch.tensor([[int(offsets[i]), h, w] for i, (h, w) in enumerate(shapes)], dtype=torch.int64).to(device),
+                  shapes, device)
+
+    def _set(self, flat, table, shapes, device):
+        """Everything an instance holds, for both constructors."""
+        self.flat, self.table, self.shapes, self.device = flat, table, list(shapes), device
+
+    @classmethod
+    def from_batch(cls, depth, device):
+        """The ground truth that arrives inside a batch (`data["depth"]` [B,H,W], ddad_dataset.py:165): a host tensor or array
+        is uploaded with one copy, a device tensor is used where it is; the table is written on the device."""
+        if not torch.is_tensor(depth):
+            depth = torch.from_numpy(np.ascontiguousarray(depth))
+        if depth.dim() != 3 or depth.shape[0] == 0:
+            raise ValueError(f"depth: a [B,H,W] batch of depth maps, got {tuple(depth.shape)}")
+        self = cls.__new__(cls)
+        B, H, W = depth.shape
+        device = torch.device(device)
+        table = torch.stack([torch.arange(B, device=device) * (H * W),
+                             torch.full((B,), H, device=device, dtype=torch.int64),
+                             torch.full((B,), W, device=device, dtype=torch.int64)], 1)
+        self._set(depth.to(device, torch.float32).contiguous().reshape(-1), table, [(H, W)] * B, device)
+        return self
 
     def __len__(self):
         return len(self.shapes)

@@ -37,22 +37,39 @@ def _lanczos(x):
     return 0.0
 
 
-def lanczos_matrix(insize, outsize):
-    """[outsize, insize] fp64 matrix of Pillow's fixed-point LANCZOS coefficients (precompute_coeffs + normalize_coeffs_8bpc)."""
+def _bilinear(x):
+    x = abs(x)                                  # Pillow Resample.c bilinear_filter
+    return 1.0 - x if x < 1.0 else 0.0
+
+
+FILTERS = {"lanczos": (_lanczos, 3.0), "bilinear": (_bilinear, 1.0)}      # Pillow's (filter, support)
+
+
+def resample_matrix(insize, outsize, filter="lanczos"):
+    """[outsize, insize] fp64 matrix of Pillow's fixed-point coefficients of an 8-bit resize (precompute_coeffs +
+    normalize_coeffs_8bpc) with `filter` "lanczos" (support 3) or "bilinear" (the triangle 1 - |x|, support 1)."""
+    if filter not in FILTERS:
+        raise ValueError(f"filter {filter!r}: expected one of {sorted(FILTERS)}")
+    kernel, support = FILTERS[filter]
     scale = insize / outsize
     filterscale = max(scale, 1.0)
-    support = 3.0 * filterscale
+    support = support * filterscale
     m = np.zeros((outsize, insize), dtype=np.float64)
     for xx in range(outsize):
         center = (xx + 0.5) * scale
         xmin = max(int(center - support + 0.5), 0)
         xmax = min(int(center + support + 0.5), insize)
         ss = 1.0 / filterscale
-        w = np.array([_lanczos((x + xmin - center + 0.5) * ss) for x in range(xmax - xmin)], dtype=np.float64)
+        w = np.array([kernel((x + xmin - center + 0.5) * ss) for x in range(xmax - xmin)], dtype=np.float64)
         w /= w.sum()
         fixed = np.where(w < 0, np.trunc(-0.5 + w * (1 << PRECISION_BITS)), np.trunc(0.5 + w * (1 << PRECISION_BITS)))
         m[xx, xmin:xmax] = fixed
     return m
+
+
+def lanczos_matrix(insize, outsize):
+    """[outsize, insize] fp64 matrix of Pillow's fixed-point LANCZOS coefficients."""
+    return resample_matrix(insize, outsize, "lanczos")
 
 
 def compact_taps(matrix):
@@ -83,14 +100,15 @@ def identity_taps(size):
 
 
 class LanczosResize:
-    """uint8 [.., Hin, Win] -> uint8 [.., Hout, Wout], bit-exact with PIL's LANCZOS resize of an 8-bit image.
+    """uint8 [.., Hin, Win] -> uint8 [.., Hout, Wout], bit-exact with PIL's LANCZOS resize of an 8-bit image (or, with
+    filter="bilinear", its BILINEAR resize: the kernels read generic tap tables).
     backend "torch": fp64 GEMMs over the dense coefficient matrices; "hip": ops.lanczos_resize_u8 over the compact tables
     ([N,C,Hin,Win] input, or a list of such tensors; `flip` / `nonzero` as there; `first` = this is the pipeline's first
     level, whose horizontal pass always runs because it carries the flip and the blank-frame mark)."""
 
-    def __init__(self, in_hw, out_hw, device, backend="torch", first=False):
+    def __init__(self, in_hw, out_hw, device, backend="torch", first=False, filter="lanczos"):
         self.in_hw, self.out_hw, self.backend = tuple(in_hw), tuple(out_hw), backend
-        mh, mv = lanczos_matrix(in_hw[1], out_hw[1]), lanczos_matrix(in_hw[0], out_hw[0])
+        mh, mv = resample_matrix(in_hw[1], out_hw[1], filter), resample_matrix(in_hw[0], out_hw[0], filter)
         if backend == "hip":
             th = compact_taps(mh) if in_hw[1] != out_hw[1] else (identity_taps(in_hw[1]) if first else None)
             tv = compact_taps(mv) if in_hw[0] != out_hw[0] else None
@@ -351,4 +369,94 @@ class DeviceInputPipeline:
         for s in range(S):
             inputs[("K", s)] = KK[s]
             inputs[("inv_K", s)] = KK[S + s]
+        return inputs
+
+
+DDAD_RAW_HW = (1216, 1936)                      # ddad_dataset.py:137-138
+
+
+class DDADInputPipeline:
+    """The DDAD loader's image path (datasets/ddad_dataset.py:116-167) for a whole batch: raw uint8 frames 0 and -1 and the
+    per-sample intrinsics -> the row-P dictionary.  Not the KITTI pipeline with other sizes:
+      * level 0 is Pillow's BILINEAR resize of the raw frame (:121); the loader's LANCZOS resize to that same size (:77) is
+        Pillow's copy; level s >= 1 is LANCZOS from level s-1;
+      * no ColorJitter (`do_color_aug = False`, :124): color_aug holds the bytes of color; `do_flip` is drawn and never
+        applied, so nothing is flipped;
+      * ("K", s) / ("inv_K", s) are per sample and the SAME matrix at every scale (:132-143): rows 0 and 1 of the 4x4
+        float32 matrix times width / raw width and height / raw height, the inverse `np.linalg.pinv` of that float32 matrix.
+        These B small matrices are computed on the host with numpy, exactly as the loader does (a float32 SVD is not
+        reproducible bit for bit in a kernel), and uploaded with the call's one host-to-device copy.
+    backend "hip" (the default on a GPU device; refused on the CPU): per level the horizontal and the vertical resize pass
+    and the uint8 -> fp32 conversion on the kernels of csrc/input_pipeline.hip, all frames stacked, plus one launch that
+    repeats the intrinsics over the scales; "torch": the formulation above.  Both return the same bytes."""
+
+    def __init__(self, device, height=384, width=640, raw_hw=DDAD_RAW_HW, num_scales=4, frame_idxs=(0, -1), backend=None):
+        self.device = torch.device(device)
+        self.backend = backend or ("hip" if self.device.type == "cuda" else "torch")
+        if self.backend not in ("hip", "torch"):
+            raise ValueError(f"backend {backend!r}: expected 'hip' or 'torch'")
+        if self.backend == "hip" and self.device.type != "cuda":
+            raise ValueError("backend 'hip' needs a GPU device; the CPU path is backend 'torch'")
+        self.height, self.width, self.raw_hw, self.num_scales = height, width, tuple(raw_hw), num_scales
+        self.frame_idxs = tuple(frame_idxs)
+        self.resize, prev = [], self.raw_hw
+        for s in range(num_scales):
+            hw = (height // 2 ** s, width // 2 ** s)
+            self.resize.append(LanczosResize(prev, hw, self.device, self.backend, first=(s == 0),
+                                             filter="bilinear" if s == 0 else "lanczos"))
+            prev = hw
+        self.unit = torch.full((), 255.0, device=self.device)          # see DeviceInputPipeline
+
+    def intrinsics(self, intrinsics):
+        """[B,3,3] camera matrices -> float32 [2,B,4,4]: K and inv_K of ddad_dataset.py:132-143, in numpy on the host."""
+        intr = intrinsics.cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics)
+        if intr.ndim != 3 or intr.shape[1:] != (3, 3):
+            raise ValueError(f"intrinsics: [B,3,3] camera matrices, got {intr.shape}")
+        out = np.zeros((2, len(intr), 4, 4), np.float32)
+        for b in range(len(intr)):
+            K = np.zeros((4, 4), np.float32)
+            K[:3, :3] = intr[b].copy()
+            K[3][3] = 1
+            K[0, :] *= self.width / self.raw_hw[1]
+            K[1, :] *= self.height / self.raw_hw[0]
+            out[0, b], out[1, b] = K, np.linalg.pinv(K)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, raw, intrinsics):
+        """raw: {frame id: uint8 [B,3,Hraw,Wraw]}; intrinsics: [B,3,3] (host tensor or array)."""
+        B = raw[self.frame_idxs[0]].shape[0]
+        for f in self.frame_idxs:
+            if tuple(raw[f].shape) != (B, 3) + self.raw_hw or raw[f].dtype != torch.uint8:
+                raise ValueError(f"frame {f}: expected uint8 {(B, 3) + self.raw_hw}, got {raw[f].dtype} {tuple(raw[f].shape)}")
+        kk = self.intrinsics(intrinsics)
+        if kk.shape[1] != B:
+            raise ValueError(f"{kk.shape[1]} camera matrices for a batch of {B}")
+        kk = torch.from_numpy(kk).to(self.device)                      # the call's parameter copy
+        F, S = len(self.frame_idxs), self.num_scales
+        inputs = {}
+        if self.backend == "hip":
+            from ppeadepth import ops
+            img = [raw[f].to(self.device).contiguous() for f in self.frame_idxs]
+            # no jitter: an all-zero parameter table (apply = 0, written on the device) turns the ColorJitter launch into the
+            # uint8 -> fp32 conversion of both outputs
+            params = torch.zeros(F * B, ops.JITTER_PARAM_WORDS, device=self.device, dtype=torch.int32)
+            for s in range(S):
+                img = self.resize[s](img)
+                color, aug = ops.color_jitter_u8(img, params)
+                for fi, f in enumerate(self.frame_idxs):
+                    inputs[("color", f, s)] = color[fi * B:(fi + 1) * B]
+                    inputs[("color_aug", f, s)] = aug[fi * B:(fi + 1) * B]
+            KK = ops.repeat_rows(kk.reshape(1, -1), S).reshape(S, 2, B, 4, 4)
+        else:
+            for f in self.frame_idxs:
+                img = raw[f].to(self.device)
+                for s in range(S):
+                    img = self.resize[s](img)
+                    inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
+                    inputs[("color_aug", f, s)] = inputs[("color", f, s)].clone()
+            KK = kk[None].repeat(S, 1, 1, 1, 1)
+        for s in range(S):
+            inputs[("K", s)] = KK[s, 0]
+            inputs[("inv_K", s)] = KK[s, 1]
         return inputs

@@ -718,15 +718,20 @@ def cost_volume_ring(cur, ring, state, poses, K, inv_K, bins, eps=1e-7, zero_pos
 
 
 # ---------------------------------------------------------------------------------------------
-# Validation metric (trainer.py:780-843): the per-image error protocol on the device   (csrc/eval_metrics.hip)
+# Validation metric (trainer.py:780-843, and val_ddad's, :583-623): the per-image error protocol on the device   (csrc/eval_metrics.hip)
 # ---------------------------------------------------------------------------------------------
-EVAL_MODES = {"eigen": 1, "cityscapes": 2}          # any other split name: the range test only (mode 0)
+# any other split name ("ddad" and "benchmark" among them): the 80 m range test only (mode 0); "val_ddad" is the protocol of
+# the reference's Trainer.val_ddad (evaluate.evaluate_image_ddad)
+EVAL_MODES = {"eigen": 1, "cityscapes": 2, "val_ddad": 3}
 
 
 @torch.no_grad()
 def depth_errors(pred_disp, gt, table, max_region, eval_split="eigen", median_scaling=True, scale=1.0, out=None):
     """pred_disp [B,h,w] fp32 scaled disparity; gt flat fp32 ground truth; table [B,3] int64 (offset, H_gt, W_gt) of the
     batch's images; max_region >= the largest cropped rectangle of the batch (evaluate.region_size).
+    eval_split "eigen" / "cityscapes": `Trainer.val`'s protocol with that crop; "val_ddad": mode 3, `Trainer.val_ddad`'s
+    (trainer.py:583-623: the DEPTH 1 / disparity is resized, range test 1e-3 < gt < 200, clamp [1e-3, 200], whole map); any
+    other name, "ddad" included: `val`'s 80 m range test without a crop.
     -> (errors [B,7] fp64, ratio [B] fp32, count [B] int32); `out`: a contiguous [B,7] fp64 tensor to write the errors to."""
     if pred_disp.dim() != 3:
         raise _abi.PpeaKernelError(f"expected a [B,h,w] disparity batch, got {tuple(pred_disp.shape)}")

@@ -54,6 +54,20 @@ class MonodepthOptions:
         return self.options
 
 
+def apply_ddad(opt):
+    """What `--ddad` means (reference trainer.py:98-103): dataset, split and eval_split "ddad" at 384x640.  The reference
+    builds its model inside the trainer, after this rewrite; here the caller builds the model, so a caller that sizes anything
+    from `opt.height` / `opt.width` applies this to the parsed options BEFORE building the model.  `Trainer.__init__` applies
+    it too; applying it twice changes nothing, and without `--ddad` it changes nothing."""
+    if getattr(opt, "ddad", False):
+        opt.dataset = "ddad"
+        opt.height = 384
+        opt.width = 640
+        opt.split = "ddad"
+        opt.eval_split = "ddad"
+    return opt
+
+
 def default_options(**overrides):
     """Stage-1 defaults of the README training command (`--adapter --use_checkpoint`) with
     `--weights_init scratch` (no network in this environment)."""

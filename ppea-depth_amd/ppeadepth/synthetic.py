@@ -258,3 +258,43 @@ class SynthEigenDataset(torch.utils.data.Dataset):
 
 def collate(items):
     return {k: torch.stack([it[k] for it in items]) for k in items[0]}
+
+
+# ---------------------------------------------------------------------------------------------
+# synthetic validation set in the DDAD loader's item format (datasets/ddad_dataset.py:116-167, is_train=False)
+# ---------------------------------------------------------------------------------------------
+def make_ddad_val(n=4, raw_hw=(1216, 1936), seed=7, valid=0.01, tz=0.4):
+    """-> n items {"raw": {0, -1: uint8 [3,Hraw,Wraw]}, "intrinsics": float32 [3,3], "depth": float32 [Hraw,Wraw]}: what the
+    DDAD loader reads per sample before its image path (`input_pipeline.DDADInputPipeline`), frame -1 rendered from frame 0
+    with the camera moved back `tz` metres, the camera matrix of each sample its own, and a projected-LiDAR-like depth map
+    with about `valid` of its pixels non-zero.  The road reaches from a few metres to the horizon and the region above it
+    lies at 150 .. 250 m, so the map holds values in each class `val_ddad` tells apart: (1e-3, 80), [80, 200) and >= 200."""
+    Hr, Wr = raw_hw
+    g = torch.Generator(device="cpu")
+    g.manual_seed(seed)
+    items = []
+    for i in range(n):
+        tex, depth = _scene(i, Hr, Wr, seed)
+        ys = torch.linspace(0, 1, Hr)[:, None].expand(Hr, Wr)
+        blobs = ((depth / torch.where(ys > 0.37, (1.6 / (0.04 + 0.9 * (ys - 0.35).clamp_min(0.0))).clamp(max=70.0),
+                                      torch.full_like(depth, 70.0)) - 0.6) / 0.5).clamp(0, 1)
+        depth = torch.where(ys > 0.37, depth * 2.0, 150.0 + 100.0 * blobs)
+        f = Wr * (1.10 + 0.05 * float(torch.rand((), generator=g)))            # DDAD's front camera: fx ~ 1.13 x width
+        intr = torch.tensor([[f, 0, Wr * (0.5 + 0.01 * float(torch.rand((), generator=g)))],
+                             [0, f, Hr * (0.5 + 0.01 * float(torch.rand((), generator=g)))],
+                             [0, 0, 1]], dtype=torch.float32)
+        K = torch.eye(4)
+        K[:3, :3] = intr
+        prev = _render_neighbour(tex, depth, K, torch.linalg.inv(K), -tz)
+        keep = torch.rand(Hr, Wr, generator=g) < valid
+        to_u8 = lambda t: (t.clamp(0, 1) * 255).round().to(torch.uint8)      # noqa: E731
+        items.append({"raw": {0: to_u8(tex), -1: to_u8(prev)}, "intrinsics": intr.numpy(),
+                      "depth": (depth * keep).numpy().astype(np.float32)})
+    return items
+
+
+def collate_ddad(items):
+    """-> (raw {f: uint8 [B,3,Hraw,Wraw]}, intrinsics float32 [B,3,3], depth float32 tensor [B,Hraw,Wraw])."""
+    raw = {f: torch.stack([it["raw"][f] for it in items]) for f in items[0]["raw"]}
+    return (raw, np.stack([it["intrinsics"] for it in items]),
+            torch.from_numpy(np.stack([it["depth"] for it in items])))

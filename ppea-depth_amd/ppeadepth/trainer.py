@@ -92,6 +92,10 @@ class _NullAccelerator:
 class Trainer:
     def __init__(self, options, model, device, acc=None, amp_dtype=None):
         self.opt = options
+        # trainer.py:98-103, before anything is sized from them; validation is then `val_ddad` (trainer.py:372-394).  The
+        # model was built by the caller: under `--ddad` from options that `options.apply_ddad` had already rewritten.
+        from .options import apply_ddad
+        apply_ddad(self.opt)
         assert self.opt.height % 32 == 0 and self.opt.width % 32 == 0
         assert self.opt.frame_ids[0] == 0 and len(self.opt.frame_ids) > 1
         self.device = torch.device(device)
@@ -177,14 +181,18 @@ class Trainer:
 
     # ---- trainer.py:653-857 -----------------------------------------------------------------------
     @torch.no_grad()
-    def predict_disps(self, data, mono=True, predictor=None):
+    def predict_disps(self, data, mono=True, predictor=None, mono_max_depth=None):
         """Inference path of `val` for one batch (trainer.py:676-752): poses of the lookup frames `matching_ids[1:]` from
         the pose network, chained 0 -> -1 -> -2 ... and 0 -> +1 (eval_depth_ori.py:224-253; upstream's `val` itself stops at
         frame -1), written to `data[("relative_pose", f)]`; cost volume + multi-frame encoder + decoder, optionally the
         single-frame teacher; model in eval mode.
         -> (scaled multi-frame disparity [B,H,W], scaled teacher disparity or None), as `disp_to_depth(., 1e-3, 80)`.
-        predictor: an `inference.DepthPredictor` of this model -- the same outputs from its fused schedule."""
+        predictor: an `inference.DepthPredictor` of this model -- the same outputs from its fused schedule.
+        mono_max_depth: the far end the teacher's disparity is scaled with; `val` uses `opt.max_depth` (trainer.py:757, the
+        default), `val_ddad` 80 like the student's (trainer.py:593)."""
         from .layers import pose_chain
+        if mono_max_depth is None:
+            mono_max_depth = self.opt.max_depth
         model = self._module()
         dev = self.device
         ids = [int(f) for f in model.matching_ids[1:]]
@@ -200,7 +208,7 @@ class Trainer:
             pred, _ = disp_to_depth(r["disp"], MIN_VAL_EVAL, 80)
             pred_mono = None
             if mono:
-                pred_mono, _ = disp_to_depth(predictor.predict_mono(data[("color", 0, 0)]), MIN_VAL_EVAL, self.opt.max_depth)
+                pred_mono, _ = disp_to_depth(predictor.predict_mono(data[("color", 0, 0)]), MIN_VAL_EVAL, mono_max_depth)
                 pred_mono = pred_mono[:, 0]
             return pred[:, 0], pred_mono
         ctx = torch.autocast("cuda", dtype=self.amp_dtype) if self.amp_dtype is not None else contextlib.nullcontext()
@@ -230,7 +238,7 @@ class Trainer:
             pred_mono = None
             if mono:
                 dm = model.mono_depth(model.mono_encoder(color[0]))[("disp", 0)].float()
-                pred_mono, _ = disp_to_depth(dm, MIN_VAL_EVAL, self.opt.max_depth)
+                pred_mono, _ = disp_to_depth(dm, MIN_VAL_EVAL, mono_max_depth)
                 pred_mono = pred_mono[:, 0]
         return pred[:, 0], pred_mono
 
@@ -290,6 +298,70 @@ class Trainer:
         if mono_flag:
             return mean_errors, evaluate.evaluate_disps(np.concatenate(disps_mono), gt_depths, eval_split, True)
         return mean_errors
+
+    # ---- trainer.py:490-650 -----------------------------------------------------------------------
+    def val_ddad(self, batches, gt_depths=None, hard_test_mono=False, median_scaling=None, predictor=None, metrics="host"):
+        """`Trainer.val_ddad` (trainer.py:490-650), what the reference's `run_epoch` calls instead of `val` under `--ddad`:
+        the protocol of `evaluate.evaluate_image_ddad` over an iterable of row-P batches.  The ground truth is
+        `data["depth"]` [B,H,W] of each batch (ddad_dataset.py:165) unless `gt_depths` is given: a list of maps or, for
+        metrics="device", a `DeviceGroundTruth`, as for `val`.  Both networks' disparities are scaled with (1e-3, 80)
+        (trainer.py:583, :593).  Returns what `val` returns.
+        metrics="device": every batch is scored where it was predicted (a host `data["depth"]` costs one upload per batch, a
+        device tensor none), the mean is taken on the device and one copy brings the result back."""
+        import numpy as np
+        from . import evaluate
+        if metrics not in ("host", "device"):
+            raise ValueError(f"metrics={metrics!r}: 'host' or 'device'")
+        if metrics == "host" and isinstance(gt_depths, evaluate.DeviceGroundTruth):
+            raise ValueError("metrics='host' scores numpy maps: pass gt_depths as a list of [H,W] maps (or None for "
+                             "data['depth']), or use metrics='device' with a DeviceGroundTruth")
+        model = self._module()
+        was_training = model.training
+        model.eval()
+        mono_flag = (not self.freeze_tp) or hard_test_mono
+        # trainer.py:614-618: the student's options; the teacher is always median-scaled, without the factor (:630-632)
+        scale = float(getattr(self.opt, "pred_depth_scale_factor", 1.0))
+        if median_scaling is None:
+            median_scaling = not getattr(self.opt, "disable_median_scaling", False)
+        device_metrics = metrics == "device"
+        whole = gt_depths
+        if device_metrics and whole is not None and not isinstance(whole, evaluate.DeviceGroundTruth):
+            whole = evaluate.DeviceGroundTruth(whole, self.device)
+        errors, errors_mono, first = [], [], 0
+        try:
+            for data in batches:
+                d, dm = self.predict_disps(data, mono_flag, predictor, mono_max_depth=80)
+                B = d.shape[0]
+                if device_metrics:
+                    gt, at = (whole, first) if whole is not None else (evaluate.DeviceGroundTruth.from_batch(data["depth"],
+                                                                                                             self.device), 0)
+                    errors.append(gt.score(d.float().contiguous(), at, "val_ddad", median_scaling, scale)[0])
+                    if mono_flag:
+                        errors_mono.append(gt.score(dm.float().contiguous(), at, "val_ddad", True, 1.0)[0])
+                else:
+                    if whole is not None:
+                        gts = whole[first:first + B]
+                    else:
+                        gts = data["depth"]
+                        gts = gts.cpu().numpy() if torch.is_tensor(gts) else np.asarray(gts)
+                    if len(gts) != B:
+                        raise ValueError(f"{B} predictions for {len(gts)} ground-truth maps")
+                    d = d.float().cpu().numpy()
+                    errors += [evaluate.evaluate_image_ddad(d[i], gts[i], median_scaling, scale)[0] for i in range(B)]
+                    if mono_flag:
+                        dm = dm.float().cpu().numpy()
+                        errors_mono += [evaluate.evaluate_image_ddad(dm[i], gts[i], True)[0] for i in range(B)]
+                first += B
+        finally:
+            model.train(was_training)
+        if first == 0 or (whole is not None and first != len(whole)):
+            raise ValueError(f"{first} predictions for a split of {0 if whole is None else len(whole)} ground-truth maps")
+        if device_metrics:
+            nets = [errors, errors_mono] if mono_flag else [errors]
+            means = torch.stack([ops.depth_errors_mean(torch.cat(e)) for e in nets]).cpu().numpy()
+            return (means[0], means[1]) if mono_flag else means[0]
+        mean_errors = np.array(errors).mean(0)
+        return (mean_errors, np.array(errors_mono).mean(0)) if mono_flag else mean_errors
 
     # ---- trainer.py:859-869 -----------------------------------------------------------------------
     def compute_matching_mask(self, outputs):

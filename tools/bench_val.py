@@ -10,6 +10,12 @@ prediction loop alone, and the scoring alone on kept disparities.  The select ke
 profiler and stands beside its streaming floor (bytes it reads / 6.3 TB/s).  Prints ONE JSON line.  On a tree whose
 `Trainer.val` has no `metrics` keyword only the host numbers are reported.  Run it three times and pass the earlier outputs
 with --repeat-of: the last run then records the run-to-run spread and the acceptance (slowest device run < fastest host run).
+
+    python tools/bench_val.py --case ddad [--reps 3] [--out profiles/val_bench_ddad.json]
+
+The DDAD case: `Trainer.val_ddad` over 24 images at 384x640 (B = 12, frames 0 and -1) whose 1216x1936 ground truth with 1 %
+valid pixels arrives inside each batch, host metric against `metrics="device"`, timed the same way.  A report, not a gate:
+the only comparison is the host-scored `val_ddad` of the same commit.
 """
 import argparse
 import contextlib
@@ -65,12 +71,89 @@ def kernel_us(fn, pattern):
     return sum(e.time_range.elapsed_us() for e in ev if pattern in e.name), len(ev)
 
 
+DDAD = dict(n=24, hw=(384, 640), gt=(1216, 1936), keep=0.01)
+
+
+def ddad_case(args):
+    from ppeadepth import evaluate, networks, options, synthetic
+    from ppeadepth.inference import DepthPredictor
+    from ppeadepth.trainer import Trainer
+    dev = torch.device("cuda:0")
+    (H, W), n, (gh, gw) = DDAD["hw"], DDAD["n"], DDAD["gt"]
+    opt = options.default_options(height=H, width=W, batch_size=B, use_checkpoint=False, frame_ids=[0, -1])
+    torch.manual_seed(0)
+    model = networks.RepDepth(opt)
+    synthetic.fill_state_dict(model, conditioned=True)
+    model.to(dev).eval()
+    tr = Trainer(opt, model, dev, amp_dtype=torch.bfloat16)
+    pred = DepthPredictor(model, opt).capture(B)
+    g = torch.Generator().manual_seed(11)
+    y = torch.linspace(0, 1, gh)[:, None]
+    batches, depths = [], []
+    for j in range(n // B):
+        data = {k: v.to(dev) for k, v in synthetic.make_rendered_inputs(B, H, W, seed=7 + j, frame_ids=(0, -1)).items()}
+        depth = (6 + 230 * (1 - y) ** 2) * (1 + 0.1 * torch.randn(B, gh, gw, generator=g)).clamp(0.5, 1.5)
+        depths.append((depth * (torch.rand(B, gh, gw, generator=g) < DDAD["keep"])).float())
+        batches.append(data)
+    on_host = lambda: [dict(b, depth=d) for b, d in zip(batches, depths)]                  # noqa: E731
+    depths_dev = [d.to(dev) for d in depths]
+    on_device = lambda: [dict(b, depth=d) for b, d in zip(batches, depths_dev)]            # noqa: E731
+
+    def predict_only():
+        for data in on_host():
+            tr.predict_disps(data, True, pred, mono_max_depth=80)
+
+    disps = [tr.predict_disps(data, True, pred, mono_max_depth=80) for data in on_host()]
+    host_disps = [np.concatenate([d[k].float().cpu().numpy() for d in disps]) for k in (0, 1)]
+    gts = np.concatenate([d.numpy() for d in depths])
+    dgs = [evaluate.DeviceGroundTruth.from_batch(d, dev) for d in depths_dev]
+
+    def host_scoring():
+        evaluate.evaluate_disps_ddad(host_disps[0], gts, True, 1.0)
+        evaluate.evaluate_disps_ddad(host_disps[1], gts, True)
+
+    def device_scoring():
+        from ppeadepth import ops
+        errors = [[dg.score(d[k].float().contiguous(), 0, "val_ddad")[0] for dg, d in zip(dgs, disps)] for k in (0, 1)]
+        return torch.stack([ops.depth_errors_mean(torch.cat(e)) for e in errors]).cpu()
+
+    cell = {"images": n, "batch": B, "frames_hw": [H, W], "ground_truth_hw": [gh, gw], "valid_fraction": DDAD["keep"],
+            "val_ms": {"host": wall(lambda: tr.val_ddad(on_host(), predictor=pred), args.reps),
+                       "device": wall(lambda: tr.val_ddad(on_device(), predictor=pred, metrics="device"), args.reps),
+                       "device_with_upload": wall(lambda: tr.val_ddad(on_host(), predictor=pred, metrics="device"), args.reps)},
+            "predict_ms": wall(predict_only, args.reps),
+            "scoring_ms": {"host": wall(host_scoring, args.reps), "device": wall(device_scoring, args.reps)}}
+    one = disps[0][0].float().contiguous()
+    us, events = kernel_us(lambda: dgs[0].score(one, 0, "val_ddad"), "eval_select_pass")
+    gather, _ = kernel_us(lambda: dgs[0].score(one, 0, "val_ddad"), "eval_gather")
+    total, _ = kernel_us(lambda: dgs[0].score(one, 0, "val_ddad"), "eval_")
+    moved = 10 * 4 * gh * gw                  # gather: gt read, 2 workspaces written; 4 passes x 2 read; partial: 2 read
+    cell["kernels"] = {"gather_us_per_image": round(gather / B, 3), "select_us_per_image": round(us / B, 3),
+                       "all_scoring_kernels_us_per_image": round(total / B, 3), "bytes_moved_per_image": moved,
+                       "floor_us_per_image_at_6.3TBps": round(moved / 6.3e12 * 1e6, 3), "device_events_per_batch": events}
+    h = tr.val_ddad(on_host(), predictor=pred)
+    d = tr.val_ddad(on_device(), predictor=pred, metrics="device")
+    cell["max_rel_difference_of_the_7_errors"] = float(max(np.max(np.abs(a - b) / np.abs(b)) for a, b in zip(d, h)))
+    cell["metric_share_of_host_val"] = round(1 - cell["predict_ms"] / cell["val_ms"]["host"], 4)
+    res = {"metric": "Trainer.val_ddad wall ms (both networks), bf16 DepthPredictor graph replay at B=12, median of reps; "
+                     "the only comparison is the host-scored val_ddad of the same commit",
+           "reps": args.reps, "device": torch.cuda.get_device_name(0), "cells": {"val_ddad": cell},
+           "command": "python tools/bench_val.py --case ddad --reps %d" % args.reps}
+    line = json.dumps(res)
+    with open(args.out or os.path.join(ROOT, "profiles", "val_bench_ddad.json"), "w") as f:
+        f.write(line + "\n")
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--repeat-of", nargs="*", default=[])
+    ap.add_argument("--case", choices=["splits", "ddad"], default="splits")
     args = ap.parse_args()
+    if args.case == "ddad":
+        return ddad_case(args)
     from ppeadepth import evaluate, networks, options, synthetic
     from ppeadepth.inference import DepthPredictor
     from ppeadepth.trainer import Trainer
