@@ -21,6 +21,8 @@ MI355X design notes
     multi-tensor ops, after the forward pass (`DeferredStats.flush`), which is also when the
     reference's recompute happens.
 """
+import os
+
 import torch
 import torch.distributed as dist
 import torch.nn as nn
@@ -77,6 +79,25 @@ _ACTIVE_DEFERRED = None     # set by RepDepth.forward for the duration of a trai
 def set_deferred(d):
     global _ACTIVE_DEFERRED
     _ACTIVE_DEFERRED = d
+
+
+def book(bn, mean=None, invstd=None, count=0.0, n=1):
+    """Bookkeeping of `n` training-mode forward calls of `bn`, the only reader of the step's deferred book:
+    num_batches_tracked (at once, or through the book's multi-tensor update) and, given the batch statistics of a
+    grad-enabled call inside a segment the reference checkpoints, the replayed second running-statistics update.
+    Without statistics it only counts."""
+    if _ACTIVE_DEFERRED is None:
+        bn.num_batches_tracked += n
+        return
+    _ACTIVE_DEFERRED.count(bn, n)
+    if mean is not None and bn.replay_update and torch.is_grad_enabled():
+        _ACTIVE_DEFERRED.add(bn, mean, invstd, count)
+
+
+def _book_stats(bns, st, count):
+    """book() for the BatchNorms of one fused launch (st = mean1 | invstd1 | mean2 | invstd2)."""
+    for k, bn in enumerate(bns):
+        book(bn, st[2 * k], st[2 * k + 1], count)
 
 
 def _collectives_on():
@@ -150,7 +171,7 @@ def _global_stats(bn, z, sums=None):
     return mean, invstd, float(cnt * world), (group,)
 
 
-PACK_PAIR = __import__("os").environ.get("PPEA_BN_PAIR", "1") == "1"
+PACK_PAIR = os.environ.get("PPEA_BN_PAIR", "1") == "1"
 
 
 def _global_stats_pair(bn1, z1, bn2, z2, sums=None):
@@ -176,7 +197,7 @@ def _global_stats_pair(bn1, z1, bn2, z2, sums=None):
     return out[0], out[1]
 
 
-SYNC_FUSED = __import__("os").environ.get("PPEA_SYNC_FUSED", "1") == "1"     # 0: the round-2 multi-rank path (A/B only)
+SYNC_FUSED = os.environ.get("PPEA_SYNC_FUSED", "1") == "1"     # 0: the round-2 multi-rank path (A/B only)
 
 
 def _sync_path_ok(z, bns):
@@ -189,18 +210,19 @@ def _sync_path_ok(z, bns):
                 and bn.running_mean.dtype == torch.float32 for bn in bns) and ops.sync_bn_supported(z))
 
 
-def _book_sync(bns, st, z):
-    """num_batches_tracked / checkpoint-replay bookkeeping of a sync_bn_act call (st = mean1 | invstd1 | mean2 | invstd2)."""
-    group = getattr(bns[0][1], "group", None)
+def _channel_path_ok(z, bns):
+    """One rank (no SyncBN exchange to make), every BN in training mode with the same eps / momentum and fp32 running
+    statistics, and a shape the one-launch channel kernels serve."""
     from . import ops
-    cnt = float(z.numel() // z.shape[1] * ops.sync_world(group))
-    for k, (_, bn) in enumerate(bns):
-        if _ACTIVE_DEFERRED is None:
-            bn.num_batches_tracked += 1
-        else:
-            _ACTIVE_DEFERRED.count(bn)
-            if bn.replay_update and torch.is_grad_enabled():
-                _ACTIVE_DEFERRED.add(bn, st[2 * k], st[2 * k + 1], cnt)
+    return (ops.bn_channel_ok(z) and all(bn.training for bn in bns) and not any(bn.sync and _collectives_on() for bn in bns)
+            and all(bn.eps == bns[0].eps and bn.momentum == bns[0].momentum for bn in bns)
+            and bns[0].running_mean.dtype == torch.float32)
+
+
+def _global_count(z, group):
+    """Elements per channel of the global batch, as a float."""
+    from . import ops
+    return float(z.numel() // z.shape[1] * ops.sync_world(group))
 
 
 def assign_groups(model, any_backend=False):
@@ -230,55 +252,35 @@ def fused_bn_act(z1, bn1, z2=None, bn2=None, act=0, mask=None, r1=None, r2=None,
     one-launch kernels serve the shape, the gradient of that use is added inside this BN's backward launch."""
     from . import ops
     assert bn1.training, "fused_bn_act is the training-mode path; eval goes through BatchNorm2d.forward"
-    bns = [(z1, bn1)] + ([(z2, bn2)] if z2 is not None else [])
-    if _sync_path_ok(z1, [bn for _, bn in bns]):
-        # several ranks: [statistics launch] -> all-gather -> combine + apply launch (same fused neighbours as below)
-        want_skip = bool(skip and torch.is_grad_enabled() and z1.requires_grad)
-        want_dup = bool(want_skip and BN_DUP and r1 is None and r2 is None and ops.bn_channel_ok(z1))
-        outs = ops.sync_bn_act(z1, bn1, z2, bn2, mask=mask, r1=r1, r2=r2, r2_scale=r2_scale, act=act,
-                               group=getattr(bn1, "group", None), sums=sums, skip=want_skip, dup=want_dup)
-        _book_sync(bns, outs[1], z1)
-        if want_dup:
-            outs[0]._second_use = outs[-1]
-        return (outs[0], outs[2] if want_skip else z1) if skip else outs[0]
-    # small channels on one rank: statistics, running-statistics update and apply in ONE launch (backward likewise)
-    if (ops.bn_channel_ok(z1) and all(bn.training for _, bn in bns) and not any(bn.sync and _collectives_on() for _, bn in bns)
-            and (bn2 is None or (bn2.eps == bn1.eps and bn2.momentum == bn1.momentum))
-            and bn1.running_mean.dtype == torch.float32):
-        z1_skip = z1
-        if skip and torch.is_grad_enabled() and z1.requires_grad:
-            if BN_DUP and r1 is None and r2 is None:
-                y, st, z1_skip, y_b = ops.bn_act_channel(z1, bn1, z2, bn2, mask=mask, act=act, skip=True, dup=True)
-                y._second_use = y_b                      # see second_use()
-            else:
-                y, st, z1_skip = ops.bn_act_channel(z1, bn1, z2, bn2, mask=mask, r1=r1, r2=r2, r2_scale=r2_scale, act=act,
-                                                    skip=True)
+    zs, bns = [z1] + ([z2] if z2 is not None else []), [bn1] + ([bn2] if z2 is not None else [])
+    want_skip = bool(skip and torch.is_grad_enabled() and z1.requires_grad)
+    want_dup = bool(want_skip and BN_DUP and r1 is None and r2 is None and ops.bn_channel_ok(z1))
+    sync = _sync_path_ok(z1, bns)
+    if sync or _channel_path_ok(z1, bns):
+        kw = dict(mask=mask, r1=r1, r2=r2, r2_scale=r2_scale, act=act, skip=want_skip, dup=want_dup)
+        if sync:
+            # several ranks: [statistics launch] -> all-gather -> combine + apply launch (same fused neighbours as below)
+            group = getattr(bn1, "group", None)
+            outs = ops.sync_bn_act(z1, bn1, z2, bn2, group=group, sums=sums, **kw)
+            cnt = _global_count(z1, group)
         else:
-            y, st = ops.bn_act_channel(z1, bn1, z2, bn2, mask=mask, r1=r1, r2=r2, r2_scale=r2_scale, act=act,
-                                       sums=sums if (z2 is None and torch.is_tensor(sums)) else None)
-        cnt = float(z1.numel() // z1.shape[1])
-        for k, (_, bn) in enumerate(bns):
-            if _ACTIVE_DEFERRED is None:
-                bn.num_batches_tracked += 1
-            else:
-                _ACTIVE_DEFERRED.count(bn)
-                if bn.replay_update and torch.is_grad_enabled():
-                    _ACTIVE_DEFERRED.add(bn, st[2 * k], st[2 * k + 1], cnt)
-        return (y, z1_skip) if skip else y
+            # small channels on one rank: statistics, running-statistics update and apply in ONE launch (backward likewise)
+            outs = ops.bn_act_channel(z1, bn1, z2, bn2, **kw,
+                                      sums=sums if (not want_skip and z2 is None and torch.is_tensor(sums)) else None)
+            cnt = float(z1.numel() // z1.shape[1])
+        _book_stats(bns, outs[1], cnt)
+        if want_dup:
+            outs[0]._second_use = outs[-1]               # see second_use()
+        return (outs[0], outs[2] if want_skip else z1) if skip else outs[0]
     stats = []
     count, group = None, None
     pre = None
     if z2 is not None and bn1.training and bn2.training:
         pre = list(_global_stats_pair(bn1, z1, bn2, z2, sums if isinstance(sums, tuple) else None))
-    for z, bn in bns:
+    for z, bn in zip(zs, bns):
         if bn.training:
             mean, invstd, count, group = pre.pop(0) if pre is not None else _global_stats(bn, z, sums if (z is z1 and not isinstance(sums, tuple)) else None)
-            if _ACTIVE_DEFERRED is None:
-                bn.num_batches_tracked += 1
-            else:
-                _ACTIVE_DEFERRED.count(bn)
-                if bn.replay_update and torch.is_grad_enabled():
-                    _ACTIVE_DEFERRED.add(bn, mean, invstd, count)
+            book(bn, mean, invstd, count)
         else:
             mean = bn.running_mean.float()
             invstd = torch.rsqrt(bn.running_var.float() + bn.eps)
@@ -290,11 +292,11 @@ def fused_bn_act(z1, bn1, z2=None, bn2=None, act=0, mask=None, r1=None, r2=None,
     return (y, z1) if skip else y
 
 
-BN_CHAIN = __import__("os").environ.get("PPEA_BN_CHAIN", "1") == "1"
+BN_CHAIN = os.environ.get("PPEA_BN_CHAIN", "1") == "1"
 # A block's first BatchNorm output feeds its first 1x1 conv AND its adapter: hand the adapter an alias of it whose gradient
 # arrives separately at the BatchNorm's backward launch, which adds the two (bit-identical to autograd's own add kernel,
 # one launch fewer on the dependent chain per block and network)
-BN_DUP = __import__("os").environ.get("PPEA_BN_DUP", "1") == "1"
+BN_DUP = os.environ.get("PPEA_BN_DUP", "1") == "1"
 
 
 def second_use(y):
@@ -308,38 +310,29 @@ def fused_bn_act_next(z, bnA, bnB, mask=None, r1=None, r2=None, r2_scale=1.0, su
     served by the one-launch channel kernels (the caller then runs the two BatchNorms separately).  Same numbers, running
     statistics and bookkeeping as fused_bn_act(z, bnA, ...) followed by fused_bn_act(y, bnB, skip=True)."""
     from . import ops
-    if (BN_CHAIN and ops.bn_channel_ok(z) and bnA.num_features == bnB.num_features and _sync_path_ok(z, [bnA, bnB])):
+    if not (BN_CHAIN and ops.bn_channel_ok(z) and bnA.num_features == bnB.num_features):
+        return None
+    if _sync_path_ok(z, [bnA, bnB]):
         # several ranks: stats(z) -> gather -> [apply A + local statistics of y] -> gather -> apply B: the second
         # BatchNorm needs no statistics launch, and its backward adds the residual use's gradient of y in its apply launch
         group = getattr(bnA, "group", None)
         y, stA, tab = ops.sync_bn_act(z, bnA, mask=mask, r1=r1, r2=r2, r2_scale=r2_scale, group=group, emit=True, sums=sums)
-        _book_sync([(z, bnA)], stA, z)
+        book(bnA, stA[0], stA[1], _global_count(z, group))
         want_skip = bool(torch.is_grad_enabled() and y.requires_grad)
-        outs = ops.sync_bn_act(y, bnB, group=group, table=tab, skip=want_skip, dup=bool(want_skip and BN_DUP))
-        _book_sync([(y, bnB)], outs[1], y)
-        if want_skip and BN_DUP:
+        want_dup = bool(want_skip and BN_DUP)
+        outs = ops.sync_bn_act(y, bnB, group=group, table=tab, skip=want_skip, dup=want_dup)
+        book(bnB, outs[1][0], outs[1][1], _global_count(y, group))
+        if want_dup:
             outs[0]._second_use = outs[-1]
         return (outs[2] if want_skip else y), outs[0]
-    if not (BN_CHAIN and ops.bn_channel_ok(z) and bnA.training and bnB.training
-            and not ((bnA.sync or bnB.sync) and _collectives_on())
-            and bnA.eps == bnB.eps and bnA.momentum == bnB.momentum
-            and bnA.running_mean.dtype == torch.float32 and bnB.running_mean.dtype == torch.float32
-            and bnA.num_features == bnB.num_features):
+    if not (_channel_path_ok(z, [bnA, bnB]) and bnB.running_mean.dtype == torch.float32):
         return None
-    if BN_DUP and torch.is_grad_enabled() and z.requires_grad:
-        y, y2, st, y2_b = ops.bn_act_channel_next(z, bnA, bnB, mask=mask, r1=r1, r2=r2, r2_scale=r2_scale, dup=True)
-        y2._second_use = y2_b
-    else:
-        y, y2, st = ops.bn_act_channel_next(z, bnA, bnB, mask=mask, r1=r1, r2=r2, r2_scale=r2_scale)
-    cnt = float(z.numel() // z.shape[1])
-    for k, bn in enumerate((bnA, bnB)):
-        if _ACTIVE_DEFERRED is None:
-            bn.num_batches_tracked += 1
-        else:
-            _ACTIVE_DEFERRED.count(bn)
-            if bn.replay_update and torch.is_grad_enabled():
-                _ACTIVE_DEFERRED.add(bn, st[2 * k], st[2 * k + 1], cnt)
-    return y, y2
+    want_dup = bool(BN_DUP and torch.is_grad_enabled() and z.requires_grad)
+    outs = ops.bn_act_channel_next(z, bnA, bnB, mask=mask, r1=r1, r2=r2, r2_scale=r2_scale, dup=want_dup)
+    if want_dup:
+        outs[1]._second_use = outs[-1]
+    _book_stats((bnA, bnB), outs[2], float(z.numel() // z.shape[1]))
+    return outs[0], outs[1]
 
 
 class BatchNorm2d(nn.Module):
@@ -372,10 +365,5 @@ class BatchNorm2d(nn.Module):
         else:
             out, mean, invstd = torch.native_batch_norm(x, self.weight, self.bias, self.running_mean,
                                                         self.running_var, True, self.momentum, self.eps)
-        if _ACTIVE_DEFERRED is None:
-            self.num_batches_tracked += 1
-        else:
-            _ACTIVE_DEFERRED.count(self)
-            if self.replay_update and torch.is_grad_enabled():
-                _ACTIVE_DEFERRED.add(self, mean.detach(), invstd.detach(), float(count))
+        book(self, mean.detach(), invstd.detach(), float(count))
         return out

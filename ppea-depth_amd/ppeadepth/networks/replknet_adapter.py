@@ -499,13 +499,7 @@ class RepLKBlock(nn.Module):
         if sums is None:                                       # this 1x1 conv is not served by the MFMA GEMM: unfused
             return lk.forward_act(fused_bn_act(z1, bn, act=ops.ACT_RELU), ops.ACT_RELU)
         y_big, y_small, st = ops.dwconv_lk_bn(z1, sums, bn, big.weight, small.weight)
-        cnt = float(z1.numel() // z1.shape[1])
-        if bnm._ACTIVE_DEFERRED is None:
-            bn.num_batches_tracked += 1
-        else:
-            bnm._ACTIVE_DEFERRED.count(bn)
-            if bn.replay_update and torch.is_grad_enabled():
-                bnm._ACTIVE_DEFERRED.add(bn, st[0], st[1], cnt)
+        bnm.book(bn, st[0], st[1], float(z1.numel() // z1.shape[1]))
         return fused_bn_act(y_big, lk.lkb_origin.bn, y_small, lk.small_conv.bn, act=ops.ACT_RELU)
 
     def forward(self, x, pre_out=None, next_bn=None):

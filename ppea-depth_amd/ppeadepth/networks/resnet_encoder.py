@@ -8,6 +8,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..batchnorm import book
 
 
 CHANNELS_LAST = True
@@ -69,12 +70,7 @@ class GroupBN(nn.BatchNorm2d):
 
 def _count_batches(bn, n):
     """num_batches_tracked += n, through the step's deferred multi-tensor update when one is active."""
-    from .. import batchnorm
-    d = batchnorm._ACTIVE_DEFERRED
-    if d is None:
-        bn.num_batches_tracked += n
-    else:
-        d.count(bn, n)
+    book(bn, n=n)
 
 
 def replay_updates(recorded):

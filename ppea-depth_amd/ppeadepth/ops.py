@@ -3,12 +3,16 @@ forward/backward below is one (or two) kernel launches on the current HIP stream
 
 Reference call sites are cited per op (paths relative to /root/reference/ppeadepth/).
 """
+import ctypes as _ct
+import os
 import weakref
 
 import torch
+import torch.distributed as dist
 
 from . import _abi
 from ._abi import PpeaKernelError, call, ptr, stream_ptr, try_call
+from .dist import log_collective
 
 _F32 = torch.float32
 _BF16 = torch.bfloat16
@@ -221,20 +225,15 @@ class _DwConvLKBn(torch.autograd.Function):
                                         ptr(dt), N, C, H, W, K, 5, stream_ptr()))
         # BatchNorm + ReLU backward on the saved pre-BN tensor (as _BnActChannel / _BnAct would)
         HW = H * W
-        stats = _stats_array((st[0], st[1], g, b, None, None, None, None))
-        sums = torch.empty(3, C, device=z.device, dtype=_F32)
+        stats = _ptr_array((st[0], st[1], g, b, None, None, None, None))
         dz = torch.empty_like(z)
         sfx = _suffix(z)
         if bn_channel_ok(z):
+            sums = torch.empty(3, C, device=z.device, dtype=_F32)
             call(f"ppea_bn_bwd_channel_{sfx}", ptr(dt), ptr(z), None, stats, None, 1.0 / float(N * HW), None, ptr(dz), None,
                  ptr(sums), ACT_RELU, N, C, HW, stream_ptr())
         else:
-            if not try_call(f"ppea_bn_bwd_reduce_final_{sfx}", ptr(dt), ptr(z), None, stats, None, ptr(sums), ACT_RELU, N, C,
-                            HW, stream_ptr()):
-                partial = torch.empty(C * N * 3, device=z.device, dtype=_F32)
-                call(f"ppea_bn_bwd_reduce_{sfx}", ptr(dt), ptr(z), None, stats, None, ptr(partial), ACT_RELU, N, C, HW,
-                     stream_ptr())
-                call("ppea_bn_bwd_finalize_f32", ptr(partial), N, C, ptr(sums), stream_ptr())
+            sums, _, _ = _bn_bwd_sums(dt, z, None, stats, None, ACT_RELU)
             call(f"ppea_bn_bwd_apply_{sfx}", ptr(dt), ptr(z), None, stats, None, ptr(sums), 1.0 / float(N * HW), ptr(dz), None,
                  ACT_RELU, N, C, HW, stream_ptr())
         dg = sums[1].to(ctx.pdt[0]) if ctx.needs_input_grad[2] else None
@@ -848,17 +847,66 @@ def repeat_rows(src, reps):
 # ---------------------------------------------------------------------------------------------
 # A2 + block glue: y = act(BN_a(z1) [+ BN_b(z2)]) [* mask[n]] [+ r1] [+ s * r2]   (csrc/bn_fused.hip)
 # ---------------------------------------------------------------------------------------------
-import ctypes as _ct
-
 ACT_NONE, ACT_RELU, ACT_GELU = 0, 1, 2
 
 
-def _stats_array(t):
-    """host array of 8 device pointers (NULL for the absent second branch)."""
-    arr = (_ct.c_void_p * 8)()
-    for i, x in enumerate(t):
-        arr[i] = None if x is None else x.data_ptr()
+def _ptr_array(ts):
+    """host array of device pointers (NULL for an absent tensor, e.g. the second branch's)."""
+    arr = (_ct.c_void_p * len(ts))()
+    for i, t in enumerate(ts):
+        arr[i] = None if t is None else t.data_ptr()
     return arr
+
+
+def _bn_operands(z1, others, params, mask):
+    """Operand prologue of the fused BatchNorm Functions: z1 contiguous; the other activations (second branch, residuals)
+    contiguous in z1's dtype; gamma / beta detached, contiguous fp32; the per-sample mask flat fp32.
+    -> (z1, others, params, mask, (N, C, HW)), absent operands staying None."""
+    z1 = z1.contiguous()
+    others = [None if t is None else t.contiguous().to(z1.dtype) for t in others]
+    params = [None if p is None else p.detach().float().contiguous() for p in params]
+    maskf = None if mask is None else mask.detach().reshape(-1).float().contiguous()
+    N, C = z1.shape[0], z1.shape[1]
+    return z1, others, params, maskf, (N, C, z1.numel() // (N * C))
+
+
+def _bn_bwd_sums(dy, z1, z2, stats, maskf, act, dyb=None):
+    """Per-channel sums of a BatchNorm backward, [3][C] = sum dy' | sum dy' xhat1 | sum dy' xhat2 (dy' = dy through the
+    activation and the mask): one launch where a workgroup can finish a channel, per-plane partials + finalize for large
+    planes.  `dyb`: a second gradient of the same output, merged in the one-launch kernel (round(dy + dyb), stored for the
+    apply launch), by an element-wise add in front of the two-launch form.  -> (sums, the merged dy, one launch served)."""
+    N, C = z1.shape[0], z1.shape[1]
+    HW = z1.numel() // (N * C)
+    sfx = _suffix(z1)
+    sums = torch.empty(3, C, device=z1.device, dtype=_F32)
+    if dyb is not None:
+        dyb = dyb.contiguous().to(z1.dtype)
+        dym = torch.empty_like(z1)
+        final = try_call(f"ppea_bn_bwd_reduce_final_dup_{sfx}", ptr(dy), ptr(dyb), ptr(dym), ptr(z1), ptr(z2), stats,
+                         ptr(maskf), ptr(sums), act, N, C, HW, stream_ptr())
+        dy = dym if final else dy + dyb
+    else:
+        final = try_call(f"ppea_bn_bwd_reduce_final_{sfx}", ptr(dy), ptr(z1), ptr(z2), stats, ptr(maskf), ptr(sums), act,
+                         N, C, HW, stream_ptr())
+    if not final:                           # large planes: per-plane partials + finalize
+        partial = torch.empty(C * N * 3, device=z1.device, dtype=_F32)
+        call(f"ppea_bn_bwd_reduce_{sfx}", ptr(dy), ptr(z1), ptr(z2), stats, ptr(maskf), ptr(partial), act, N, C, HW,
+             stream_ptr())
+        call("ppea_bn_bwd_finalize_f32", ptr(partial), N, C, ptr(sums), stream_ptr())
+    return sums, dy, final
+
+
+def _bn_grads(ctx, sums, two, dy):
+    """Gradient epilogue of the two-branch Functions: (d gamma1, d beta1, d gamma2, d beta2) from `sums` = d beta | d gamma1 |
+    d gamma2 in the parameters' dtypes, and (d r1, d r2) from the output gradient."""
+    n = ctx.needs_input_grad
+    dg1 = sums[1].to(ctx.pdt[0]) if n[1] else None
+    db1 = sums[0].to(ctx.pdt[1]) if n[2] else None
+    dg2 = sums[2].to(ctx.pdt[2]) if (two and n[6]) else None
+    db2 = sums[0].to(ctx.pdt[2]) if (two and n[7]) else None
+    dr1 = dy if ctx.has[0] else None
+    dr2 = (dy if ctx.r2_scale == 1.0 else dy * ctx.r2_scale) if ctx.has[1] else None
+    return dg1, db1, dg2, db2, dr1, dr2
 
 
 def bn_batch_stats(z, eps, momentum, running_mean=None, running_var=None):
@@ -915,20 +963,10 @@ class _BnAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, z1, g1, b1, mean1, invstd1, z2, g2, b2, mean2, invstd2, mask, r1, r2, r2_scale, act,
                 count, group):
-        z1 = z1.contiguous()
-        N, C = z1.shape[0], z1.shape[1]
-        HW = z1.numel() // (N * C)
-        dt = z1.dtype
-        z2 = None if z2 is None else z2.contiguous().to(dt)
-        r1 = None if r1 is None else r1.contiguous().to(dt)
-        r2 = None if r2 is None else r2.contiguous().to(dt)
-        g1f, b1f = g1.detach().float().contiguous(), b1.detach().float().contiguous()
-        g2f = None if g2 is None else g2.detach().float().contiguous()
-        b2f = None if b2 is None else b2.detach().float().contiguous()
-        maskf = None if mask is None else mask.detach().reshape(-1).float().contiguous()
+        z1, (z2, r1, r2), (g1f, b1f, g2f, b2f), maskf, (N, C, HW) = _bn_operands(z1, (z2, r1, r2), (g1, b1, g2, b2), mask)
         y = torch.empty_like(z1)
         st = (mean1, invstd1, g1f, b1f, mean2, invstd2, g2f, b2f)
-        call(f"ppea_bn_apply_{_suffix(z1)}", ptr(z1), ptr(z2), _stats_array(st), ptr(maskf), ptr(r1), ptr(r2),
+        call(f"ppea_bn_apply_{_suffix(z1)}", ptr(z1), ptr(z2), _ptr_array(st), ptr(maskf), ptr(r1), ptr(r2),
              float(r2_scale), ptr(y), int(act), N, C, HW, stream_ptr())
         ctx.save_for_backward(z1, z2, mean1, invstd1, g1f, b1f, mean2, invstd2, g2f, b2f, maskf)
         ctx.act, ctx.r2_scale, ctx.count, ctx.group = int(act), float(r2_scale), float(count), group
@@ -942,16 +980,8 @@ class _BnAct(torch.autograd.Function):
         N, C = z1.shape[0], z1.shape[1]
         HW = z1.numel() // (N * C)
         dy = dy.contiguous().to(z1.dtype)
-        dev = z1.device
-        st = _stats_array((mean1, invstd1, g1f, b1f, mean2, invstd2, g2f, b2f))
-        sums = torch.empty(3, C, device=dev, dtype=_F32)
-        sfx = _suffix(z1)
-        if not try_call(f"ppea_bn_bwd_reduce_final_{sfx}", ptr(dy), ptr(z1), ptr(z2), st, ptr(maskf), ptr(sums), ctx.act, N, C,
-                        HW, stream_ptr()):                       # large planes: per-plane partials + finalize
-            partial = torch.empty(C * N * 3, device=dev, dtype=_F32)
-            call(f"ppea_bn_bwd_reduce_{sfx}", ptr(dy), ptr(z1), ptr(z2), st, ptr(maskf), ptr(partial), ctx.act, N, C,
-                 HW, stream_ptr())
-            call("ppea_bn_bwd_finalize_f32", ptr(partial), N, C, ptr(sums), stream_ptr())
+        st = _ptr_array((mean1, invstd1, g1f, b1f, mean2, invstd2, g2f, b2f))
+        sums, _, _ = _bn_bwd_sums(dy, z1, z2, st, maskf, ctx.act)
         inv_count = 1.0 / ctx.count
         gscale = None
         if ctx.group is not None:                      # SyncBN: sums of the global batch (ctx.count is the global count)
@@ -959,16 +989,11 @@ class _BnAct(torch.autograd.Function):
             gscale = 1.0 / sync_world(ctx.group[0])    # d gamma / d beta: see _SyncBnAct
         dz1 = torch.empty_like(z1)
         dz2 = None if z2 is None else torch.empty_like(z2)
-        call(f"ppea_bn_bwd_apply_{sfx}", ptr(dy), ptr(z1), ptr(z2), st, ptr(maskf), ptr(sums), inv_count,
+        call(f"ppea_bn_bwd_apply_{_suffix(z1)}", ptr(dy), ptr(z1), ptr(z2), st, ptr(maskf), ptr(sums), inv_count,
              ptr(dz1), ptr(dz2), ctx.act, N, C, HW, stream_ptr())
         if gscale is not None:
             sums = sums * gscale
-        dg1 = sums[1].to(ctx.pdt[0]) if ctx.needs_input_grad[1] else None
-        db1 = sums[0].to(ctx.pdt[1]) if ctx.needs_input_grad[2] else None
-        dg2 = sums[2].to(ctx.pdt[2]) if (z2 is not None and ctx.needs_input_grad[6]) else None
-        db2 = sums[0].to(ctx.pdt[2]) if (z2 is not None and ctx.needs_input_grad[7]) else None
-        dr1 = dy if ctx.has[0] else None
-        dr2 = (dy if ctx.r2_scale == 1.0 else dy * ctx.r2_scale) if ctx.has[1] else None
+        dg1, db1, dg2, db2, dr1, dr2 = _bn_grads(ctx, sums, z2 is not None, dy)
         return (dz1, dg1, db1, None, None, dz2, dg2, db2, None, None, None, dr1, dr2, None, None, None, None)
 
 
@@ -982,13 +1007,6 @@ def bn_channel_ok(z):
     N, C = z.shape[0], z.shape[1]
     HW = z.shape[2] * z.shape[3]
     return C >= 64 and HW % 8 == 0 and N * HW <= 16384
-
-
-def _ptr_array(ts):
-    arr = (_ct.c_void_p * len(ts))()
-    for i, t in enumerate(ts):
-        arr[i] = None if t is None else t.data_ptr()
-    return arr
 
 
 def _other_stream_grad(g):
@@ -1010,17 +1028,7 @@ class _BnActChannel(torch.autograd.Function):
     def forward(ctx, z1, g1, b1, rm1, rv1, z2, g2, b2, rm2, rv2, mask, r1, r2, r2_scale, act, eps, momentum, skip=False,
                 dup=False, sums=None):
         z1_in = z1
-        z1 = z1.contiguous()
-        N, C = z1.shape[0], z1.shape[1]
-        HW = z1.numel() // (N * C)
-        dt = z1.dtype
-        z2 = None if z2 is None else z2.contiguous().to(dt)
-        r1 = None if r1 is None else r1.contiguous().to(dt)
-        r2 = None if r2 is None else r2.contiguous().to(dt)
-        g1f, b1f = g1.detach().float().contiguous(), b1.detach().float().contiguous()
-        g2f = None if g2 is None else g2.detach().float().contiguous()
-        b2f = None if b2 is None else b2.detach().float().contiguous()
-        maskf = None if mask is None else mask.detach().reshape(-1).float().contiguous()
+        z1, (z2, r1, r2), (g1f, b1f, g2f, b2f), maskf, (N, C, HW) = _bn_operands(z1, (z2, r1, r2), (g1, b1, g2, b2), mask)
         st = torch.empty(4, C, device=z1.device, dtype=_F32)          # mean1 | invstd1 | mean2 | invstd2
         y = torch.empty_like(z1)
         if sums is not None and z2 is None:
@@ -1068,7 +1076,7 @@ class _BnActChannel(torch.autograd.Function):
         sums = torch.empty(3, C, device=z1.device, dtype=_F32)
         dz1 = torch.empty_like(z1)
         dz2 = None if z2 is None else torch.empty_like(z2)
-        stats = _stats_array((st[0], st[1], g1f, b1f, st[2] if z2 is not None else None,
+        stats = _ptr_array((st[0], st[1], g1f, b1f, st[2] if z2 is not None else None,
                               st[3] if z2 is not None else None, g2f, b2f))
         if dskip is not None:
             dskip = dskip.contiguous().to(z1.dtype)
@@ -1082,12 +1090,7 @@ class _BnActChannel(torch.autograd.Function):
         else:
             call(f"ppea_bn_bwd_channel_{_suffix(z1)}", ptr(dy), ptr(z1), ptr(z2), stats, ptr(maskf), 1.0 / float(N * HW),
                  ptr(dskip), ptr(dz1), ptr(dz2), ptr(sums), ctx.act, N, C, HW, stream_ptr())
-        dg1 = sums[1].to(ctx.pdt[0]) if ctx.needs_input_grad[1] else None
-        db1 = sums[0].to(ctx.pdt[1]) if ctx.needs_input_grad[2] else None
-        dg2 = sums[2].to(ctx.pdt[2]) if (z2 is not None and ctx.needs_input_grad[6]) else None
-        db2 = sums[0].to(ctx.pdt[2]) if (z2 is not None and ctx.needs_input_grad[7]) else None
-        dr1 = dy if ctx.has[0] else None
-        dr2 = (dy if ctx.r2_scale == 1.0 else dy * ctx.r2_scale) if ctx.has[1] else None
+        dg1, db1, dg2, db2, dr1, dr2 = _bn_grads(ctx, sums, z2 is not None, dy)
         return (dz1, dg1, db1, None, None, dz2, dg2, db2, None, None, None, dr1, dr2, None, None, None, None, None, None, None)
 
 
@@ -1108,15 +1111,7 @@ class _BnActChannelNext(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, gA, bA, rmA, rvA, gB, bB, rmB, rvB, mask, r1, r2, r2_scale, eps, momentum, dup=False):
-        z = z.contiguous()
-        N, C = z.shape[0], z.shape[1]
-        HW = z.numel() // (N * C)
-        dt = z.dtype
-        r1 = None if r1 is None else r1.contiguous().to(dt)
-        r2 = None if r2 is None else r2.contiguous().to(dt)
-        gAf, bAf = gA.detach().float().contiguous(), bA.detach().float().contiguous()
-        gBf, bBf = gB.detach().float().contiguous(), bB.detach().float().contiguous()
-        maskf = None if mask is None else mask.detach().reshape(-1).float().contiguous()
+        z, (r1, r2), (gAf, bAf, gBf, bBf), maskf, (N, C, HW) = _bn_operands(z, (r1, r2), (gA, bA, gB, bB), mask)
         st = torch.empty(4, C, device=z.device, dtype=_F32)          # meanA | invstdA | meanB | invstdB
         y, y2 = torch.empty_like(z), torch.empty_like(z)
         call(f"ppea_bn_fwd_channel_next_{_suffix(z)}", ptr(z), _ptr_array((gAf, bAf, gBf, bBf)),
@@ -1144,7 +1139,7 @@ class _BnActChannelNext(torch.autograd.Function):
         dskip = None if dy is None else dy.contiguous().to(z.dtype)
         sums = torch.empty(4, C, device=z.device, dtype=_F32)
         dz, dyt = torch.empty_like(z), torch.empty_like(z)
-        stats = _stats_array((st[0], st[1], gAf, bAf, st[2], st[3], gBf, bBf))
+        stats = _ptr_array((st[0], st[1], gAf, bAf, st[2], st[3], gBf, bBf))
         if dy2b is not None:
             dy2b = dy2b.contiguous().to(z.dtype)
             call(f"ppea_bn_bwd_channel_next_dup_{_suffix(z)}", ptr(dy2), ptr(dy2b), ptr(dskip), ptr(z),
@@ -1187,20 +1182,16 @@ def sync_bn_supported(z):
 
 
 def sync_world(group):
-    import torch.distributed as dist
     return dist.get_world_size(group)
 
 
 def sync_rank(group):
-    import torch.distributed as dist
     return dist.get_rank(group)
 
 
 def gather_rows(table, group):
     """ONE all-gather, IN PLACE: `table` [world, pitch] arrives with this rank's row filled (the statistics kernel wrote
     straight into it) and leaves with every rank's row -- no staging copy on either side of the collective."""
-    import torch.distributed as dist
-    from .dist import log_collective
     mine = table[sync_rank(group)]
     log_collective("all_gather", table, group)
     if dist.get_backend(group) == "nccl":
@@ -1212,8 +1203,6 @@ def gather_rows(table, group):
 
 def reduce_sums(sums, group):
     """ONE in-place all-reduce (sum) of a BatchNorm backward's [3][C] sums."""
-    import torch.distributed as dist
-    from .dist import log_collective
     log_collective("all_reduce", sums, group)
     dist.all_reduce(sums, group=group)
     _count(collectives=1)
@@ -1233,19 +1222,9 @@ class _SyncBnAct(torch.autograd.Function):
     def forward(ctx, z1, g1, b1, rm1, rv1, z2, g2, b2, rm2, rv2, mask, r1, r2, r2_scale, act, eps, momentum, group, table,
                 sums, skip, emit, dup=False):
         z1_in = z1
-        z1 = z1.contiguous()
-        N, C = z1.shape[0], z1.shape[1]
-        HW = z1.numel() // (N * C)
-        dt = z1.dtype
+        z1, (z2, r1, r2), (g1f, b1f, g2f, b2f), maskf, (N, C, HW) = _bn_operands(z1, (z2, r1, r2), (g1, b1, g2, b2), mask)
         sfx = _suffix(z1)
         dev = z1.device
-        z2 = None if z2 is None else z2.contiguous().to(dt)
-        r1 = None if r1 is None else r1.contiguous().to(dt)
-        r2 = None if r2 is None else r2.contiguous().to(dt)
-        g1f, b1f = g1.detach().float().contiguous(), b1.detach().float().contiguous()
-        g2f = None if g2 is None else g2.detach().float().contiguous()
-        b2f = None if b2 is None else b2.detach().float().contiguous()
-        maskf = None if mask is None else mask.detach().reshape(-1).float().contiguous()
         two = z2 is not None
         pitch = (4 if two else 2) * C + 1
         world, rank = sync_world(group), sync_rank(group)
@@ -1312,22 +1291,8 @@ class _SyncBnAct(torch.autograd.Function):
         if dyb is not None and (ctx.has[0] or ctx.has[1]):
             dy, dyb = dy + dyb.to(z1.dtype), None             # (r1 / r2 receive dy itself: not a block's first BatchNorm)
         two = z2 is not None
-        stats = _stats_array((st[0], st[1], g1f, b1f, st[2] if two else None, st[3] if two else None, g2f, b2f))
-        sums = torch.empty(3, C, device=dev, dtype=_F32)
-        if dyb is not None:
-            dyb = dyb.contiguous().to(z1.dtype)
-            dym = torch.empty_like(z1)
-            final = try_call(f"ppea_bn_bwd_reduce_final_dup_{sfx}", ptr(dy), ptr(dyb), ptr(dym), ptr(z1), ptr(z2), stats,
-                             ptr(maskf), ptr(sums), ctx.act, N, C, HW, stream_ptr())
-            dy = dym if final else dy + dyb
-        else:
-            final = try_call(f"ppea_bn_bwd_reduce_final_{sfx}", ptr(dy), ptr(z1), ptr(z2), stats, ptr(maskf), ptr(sums),
-                             ctx.act, N, C, HW, stream_ptr())
-        if not final:                       # large planes: per-plane partials + finalize
-            partial = torch.empty(C * N * 3, device=dev, dtype=_F32)
-            call(f"ppea_bn_bwd_reduce_{sfx}", ptr(dy), ptr(z1), ptr(z2), stats, ptr(maskf), ptr(partial), ctx.act, N, C,
-                 HW, stream_ptr())
-            call("ppea_bn_bwd_finalize_f32", ptr(partial), N, C, ptr(sums), stream_ptr())
+        stats = _ptr_array((st[0], st[1], g1f, b1f, st[2] if two else None, st[3] if two else None, g2f, b2f))
+        sums, dy, final = _bn_bwd_sums(dy, z1, z2, stats, maskf, ctx.act, dyb)
         _count(launches=1 if final else 2)
         reduce_sums(sums, ctx.group)                            # -> sums of the global batch
         dz1 = torch.empty_like(z1)
@@ -1337,13 +1302,7 @@ class _SyncBnAct(torch.autograd.Function):
              1.0 / float(N * HW * ctx.world), ptr(dskip), ptr(dz1), ptr(dz2), ptr(dgb), 1.0 / ctx.world, ctx.act, N, C, HW,
              stream_ptr())
         _count(launches=1)
-        n = ctx.needs_input_grad
-        dg1 = dgb[1].to(ctx.pdt[0]) if n[1] else None
-        db1 = dgb[0].to(ctx.pdt[1]) if n[2] else None
-        dg2 = dgb[2].to(ctx.pdt[2]) if (two and n[6]) else None
-        db2 = dgb[0].to(ctx.pdt[2]) if (two and n[7]) else None
-        dr1 = dy if ctx.has[0] else None
-        dr2 = (dy if ctx.r2_scale == 1.0 else dy * ctx.r2_scale) if ctx.has[1] else None
+        dg1, db1, dg2, db2, dr1, dr2 = _bn_grads(ctx, dgb, two, dy)
         return (dz1, dg1, db1, None, None, dz2, dg2, db2, None, None, None, dr1, dr2) + (None,) * 10
 
 
@@ -1734,7 +1693,7 @@ def pwgrad_into(p, q, w_shape, w_dtype, taps=1, b_rows=None, b_dtype=None):
     return dw, db
 
 
-PWGRAD_PAIR = __import__("os").environ.get("PPEA_PWGRAD_PAIR", "1") == "1"
+PWGRAD_PAIR = os.environ.get("PPEA_PWGRAD_PAIR", "1") == "1"
 
 
 def pwgrad_into_pair(a, b):
@@ -2539,7 +2498,7 @@ def table_affine(x, tab, act=ACT_NONE, x2=None, tab2=None, r1=None, r2=None, r2_
     zero, one = unit_vecs(C, x.device)
     st = (zero, tab[0], one, tab[1]) + ((zero, tab2[0], one, tab2[1]) if x2 is not None else (None,) * 4)
     y = torch.empty_like(x)
-    call(f"ppea_bn_apply_{_suffix(x)}", ptr(x), ptr(_as(x2, x.dtype)), _stats_array(st), None, ptr(_as(r1, x.dtype)),
+    call(f"ppea_bn_apply_{_suffix(x)}", ptr(x), ptr(_as(x2, x.dtype)), _ptr_array(st), None, ptr(_as(r1, x.dtype)),
          ptr(_as(r2, x.dtype)), float(r2_scale), ptr(y), int(act), N, C, x.numel() // (N * C), stream_ptr())
     return y
 

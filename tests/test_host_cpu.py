@@ -139,6 +139,66 @@ def test_bn_replay_matches_two_sequential_updates():
     assert int(bn.num_batches_tracked) == 3
 
 
+def test_bn_book_counts_and_replays_in_every_state():
+    """batchnorm.book, the one bookkeeping of every BatchNorm path: (a) no deferred book: counted at once; (b) deferred,
+    grad enabled, replay_update: nothing until flush(), then two calls counted and the running statistics moved by the
+    replayed update; (c) under no_grad and (d) without replay_update: one call counted at flush(), statistics untouched."""
+    from ppeadepth.batchnorm import BatchNorm2d, DeferredStats, book, set_deferred
+    g = torch.Generator().manual_seed(3)
+    mean, var, count = torch.randn(6, generator=g), torch.rand(6, generator=g) + 0.5, 40.0
+
+    def run(deferred, replay, grad):
+        bn = BatchNorm2d(6).train()
+        bn.replay_update = replay
+        d = DeferredStats() if deferred else None
+        set_deferred(d)
+        try:
+            with torch.set_grad_enabled(grad):
+                book(bn, mean, (var + bn.eps).rsqrt(), count)
+        finally:
+            set_deferred(None)
+        before = (int(bn.num_batches_tracked), bn.running_mean.clone(), bn.running_var.clone())
+        if d is not None:
+            d.flush()
+        return bn, before
+
+    bn, before = run(False, True, True)                                              # (a)
+    assert before[0] == 1 and int(bn.num_batches_tracked) == 1
+    assert torch.equal(bn.running_mean, torch.zeros(6)) and torch.equal(bn.running_var, torch.ones(6))
+    bn, before = run(True, True, True)                                               # (b)
+    assert before[0] == 0 and torch.equal(before[1], torch.zeros(6)) and torch.equal(before[2], torch.ones(6))
+    assert int(bn.num_batches_tracked) == 2
+    assert rel_err(bn.running_mean, 0.1 * mean) < 1e-6
+    assert rel_err(bn.running_var, 0.9 + 0.1 * var * count / (count - 1)) < 1e-6
+    for replay, grad in ((True, False), (False, True)):                              # (c), (d)
+        bn, before = run(True, replay, grad)
+        assert before[0] == 0 and int(bn.num_batches_tracked) == 1
+        assert torch.equal(bn.running_mean, torch.zeros(6)) and torch.equal(bn.running_var, torch.ones(6))
+    bn = BatchNorm2d(6).train()                                                      # counting only: n calls, never a replay
+    bn.replay_update = True
+    d = DeferredStats()
+    set_deferred(d)
+    try:
+        book(bn, n=3)
+    finally:
+        set_deferred(None)
+    d.flush()
+    assert int(bn.num_batches_tracked) == 3 and torch.equal(bn.running_var, torch.ones(6))
+
+
+def test_deferred_book_is_read_only_inside_batchnorm():
+    """The step's deferred book has one reader, batchnorm.book: no other module of the package names the global."""
+    pkg = os.path.join(ROOT, "ppea-depth_amd", "ppeadepth")
+    hits = []
+    for folder, _dirs, files in os.walk(pkg):
+        for f in files:
+            path = os.path.join(folder, f)
+            if f.endswith(".py") and os.path.relpath(path, pkg) != "batchnorm.py" and "_ACTIVE_DEFERRED" in open(path).read():
+                hits.append(os.path.relpath(path, pkg))
+    assert not hits, hits
+    assert "_ACTIVE_DEFERRED" in open(os.path.join(pkg, "batchnorm.py")).read()
+
+
 def test_depth_bins_tracker(golden):
     from ppeadepth.trainer import DepthBins
     g = golden("depth_bins")

@@ -35,7 +35,7 @@ for (N, C, H, W, act) in [(12, 2048, 12, 40, ops.ACT_GELU), (12, 512, 12, 40, op
     sums = torch.empty(3, C, device=dev, dtype=torch.float32)
     dz = torch.empty_like(z)
     g1, b1 = bn.weight.detach().float(), bn.bias.detach().float()
-    stats = ops._stats_array((st[0], st[1], g1, b1, None, None, None, None))
+    stats = ops._ptr_array((st[0], st[1], g1, b1, None, None, None, None))
     tb = graph_time(lambda: ops.call("ppea_bn_bwd_channel_bf16", ops.ptr(dy), ops.ptr(z), None, stats, None, 1.0 / (N * H * W),
                                      None, ops.ptr(dz), None, ops.ptr(sums), int(act), N, C, H * W, ops.stream_ptr()))
     by = z.numel() * 2
