@@ -101,6 +101,24 @@ int ppea_dwconv3x3_bwd_data_bf16(const void* dy, const float* w, void* dx, int N
  * dw[c,0,u,v] = sum_{n,i,j} dy[n,c,i,j] * x[n,c,i+u-K/2,j+v-K/2].  dw is overwritten. */
 int ppea_dwconv_lk_bwd_filter_f32(const float* x, const float* dy, float* dw,
                                   int N, int C, int H, int W, int K, void* stream);
+/* The same quantity for bf16 activations on the matrix cores (csrc/dwconv_wgrad.hip): per channel a 32 x 32 GEMM tile
+ * over k = (n, input row, column), dw_c[u][v] = sum_k dy[n,c,r-u+K/2,j] * x[n,c,r,j+v-K/2].  BOTH filters of the
+ * re-parameterised pair leave one launch that reads x once (dy_small / dw_small NULL iff KS == 0); dw_* are fp32 and
+ * overwritten.  The (n, row band) parts go through `workspace` (ppea_dwconv_lk_bwd_filter_workspace_bytes bytes) and are
+ * added in a fixed order by a second launch: no atomics.  Served: K in {31, 29, 27, 13}, KS in {0, 5}, W <= 4096 and
+ * N * H < 2^30 (any C, planes smaller than the filter included); otherwise both return PPEA_ERR_UNSUPPORTED and the
+ * caller keeps the _f32 entry point. */
+long ppea_dwconv_lk_bwd_filter_workspace_bytes(int N, int C, int H, int W, int K, int KS);
+int ppea_dwconv_lk_bwd_filter_bf16(const uint16_t* x, const uint16_t* dy_big, const uint16_t* dy_small,
+                                   float* dw_big, float* dw_small, void* workspace,
+                                   int N, int C, int H, int W, int K, int KS, void* stream);
+/* wgrad of the depthwise 3x3 (stride 1 / 2, pad 1): dw[c,0,u,v] = sum_{n,i,j} dy[n,c,i,j] * x[n,c,i*s+u-1,j*s+v-1], fp32,
+ * overwritten; x [N,C,H,W], dy [N,C,Ho,Wo].  Per-part sums through `workspace`, added in a fixed order (no atomics). */
+long ppea_dwconv3x3_bwd_filter_workspace_bytes(int N, int C, int H, int W, int stride);
+int ppea_dwconv3x3_bwd_filter_f32(const void* x, const void* dy, float* dw, void* workspace, int N, int C, int H, int W,
+                                  int stride, void* stream);
+int ppea_dwconv3x3_bwd_filter_bf16(const void* x, const void* dy, float* dw, void* workspace, int N, int C, int H, int W,
+                                   int stride, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A5/A6  Pointwise (1x1) convolution on MFMA, NCHW bf16 (csrc/pwconv.hip): RepLKBlock.pw1/pw2,

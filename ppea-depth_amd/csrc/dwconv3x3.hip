@@ -324,9 +324,120 @@ int run_affine(const void* a, const float* w, const float* s, const float* o, in
     return launch_status();
 }
 
+// ---- filter gradient (full fine-tuning) --------------------------------------------------------------------
+// dw[c][u][v] = sum_{n,oy,ox} dy[n][c][oy][ox] * x[n][c][oy*S+u-1][ox*S+v-1].  grid (C, parts): a part is a band of
+// (n, oy) rows; every thread keeps nine fp32 sums over its pixels, the block reduces them (wave shuffles, then the four
+// waves in order) into ws[c][part][9].  dwconv3x3_bwd_filter_sum adds the parts in index order: no atomics, a bitwise function of
+// the inputs.
+template <typename T, int S>
+__global__ __launch_bounds__(256) void dwconv3x3_bwd_filter(const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ ws,
+                                                 int N, int C, int H, int W, int Ho, int Wo, int rows_per_part) {
+    const int c = blockIdx.x, part = blockIdx.y, parts = gridDim.y;
+    const long rows = (long)N * Ho;
+    const long r0 = (long)part * rows_per_part;
+    long r1 = r0 + rows_per_part;
+    if (r1 > rows) r1 = rows;
+    float acc[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) acc[t] = 0.f;
+    // a wave per (n, oy) row, its lanes over the columns: one division per row and none per pixel
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (long row = r0 + wave; row < r1; row += 4) {
+        const int n = (int)(row / Ho), oy = (int)(row - (long)n * Ho);
+        const T* dp = dy + (((long)n * C + c) * Ho + oy) * Wo;
+        const T* xp = x + ((long)n * C + c) * H * W;
+        const int iy0 = oy * S - 1;
+        for (int ox = lane; ox < Wo; ox += 64) {
+            const float g = ld_f32<T>(dp + ox);
+            const int ix0 = ox * S - 1;
+#pragma unroll
+            for (int u = 0; u < 3; ++u) {
+                const int iy = iy0 + u;
+                if (iy < 0 || iy >= H) continue;
+#pragma unroll
+                for (int v = 0; v < 3; ++v) {
+                    const int ix = ix0 + v;
+                    if (ix >= 0 && ix < W) acc[u * 3 + v] = fmaf(g, ld_f32<T>(xp + (long)iy * W + ix), acc[u * 3 + v]);
+                }
+            }
+        }
+    }
+    __shared__ float red[4][9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+        const float s = wave_sum(acc[t]);
+        if (lane == 0) red[wave][t] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < 9)
+        ws[((long)c * parts + part) * 9 + threadIdx.x] =
+            ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+__global__ __launch_bounds__(256) void dwconv3x3_bwd_filter_sum(const float* __restrict__ ws, float* __restrict__ dw, int total, int parts) {
+    const int i = blockIdx.x * 256 + threadIdx.x;          // c * 9 + t
+    if (i >= total) return;
+    const int c = i / 9, t = i - c * 9;
+    float s = 0.f;
+    for (int p = 0; p < parts; ++p) s += ws[((long)c * parts + p) * 9 + t];
+    dw[i] = s;
+}
+
+inline bool wgrad_shape_ok(int N, int C, int H, int W, int stride) {
+    return N > 0 && C > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2) && C <= 65535 * 32;
+}
+// rows of (n, oy) per part: at least ~8192 output pixels per block, at most 64 parts per channel
+inline int wgrad_rows_per_part(int N, int Ho, int Wo) {
+    const long rows = (long)N * Ho;
+    long parts = ((long)rows * Wo + 8191) / 8192;
+    if (parts < 1) parts = 1;
+    if (parts > 64) parts = 64;
+    if (parts > rows) parts = rows;
+    return (int)((rows + parts - 1) / parts);
+}
+inline int wgrad_parts(int N, int Ho, int Wo) {
+    const long rows = (long)N * Ho;
+    const int rpp = wgrad_rows_per_part(N, Ho, Wo);
+    return (int)((rows + rpp - 1) / rpp);
+}
+
+template <typename T>
+int run_wgrad(const void* x, const void* dy, float* dw, void* workspace, int N, int C, int H, int W, int stride, void* stream) {
+    if (!wgrad_shape_ok(N, C, H, W, stride)) return PPEA_ERR_UNSUPPORTED;
+    if (x == nullptr || dy == nullptr || dw == nullptr || workspace == nullptr) return PPEA_ERR_ARG;
+    const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;
+    const int rpp = wgrad_rows_per_part(N, Ho, Wo), parts = wgrad_parts(N, Ho, Wo);
+    hipStream_t st = (hipStream_t)stream;
+    float* ws = (float*)workspace;
+    const dim3 g((unsigned)C, (unsigned)parts);
+    if (stride == 1)
+        hipLaunchKernelGGL((dwconv3x3_bwd_filter<T, 1>), g, dim3(256), 0, st, (const T*)x, (const T*)dy, ws, N, C, H, W, Ho, Wo, rpp);
+    else
+        hipLaunchKernelGGL((dwconv3x3_bwd_filter<T, 2>), g, dim3(256), 0, st, (const T*)x, (const T*)dy, ws, N, C, H, W, Ho, Wo, rpp);
+    const int r = launch_status();
+    if (r != 0) return r;
+    hipLaunchKernelGGL(dwconv3x3_bwd_filter_sum, dim3((unsigned)((C * 9 + 255) / 256)), dim3(256), 0, st, ws, dw, C * 9, parts);
+    return launch_status();
+}
+
 }  // namespace
 
 extern "C" {
+// Filter gradient (full fine-tuning, --fullft_reb): dw [C,1,3,3] fp32 = sum_{n,oy,ox} dy[n,c,oy,ox] * x[n,c,oy*s+u-1,ox*s+v-1]
+// (zero outside the plane); x [N,C,H,W], dy [N,C,Ho,Wo].  `workspace`: ppea_dwconv3x3_bwd_filter_workspace_bytes bytes of
+// device scratch for the per-part sums, added in a fixed order by a second launch (no atomics).  dw is overwritten.
+long ppea_dwconv3x3_bwd_filter_workspace_bytes(int N, int C, int H, int W, int stride) {
+    if (!wgrad_shape_ok(N, C, H, W, stride)) return PPEA_ERR_UNSUPPORTED;
+    return (long)C * wgrad_parts(N, (H - 1) / stride + 1, (W - 1) / stride + 1) * 9 * (long)sizeof(float);
+}
+int ppea_dwconv3x3_bwd_filter_f32(const void* x, const void* dy, float* dw, void* workspace, int N, int C, int H, int W,
+                                  int stride, void* stream) {
+    return run_wgrad<float>(x, dy, dw, workspace, N, C, H, W, stride, stream);
+}
+int ppea_dwconv3x3_bwd_filter_bf16(const void* x, const void* dy, float* dw, void* workspace, int N, int C, int H, int W,
+                                   int stride, void* stream) {
+    return run_wgrad<uint16_t>(x, dy, dw, workspace, N, C, H, W, stride, stream);
+}
 // Inference: y = act(s[c] * DW3x3(x)[c] + o[c]), relu != 0: ReLU (eval-mode BatchNorm folded to a table); shapes as
 // ppea_dwconv3x3_fwd_*; N * C > 65535 or stride not in {1, 2}: PPEA_ERR_UNSUPPORTED.
 int ppea_dwconv3x3_fwd_affine_f32(const void* x, const float* w, const float* s, const float* o, int relu, void* y, int N, int C,

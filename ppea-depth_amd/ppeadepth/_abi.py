@@ -25,6 +25,11 @@ SIGNATURES = {
     "ppea_dwconv_lk_bwd_data_f32": [_vp] * 5 + [_i] * 6 + [_vp],
     "ppea_dwconv_lk_bwd_data_bf16": [_vp] * 5 + [_i] * 6 + [_vp],
     "ppea_dwconv_lk_bwd_filter_f32": [_vp] * 3 + [_i] * 5 + [_vp],
+    "ppea_dwconv_lk_bwd_filter_workspace_bytes": [_i] * 6,
+    "ppea_dwconv_lk_bwd_filter_bf16": [_vp] * 6 + [_i] * 6 + [_vp],
+    "ppea_dwconv3x3_bwd_filter_workspace_bytes": [_i] * 5,
+    "ppea_dwconv3x3_bwd_filter_f32": [_vp] * 4 + [_i] * 5 + [_vp],
+    "ppea_dwconv3x3_bwd_filter_bf16": [_vp] * 4 + [_i] * 5 + [_vp],
     "ppea_dwconv3x3_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ppea_dwconv3x3_fwd_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ppea_dwconv3x3_bwd_data_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

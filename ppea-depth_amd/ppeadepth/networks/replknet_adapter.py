@@ -133,10 +133,11 @@ class LargeKernelDW(nn.Conv2d):
 
 
 class SmallDW(nn.Conv2d):
-    """Depthwise 3x3, stride 1/2, pad 1 (stem / transitions) on the HIP stencil kernel when frozen."""
+    """Depthwise 3x3, stride 1/2, pad 1 (stem / transitions) on the HIP stencil kernels; a trainable filter
+    (--fullft_reb) gets its gradient from them too."""
 
     def forward(self, x):
-        if x.is_cuda and not self.weight.requires_grad and self.bias is None:
+        if x.is_cuda and self.bias is None:
             return ops.dwconv3x3(x, self.weight, self.stride[0])
         return super().forward(x)
 
@@ -151,12 +152,16 @@ class ImageConv(ops.Conv2d):
 
 
 class PointwiseConv(ops.Conv2d):
-    """1x1 stride-1 conv; frozen + bf16 activations run on the NCHW MFMA kernel (forward with W, data
-    gradient with W^T), everything else on the library conv."""
+    """1x1 stride-1 conv; bf16 activations run on the NCHW MFMA kernel (forward with W, data gradient with W^T; a
+    trainable weight -- full fine-tuning -- also gets its gradient there), everything else on ops.Conv2d."""
+
+    def _mfma(self, x, want_sums=False):
+        fn = ops.pwconv_trainable if self.weight.requires_grad else ops.pwconv_frozen
+        return fn(x, self.weight, want_sums=want_sums)
 
     def forward(self, x):
-        if PW_MFMA and x.is_cuda and x.dtype == torch.bfloat16 and not self.weight.requires_grad:
-            y = ops.pwconv_frozen(x, self.weight)
+        if PW_MFMA and x.is_cuda and x.dtype == torch.bfloat16:
+            y = self._mfma(x)
             if y is not None:
                 return y
         return super().forward(x)
@@ -168,9 +173,9 @@ class PointwiseConv(ops.Conv2d):
         from ..batchnorm import _collectives_on
         # (several ranks: BatchNorm statistics are a launch of their own at every size -- the all-gather sits between them
         # and the apply launch -- so the epilogue sums replace a pass over the activation at stages 2 / 3 as well)
-        if (PW_MFMA and BN_SUMS and x.is_cuda and x.dtype == torch.bfloat16 and not self.weight.requires_grad
+        if (PW_MFMA and BN_SUMS and x.is_cuda and x.dtype == torch.bfloat16
                 and (always or x.shape[0] * x.shape[2] * x.shape[3] > 16384 or _collectives_on())):
-            r = ops.pwconv_frozen(x, self.weight, want_sums=True)
+            r = self._mfma(x, want_sums=True)
             if r is not None:
                 return r
         return self.forward(x), None

@@ -173,15 +173,25 @@ class _DwConvLK(torch.autograd.Function):
                 _timed("bwd31", K, lambda: call(f"ppea_dwconv_lk_bwd_data_{_suffix(x)}", ptr(dy_big),
                                                  ptr(dy_small), ptr(wb), ptr(ws), ptr(dx), N, C, H, W, K, KS,
                                                  stream_ptr()))
-        if ctx.needs_input_grad[1]:
-            dwb = torch.empty_like(wb)
-            call("ppea_dwconv_lk_bwd_filter_f32", ptr(x.float().contiguous()), ptr(dy_big.float().contiguous()),
-                 ptr(dwb), N, C, H, W, K, stream_ptr())
+        want_b, want_s = ctx.needs_input_grad[1], ctx.has_small and ctx.needs_input_grad[2]
+        if want_b and _mfma_ok(x, K, KS):
+            # bf16 activations: both filter gradients from one MFMA launch that reads x once (csrc/dwconv_wgrad.hip)
+            got = dwconv_lk_bwd_filter(x, dy_big, dy_small if want_s else None, K)
+            if got is not None:
+                dwb = got[0].view_as(wb).to(ctx.w_dtypes[0])
+                if want_s:
+                    dws = got[1].view_as(ws).to(ctx.w_dtypes[1])
+                want_b = want_s = False
+        if want_b or want_s:
+            # (the fp32 copies are held in locals: a temporary freed before the next allocation would hand its block on)
+            xf = x.float().contiguous()
+        if want_b:
+            dwb, dyf = torch.empty_like(wb), dy_big.float().contiguous()
+            call("ppea_dwconv_lk_bwd_filter_f32", ptr(xf), ptr(dyf), ptr(dwb), N, C, H, W, K, stream_ptr())
             dwb = dwb.to(ctx.w_dtypes[0])
-        if ctx.has_small and ctx.needs_input_grad[2]:
-            dws = torch.empty_like(ws)
-            call("ppea_dwconv_lk_bwd_filter_f32", ptr(x.float().contiguous()),
-                 ptr(dy_small.float().contiguous()), ptr(dws), N, C, H, W, KS, stream_ptr())
+        if want_s:
+            dws, dyf = torch.empty_like(ws), dy_small.float().contiguous()
+            call("ppea_dwconv_lk_bwd_filter_f32", ptr(xf), ptr(dyf), ptr(dws), N, C, H, W, KS, stream_ptr())
             dws = dws.to(ctx.w_dtypes[1])
         return dx, dwb, dws, None
 
@@ -239,6 +249,24 @@ class _DwConvLKBn(torch.autograd.Function):
         dg = sums[1].to(ctx.pdt[0]) if ctx.needs_input_grad[2] else None
         db = sums[0].to(ctx.pdt[1]) if ctx.needs_input_grad[3] else None
         return dz, None, dg, db, None, None, None, None, None, None
+
+
+def dwconv_lk_bwd_filter(x, dy_big, dy_small, K):
+    """(dw_big [C,K,K], dw_small [C,5,5] or None) fp32: the filter gradients of the depthwise pair for bf16 x / dy
+    [N,C,H,W] from one launch on the matrix cores + a fixed-order sum of its (n, row band) parts; None where the kernel
+    does not serve (K, KS) -- the caller then keeps ppea_dwconv_lk_bwd_filter_f32."""
+    N, C, H, W = x.shape
+    KS = 0 if dy_small is None else 5
+    nbytes = _abi.lib.ppea_dwconv_lk_bwd_filter_workspace_bytes(N, C, H, W, K, KS)
+    if nbytes < 0:
+        return None
+    ws = torch.empty(nbytes // 4, device=x.device, dtype=_F32)
+    dwb = torch.empty(C, K, K, device=x.device, dtype=_F32)
+    dws = torch.empty(C, 5, 5, device=x.device, dtype=_F32) if KS else None
+    if not try_call("ppea_dwconv_lk_bwd_filter_bf16", ptr(x, _BF16), ptr(dy_big, _BF16), ptr(dy_small, _BF16), ptr(dwb),
+                    ptr(dws), ptr(ws), N, C, H, W, K, KS, stream_ptr()):
+        return None
+    return dwb, dws
 
 
 def dwconv_lk_bn_supported(shape, K, KS):
@@ -1564,23 +1592,36 @@ class _DwConv3x3(torch.autograd.Function):
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
         y = torch.empty(N, C, Ho, Wo, device=x.device, dtype=x.dtype)
         call(f"ppea_dwconv3x3_fwd_{_suffix(x)}", ptr(x), ptr(wf), ptr(y), N, C, H, W, stride, stream_ptr())
-        ctx.save_for_backward(wf)
-        ctx.meta = (N, C, H, W, stride, x.dtype)
+        # (the input is kept only for a trainable filter: full fine-tuning)
+        ctx.save_for_backward(wf, x if ctx.needs_input_grad[1] else None)
+        ctx.meta = (N, C, H, W, stride, x.dtype, w.shape, w.dtype)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        (wf,) = ctx.saved_tensors
-        N, C, H, W, stride, dt = ctx.meta
+        wf, x = ctx.saved_tensors
+        N, C, H, W, stride, dt, w_shape, w_dtype = ctx.meta
         dy = dy.contiguous().to(dt)
-        dx = torch.empty(N, C, H, W, device=dy.device, dtype=dt)
-        call(f"ppea_dwconv3x3_bwd_data_{_suffix(dy)}", ptr(dy), ptr(wf), ptr(dx), N, C, H, W, stride, stream_ptr())
-        return dx, None, None
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty(N, C, H, W, device=dy.device, dtype=dt)
+            call(f"ppea_dwconv3x3_bwd_data_{_suffix(dy)}", ptr(dy), ptr(wf), ptr(dx), N, C, H, W, stride, stream_ptr())
+        if ctx.needs_input_grad[1]:
+            nbytes = _abi.lib.ppea_dwconv3x3_bwd_filter_workspace_bytes(N, C, H, W, stride)
+            if nbytes < 0:
+                raise PpeaKernelError(f"dwconv3x3 filter gradient: shape {(N, C, H, W)} stride {stride} is not served")
+            ws = torch.empty(nbytes // 4, device=dy.device, dtype=_F32)
+            dw = torch.empty(w_shape, device=dy.device, dtype=_F32)
+            call(f"ppea_dwconv3x3_bwd_filter_{_suffix(dy)}", ptr(x), ptr(dy), ptr(dw), ptr(ws), N, C, H, W, stride,
+                 stream_ptr())
+            dw = dw.to(w_dtype)
+        return dx, dw, None
 
 
 def dwconv3x3(x, w, stride):
-    """Frozen-filter depthwise 3x3 (no weight gradient: the backbone convs are frozen, repdepth.py:47-50)."""
-    return _DwConv3x3.apply(x, w.detach(), stride)
+    """Depthwise 3x3 (stride 1 / 2, pad 1, no bias) on the stencil kernels.  A frozen filter (the adapter configurations,
+    repdepth.py:47-50) gets no gradient; a trainable one (--fullft_reb) gets it from ppea_dwconv3x3_bwd_filter_*."""
+    return _DwConv3x3.apply(x, w, stride)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1639,6 +1680,52 @@ def pwconv_frozen(x, w, want_sums=False):
     if want_sums:
         return _PwConvFrozen.apply(x, w, True)
     return _PwConvFrozen.apply(x, w)
+
+
+class _PwConvTrainable(torch.autograd.Function):
+    """1x1 conv with a TRAINABLE weight on the bf16 GEMM (full fine-tuning): the forward launches of _PwConvFrozen on
+    W [Cout][Cin] bf16 -- the parameter itself when it is stored in bf16, else an image built on THIS use (flat Adam
+    updates the weight through raw pointers, so no image of it is ever cached) --, the data gradient on W^T built per
+    use, the weight gradient from the split-K reduce kernel in the parameter's layout and dtype."""
+
+    @staticmethod
+    def forward(ctx, x, w, want_sums=False):
+        M, K = w.shape[0], w.shape[1]
+        a = w.detach().reshape(M, K)
+        a = a if a.dtype == _BF16 and a.is_contiguous() else a.to(_BF16).contiguous()
+        x = x.contiguous()
+        ctx.save_for_backward(x, a)
+        ctx.w_meta = (w.shape, _grad_dtype(w))
+        if not want_sums:
+            return pwconv_raw(a, x)
+        B, _, H, W = x.shape
+        y = torch.empty(B, M, H, W, device=x.device, dtype=_BF16)
+        P = _abi.lib.ppea_pwconv_stats_partials(B, M, K, H * W)
+        sums = torch.empty(M, P, 2, device=x.device, dtype=_F32)
+        call("ppea_pwconv_stats_bf16", ptr(a, _BF16), ptr(x, _BF16), None, ptr(y), ptr(sums), B, M, K, H * W, stream_ptr())
+        ctx.mark_non_differentiable(sums)
+        ctx.set_materialize_grads(False)
+        return y, sums
+
+    @staticmethod
+    def backward(ctx, dy, _dsums=None):
+        x, a = ctx.saved_tensors
+        dy = dy.contiguous().to(_BF16)
+        dx = pwconv_raw(a.t().contiguous(), dy) if ctx.needs_input_grad[0] else None
+        dw = pwgrad_into(dy, x, *ctx.w_meta)[0] if ctx.needs_input_grad[1] else None
+        return dx, dw, None
+
+
+def pwconv_trainable(x, w, want_sums=False):
+    """pwconv_frozen for a weight that takes a gradient: same shape conditions (None when the GEMM does not serve them:
+    the caller keeps ops.Conv2d), same forward arithmetic, and x.grad / w.grad from the bf16 GEMM kernels."""
+    B, K, H, W = x.shape
+    if (x.dtype != _BF16 or not x.is_cuda or K % 32 != 0 or w.shape[0] % 32 != 0 or (H * W) % 8 != 0
+            or w.dim() != 4 or w.shape[2:] != (1, 1)):
+        return None
+    if want_sums:
+        return _PwConvTrainable.apply(x, w, True)
+    return _PwConvTrainable.apply(x, w)
 
 
 # ---------------------------------------------------------------------------------------------
