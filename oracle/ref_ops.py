@@ -411,3 +411,21 @@ def _np_median(t):
     s = t.sort()[0]
     n = s.numel()
     return (s[n // 2 - 1] + s[n // 2]) / 2
+
+
+# ---------------------------------------------------------------------------------------------
+# optimizer: trainer.py:142 `optim.Adam(parameters, learning_rate)`, stepped at trainer.py:350
+# ---------------------------------------------------------------------------------------------
+def adam_step(p, g, m, v, t, lr, b1, b2, eps, gscale=1.0):
+    """One step of torch.optim.Adam (no weight decay, no amsgrad) in float64 on the gradient g * gscale:
+        m = b1 m + (1 - b1) g;   v = b2 v + (1 - b2) g^2;   p -= lr / (1 - b1^t) * m / (sqrt(v) / sqrt(1 - b2^t) + eps)
+    t is the number of this step (1 for the first).  Tensors of any float type are taken at their stored values; the
+    scalars are Python floats (pass the fp32 values an fp32 implementation was handed, e.g. float(numpy.float32(0.999))).
+    -> (p, m, v) float64, the inputs untouched."""
+    p, g, m, v = (x.detach().double() for x in (p, g, m, v))
+    t, lr, b1, b2, eps, gscale = (float(x) for x in (t, lr, b1, b2, eps, gscale))
+    g = g * gscale
+    m = b1 * m + (1.0 - b1) * g
+    v = b2 * v + (1.0 - b2) * g * g
+    denom = v.sqrt() / math.sqrt(1.0 - b2 ** t) + eps
+    return p - (lr / (1.0 - b1 ** t)) * (m / denom), m, v

@@ -661,8 +661,15 @@ def test_adapters_mfma(device, kind, B, C, H, W):
 
 
 def test_adam_flat_matches_torch_adam(device):
-    """One-launch Adam over a flat buffer == torch.optim.Adam (reference defaults) step for step; the bf16 working
-    copy of the head of the buffer is the rounded master."""
+    """One-launch Adam over a flat buffer == torch.optim.Adam (reference defaults) step for step -- parameters and both
+    moments; the bf16 working copy of the head of the buffer is the rounded master.  The two fp32 evaluations carry their
+    own states, so the moments' differences add up over the steps: each evaluation adds at most the a-priori one-step error
+    of tests/test_adam_cpu.py -- 2 u (|m_prev| + |g|) to m (earlier differences shrink by b1), 6 u relative to v (all terms
+    positive: relative differences add).  On top of that the two do not use the same 1 - b: the C ABI carries b as fp32 and
+    the kernel forms 1 - fp32(b) (exact), torch rounds the double 1 - b to fp32; fp32(b)'s error u b, seen from 1 - b, is
+    u b / (1 - b): 9 u for b1, 999 u = 6e-5 for b2 (1.3e-5 in fact).  It scales every g^2 term of v alike, so it does not add
+    up over the steps, and it drops out of the update, whose bias correction uses the same fp32(b2) ("Optimizer
+    phase").  (tests/test_adam_gpu.py holds the kernel to float64 one step at a time.)"""
     from ppeadepth._abi import call, ptr, stream_ptr
     g = _g(5)
     n, n_lo = 10007, 4099
@@ -673,14 +680,19 @@ def test_adam_flat_matches_torch_adam(device):
     M, V = torch.zeros_like(P), torch.zeros_like(P)
     W16 = torch.empty(n_lo, device=device, dtype=torch.bfloat16)
     state = torch.tensor([0.0, 1e-3], device=device)
+    u, m_tol = 2.0 ** -24, 0.0
     for step in range(4):
         grad = (torch.randn(n, generator=g) * (10.0 ** (step - 2))).to(device)
         ref.grad = grad.clone()
         opt.step()
         state[0] += 1
+        m_tol += (2 * 2 + 0.1 * 9) * u * float(M.abs().max() + grad.abs().max())
         call("ppea_adam_flat_f32", ptr(P), ptr(grad), ptr(M), ptr(V), ptr(W16), n, n_lo, ptr(state), 0.9, 0.999, 1e-8,
              stream_ptr())
         assert (P - ref.detach()).abs().max() <= 2e-7 * ref.detach().abs().max() + 1e-9, step
+        st = opt.state[ref]
+        assert float((M - st["exp_avg"]).abs().max()) <= m_tol, step
+        assert bool(((V - st["exp_avg_sq"]).abs() <= ((step + 1) * 2 * 6 + 999) * u * st["exp_avg_sq"]).all()), step
     assert torch.equal(W16, P[:n_lo].bfloat16())
 
 
