@@ -531,6 +531,14 @@ int ppea_loss_tail_bwd_f32(const float* mask, const uint8_t* src, const float* o
  *        (deterministic; Cin % 8 == 0, Cout % 8 == 0).
  *   ppea_image_to_nhwc_bf16   fp32 NCHW frames -> bf16 channels-last, channels zero-padded to Cp (% 8 == 0),
  *        y = (x - sub) / div  (resnet_encoder.py:399 normalisation for the pose trunk; sub 0, div 1 for stem[0]).
+ *   ppea_conv_nhwc_plan / ppea_conv_wgrad_plan   host only, no device call, no stream: the kernel the two entry points
+ *        above launch for these shape arguments, decided by the function they launch by.
+ *        ppea_conv_nhwc_plan   plan[0..4] = NTC (conv3x3_resident_kernel<NTC, 1>; 0: the per-tile kernel), BN, RPS
+ *        (conv_nhwc_kernel<BN, ., ., stride, out_nchw, R, RPS>; 0 with NTC > 0), TR, TC (pixel tile).
+ *        ppea_conv_wgrad_plan  plan[0..11] = BM, BN, WK, splits, slabs, rows_per_block, rgroups, TR, TC, n_patches
+ *        (conv_wgrad_kernel<stride, R, BM, BN>), split_rule (what set `splits`: 0 two waves of workgroups, 1 the
+ *        workspace cap, 2 the floor min(two waves, 4) that a lower cap is raised to, 3 one workgroup per CU, 4 one patch per workgroup), tree_reduce (1: the
+ *        slab sum runs on the parallel reducer, 0: on the flat one).
  * ---------------------------------------------------------------------------------------- */
 long ppea_conv_packed_bytes(int Cout, int Cin, int R, int S, int flip);
 int ppea_conv_pack_weights(const void* w, int w_is_bf16, void* packed, int Cout, int Cin, int R, int S, int flip,
@@ -544,6 +552,9 @@ int ppea_conv_wgrad_nhwc_bf16(const void* dz, const void* x, void* dw, int dw_bf
                               int Ho, int Wo, void* stream);
 int ppea_image_to_nhwc_bf16(const float* x, void* y, int N, int C, int H, int W, int Cp, float sub, float div,
                             void* stream);
+int ppea_conv_nhwc_plan(int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int reflect, int dil,
+                        int Ho, int Wo, int out_nchw, int* plan);
+int ppea_conv_wgrad_plan(int N, int Cin, int Cout, int R, int S, int stride, int Ho, int Wo, int* plan);
 
 /* fp32 dense convolutions / linear layers on the fp32 matrix cores (csrc/conv_f32.hip, v_mfma_f32_32x32x2_f32): the
  * fp32 (parity, BASELINE config 1) step's replacement for every library convolution and GEMM behind

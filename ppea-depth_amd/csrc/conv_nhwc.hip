@@ -288,19 +288,15 @@ void pick_tile(ConvArgs& a, int stride, int ks, bool nchw) {
     a.tiles_x = (a.Wo + a.TC - 1) / a.TC; a.tiles_y = (a.Ho + a.TR - 1) / a.TR;
 }
 
+// What the host decided for one call: the persistent kernel (NTC > 0: conv3x3_resident_kernel<NTC, 1>) or the per-tile
+// kernel conv_nhwc_kernel<BN, ., ., stride, out_nchw, ks, RPS> on TR x TC tiles.  choose_conv() is the only place that
+// decides; ppea_conv_nhwc_bf16 launches what it returns and ppea_conv_nhwc_plan reports it.
+struct ConvPlan { int NTC, BN, RPS, TR, TC; };
+
 template <int BN, int WM, int WN, int STRIDE, bool NCHW, int KS, int RPS = 1>
 int launch_conv(const ConvArgs& a, hipStream_t st) {
     const int halo_px = ((a.TR - 1) * STRIDE + KS) * ((a.TC - 1) * STRIDE + KS);
     if (halo_px > halo_cap(STRIDE, KS)) return PPEA_ERR_UNSUPPORTED;
-    if constexpr (RPS == 1 && KS == 3 && BN <= 64) {
-        // Long contractions (>= 256 input channels): the whole 3 x 3 weight slice per step -- 2 barriers per 32-channel slice
-        // instead of 6; the waves of these layers were parked at barriers for 35-50 % of their cycles (PMC, round 2).
-        // 1024 -> 512 @6x20 forward 106 -> 59 us, @12x40 161 -> 107, ResNet 512 -> 512 55 -> 38 / data gradient 42 -> 29
-        // (profiles/r04_conv_layers_vs_library.txt).  With 64 / 128 input channels the 36 KB weight image per 12-17 KB
-        // halo costs occupancy and loses (64 -> 64 @96x320: 74 -> 95 us): those keep one filter row per step.
-        static const bool one_row = getenv("PPEA_CONV_RPS") != nullptr && getenv("PPEA_CONV_RPS")[0] == '1';
-        if (!one_row && a.CinP >= 256) return launch_conv<BN, WM, WN, STRIDE, NCHW, KS, KS>(a, st);
-    }
     const size_t smem = (size_t)((halo_px * PITCH + 127) / 128) * 128 + (size_t)RPS * KS * BN * PITCH;
     if (smem > 160 * 1024) return PPEA_ERR_UNSUPPORTED;
     auto kern = conv_nhwc_kernel<BN, WM, WN, STRIDE, NCHW, KS, RPS>;
@@ -313,29 +309,34 @@ int launch_conv(const ConvArgs& a, hipStream_t st) {
     return launch_status();
 }
 
-template <int STRIDE, bool NCHW, int KS>
-int dispatch_bn(const ConvArgs& a, hipStream_t st) {
-    const long tiles = (long)a.tiles_x * a.tiles_y * a.N;
-    if constexpr (KS <= 3) {
-        // 128 channels per workgroup only when that still leaves two waves of workgroups for the 256 CUs
-        // (3 x 3 with >= 256 input channels: 64 channels per workgroup with the whole weight slice per step is faster than
-        // 128 with one filter row per step -- 256 -> 128 @48x160 forward 105 -> 97 us; launch_conv)
-        if (a.Cout > 64 && tiles * ((a.Cout + 127) / 128) >= 512 && !(KS == 3 && a.CinP >= 256))
-            return launch_conv<128, 2, 2, STRIDE, NCHW, KS>(a, st);
+// filter rows per step: the whole 3 x 3 slice exists for BN <= 64 only (choose_conv never asks for it elsewhere)
+template <int BN, int WM, int WN, int STRIDE, bool NCHW, int KS>
+int launch_rps(const ConvArgs& a, int rps, hipStream_t st) {
+    if constexpr (KS == 3 && BN <= 64) {
+        if (rps == KS) return launch_conv<BN, WM, WN, STRIDE, NCHW, KS, KS>(a, st);
     }
-    // 64 channels per workgroup unless that leaves CUs without one (small maps, e.g. 1024 -> 512 @6x20: 96 workgroups)
-    static const bool no_narrow = getenv("PPEA_CONV_NO_NARROW") != nullptr;           // tuning hook (tools/bench_conv.py)
-    if (a.Cout > 32 && (no_narrow || tiles * ((a.Cout + 63) / 64) >= 256)) return launch_conv<64, 2, 2, STRIDE, NCHW, KS>(a, st);
-    return launch_conv<32, 4, 1, STRIDE, NCHW, KS>(a, st);
+    if (rps != 1) return PPEA_ERR_UNSUPPORTED;
+    return launch_conv<BN, WM, WN, STRIDE, NCHW, KS>(a, st);
+}
+
+template <int STRIDE, bool NCHW, int KS>
+int launch_bn(const ConvArgs& a, const ConvPlan& p, hipStream_t st) {
+    switch (p.BN) {
+        case 128:
+            if constexpr (KS <= 3) return launch_rps<128, 2, 2, STRIDE, NCHW, KS>(a, p.RPS, st);
+            break;
+        case 64: return launch_rps<64, 2, 2, STRIDE, NCHW, KS>(a, p.RPS, st);
+        case 32: return launch_rps<32, 4, 1, STRIDE, NCHW, KS>(a, p.RPS, st);
+    }
+    return PPEA_ERR_UNSUPPORTED;
 }
 
 template <int STRIDE, bool NCHW>
-int dispatch_conv(ConvArgs& a, int ks, hipStream_t st) {
-    pick_tile(a, STRIDE, ks, NCHW);
+int launch_ks(const ConvArgs& a, int ks, const ConvPlan& p, hipStream_t st) {
     switch (ks) {
-        case 1: return dispatch_bn<STRIDE, NCHW, 1>(a, st);
-        case 3: return dispatch_bn<STRIDE, NCHW, 3>(a, st);
-        case 7: return dispatch_bn<STRIDE, NCHW, 7>(a, st);
+        case 1: return launch_bn<STRIDE, NCHW, 1>(a, p, st);
+        case 3: return launch_bn<STRIDE, NCHW, 3>(a, p, st);
+        case 7: return launch_bn<STRIDE, NCHW, 7>(a, p, st);
     }
     return PPEA_ERR_UNSUPPORTED;
 }
@@ -550,13 +551,60 @@ bool resident_ok(const ConvArgs& a, int ks, int out_nchw) {
            (long)a.N * a.H * a.W * a.Cin * 2 < (1L << 31);
 }
 
-int dispatch_resident(const ConvArgs& a, hipStream_t st) {
-    switch ((a.Cout + 15) / 16) {
+int launch_resident_ntc(const ConvArgs& a, int ntc, hipStream_t st) {
+    switch (ntc) {
         case 1: return launch_resident<1, 1>(a, st);
         case 2: return launch_resident<2, 1>(a, st);
-        case 3: case 4: return launch_resident<4, 1>(a, st);
+        case 4: return launch_resident<4, 1>(a, st);
     }
     return PPEA_ERR_UNSUPPORTED;
+}
+
+// The one decision: which kernel serves `a` (stride in {1, 2}, ks in {1, 3, 7}) and on which tile.  Fills the tile fields
+// of `a` for the per-tile kernel (the persistent one has its own fixed 8 x 16).  Host arithmetic only.
+ConvPlan choose_conv(ConvArgs& a, int ks, int out_nchw) {
+    ConvPlan p = {0, 0, 0, 8, 16};
+    static const bool no_resident = getenv("PPEA_CONV_NO_RESIDENT") != nullptr;        // tuning hook (tools/bench_conv.py)
+    if (!no_resident && resident_ok(a, ks, out_nchw)) {
+        const int ct = (a.Cout + 15) / 16;                     // 16-channel column tiles: 1, 2, or 3 / 4 on the 4
+        p.NTC = ct <= 2 ? ct : 4;
+        return p;
+    }
+    pick_tile(a, a.stride, ks, out_nchw != 0);
+    p.TR = a.TR; p.TC = a.TC;
+    const long tiles = (long)a.tiles_x * a.tiles_y * a.N;
+    // 128 channels per workgroup only when that still leaves two waves of workgroups for the 256 CUs
+    // (3 x 3 with >= 256 input channels: 64 channels per workgroup with the whole weight slice per step is faster than
+    // 128 with one filter row per step -- 256 -> 128 @48x160 forward 105 -> 97 us)
+    // 64 channels per workgroup unless that leaves CUs without one (small maps, e.g. 1024 -> 512 @6x20: 96 workgroups)
+    static const bool no_narrow = getenv("PPEA_CONV_NO_NARROW") != nullptr;           // tuning hook (tools/bench_conv.py)
+    if (ks <= 3 && a.Cout > 64 && tiles * ((a.Cout + 127) / 128) >= 512 && !(ks == 3 && a.CinP >= 256)) p.BN = 128;
+    else if (a.Cout > 32 && (no_narrow || tiles * ((a.Cout + 63) / 64) >= 256)) p.BN = 64;
+    else p.BN = 32;
+    // Long contractions (>= 256 input channels): the whole 3 x 3 weight slice per step -- 2 barriers per 32-channel slice
+    // instead of 6; the waves of these layers were parked at barriers for 35-50 % of their cycles (PMC, round 2).
+    // 1024 -> 512 @6x20 forward 106 -> 59 us, @12x40 161 -> 107, ResNet 512 -> 512 55 -> 38 / data gradient 42 -> 29
+    // (profiles/r04_conv_layers_vs_library.txt).  With 64 / 128 input channels the 36 KB weight image per 12-17 KB
+    // halo costs occupancy and loses (64 -> 64 @96x320: 74 -> 95 us): those keep one filter row per step.
+    static const bool one_row = getenv("PPEA_CONV_RPS") != nullptr && getenv("PPEA_CONV_RPS")[0] == '1';
+    p.RPS = (ks == 3 && p.BN <= 64 && !one_row && a.CinP >= 256) ? 3 : 1;
+    return p;
+}
+
+// argument checks of ppea_conv_nhwc_bf16 / ppea_conv_nhwc_plan and the shape half of ConvArgs
+int conv_shape_args(ConvArgs& a, int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int reflect,
+                    int dil, int Ho, int Wo) {
+    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0) return PPEA_ERR_ARG;
+    if ((Cin % 8) != 0 || R != S || (R != 1 && R != 3 && R != 7) || (stride != 1 && stride != 2) || dil < 1 || pad < 0)
+        return PPEA_ERR_UNSUPPORTED;
+    if (reflect && (pad > 1 || dil != 1 || H < 2 || W < 2)) return PPEA_ERR_UNSUPPORTED;
+    if ((long)H * W * Cin >= (1L << 31)) return PPEA_ERR_UNSUPPORTED;
+    a.x = nullptr; a.w = nullptr; a.bias = nullptr; a.y = nullptr;
+    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = (Cin + 31) / 32 * 32; a.Cout = Cout;
+    a.stride = stride; a.pad = pad; a.reflect = reflect; a.dil = dil; a.Ho = Ho; a.Wo = Wo; a.act = 0;
+    a.bias_bf16 = 0;
+    a.TR = 8; a.TC = 16; a.tiles_x = (Wo + 15) / 16; a.tiles_y = (Ho + 7) / 8;
+    return 0;
 }
 
 // weights [Cout][Cin][R][S] (bf16 or fp32) -> packed bf16 [R*S][Cout][CinP]  (flip = 0)
@@ -634,21 +682,30 @@ int ppea_image_to_nhwc_bf16(const float* x, void* y, int N, int C, int H, int W,
 int ppea_conv_nhwc_bf16(const void* x, const void* w_packed, const void* bias, int bias_bf16, void* y, int N, int H, int W,
                         int Cin, int Cout, int R, int S, int stride, int pad, int reflect, int dil, int Ho, int Wo, int act,
                         int out_nchw, void* stream) {
-    if (N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0) return PPEA_ERR_ARG;
-    if ((Cin % 8) != 0 || R != S || (R != 1 && R != 3 && R != 7) || (stride != 1 && stride != 2) || dil < 1 || pad < 0)
-        return PPEA_ERR_UNSUPPORTED;
-    if (reflect && (pad > 1 || dil != 1 || H < 2 || W < 2)) return PPEA_ERR_UNSUPPORTED;
-    if ((long)H * W * Cin >= (1L << 31)) return PPEA_ERR_UNSUPPORTED;
     ConvArgs a;
+    const int err = conv_shape_args(a, N, H, W, Cin, Cout, R, S, stride, pad, reflect, dil, Ho, Wo);
+    if (err) return err;
     a.x = (const uint16_t*)x; a.w = (const uint16_t*)w_packed; a.bias = bias; a.y = (uint16_t*)y;
-    a.N = N; a.H = H; a.W = W; a.Cin = Cin; a.CinP = (Cin + 31) / 32 * 32; a.Cout = Cout;
-    a.stride = stride; a.pad = pad; a.reflect = reflect; a.dil = dil; a.Ho = Ho; a.Wo = Wo; a.act = act;
-    a.bias_bf16 = bias_bf16;
+    a.act = act; a.bias_bf16 = bias_bf16;
     hipStream_t st = (hipStream_t)stream;
-    static const bool no_resident = getenv("PPEA_CONV_NO_RESIDENT") != nullptr;        // tuning hook (tools/bench_conv.py)
-    if (!no_resident && resident_ok(a, R, out_nchw)) return dispatch_resident(a, st);
-    if (stride == 1) return out_nchw ? dispatch_conv<1, true>(a, R, st) : dispatch_conv<1, false>(a, R, st);
-    return out_nchw ? dispatch_conv<2, true>(a, R, st) : dispatch_conv<2, false>(a, R, st);
+    const ConvPlan p = choose_conv(a, R, out_nchw);
+    if (p.NTC > 0) return launch_resident_ntc(a, p.NTC, st);
+    if (stride == 1) return out_nchw ? launch_ks<1, true>(a, R, p, st) : launch_ks<1, false>(a, R, p, st);
+    return out_nchw ? launch_ks<2, true>(a, R, p, st) : launch_ks<2, false>(a, R, p, st);
+}
+
+// The kernel ppea_conv_nhwc_bf16 launches for these arguments, from the function it launches by (no device call):
+// plan[0] = NTC of conv3x3_resident_kernel<NTC, 1> (0: the per-tile kernel), plan[1] = BN and plan[2] = RPS of
+// conv_nhwc_kernel<BN, ., ., stride, out_nchw, R, RPS> (0 with NTC > 0), plan[3], plan[4] = TR, TC of the pixel tile.
+int ppea_conv_nhwc_plan(int N, int H, int W, int Cin, int Cout, int R, int S, int stride, int pad, int reflect, int dil,
+                        int Ho, int Wo, int out_nchw, int* plan) {
+    if (!plan) return PPEA_ERR_ARG;
+    ConvArgs a;
+    const int err = conv_shape_args(a, N, H, W, Cin, Cout, R, S, stride, pad, reflect, dil, Ho, Wo);
+    if (err) return err;
+    const ConvPlan p = choose_conv(a, R, out_nchw);
+    plan[0] = p.NTC; plan[1] = p.BN; plan[2] = p.RPS; plan[3] = p.TR; plan[4] = p.TC;
+    return 0;
 }
 
 }  // extern "C"

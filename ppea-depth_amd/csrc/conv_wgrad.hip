@@ -306,7 +306,12 @@ __global__ void conv_wgrad_reduce_flat_kernel(const float* __restrict__ ws, void
     }
 }
 
-struct WgPlan { int BM, BN, WK, splits, slabs, rows_per_block, rgroups, CoutP, CinP, n_patches, TR, TC, tiles_x, tiles_y; long ws_bytes; };
+// split_rule: which clause of plan() set `splits`; tree_reduce: the slab sum runs on conv_wgrad_reduce_kernel (else the flat one)
+enum { SPLIT_WANT = 0, SPLIT_CAP = 1, SPLIT_FLOOR = 2, SPLIT_FILL = 3, SPLIT_PATCHES = 4 };
+struct WgPlan {
+    int BM, BN, WK, splits, slabs, rows_per_block, rgroups, CoutP, CinP, n_patches, TR, TC, tiles_x, tiles_y, split_rule, tree_reduce;
+    long ws_bytes;
+};
 
 WgPlan plan(int N, int Cin, int Cout, int K, int stride, int Ho, int Wo) {
     WgPlan p;
@@ -334,7 +339,8 @@ WgPlan plan(int N, int Cin, int Cout, int K, int stride, int Ho, int Wo) {
     long splits = (512 + tiles - 1) / tiles;                         // two waves of workgroups on 256 CUs
     const long want = splits;
     const long cap = (32L << 20) / (per_slab * p.WK);                // workspace <= 32 MB, or up to 4/3 of that (42.7 MB) ...
-    if (splits > cap) splits = cap;
+    p.split_rule = SPLIT_WANT;
+    if (splits > cap) { splits = cap; p.split_rule = SPLIT_CAP; }
     // ... except that a layer never runs as fewer workgroups than CUs for want of workspace: 1024 -> 512 (19 MB per slab,
     // 128 tiles) ran as 128 workgroups walking 48 patches each -- 307 us against the library's 153; with 4 splits 184 us.
     // (More slabs everywhere -- a 128 MB cap -- was a net loss: every slab is a full-size fp32 gradient written and re-read.)
@@ -343,12 +349,18 @@ WgPlan plan(int N, int Cin, int Cout, int K, int stride, int Ho, int Wo) {
     // slabs are reduced by the flat kernel -- tests/test_kernels_gpu.py CONV_CASES wgrad_512_256_fill / wgrad_256_128_fill)
     long floor_splits = want < 4 ? want : 4;
     const long fill = (256 + tiles - 1) / tiles;
-    if (fill <= want && fill > floor_splits && fill * 3 <= cap * 4) floor_splits = fill;
-    if (splits < floor_splits) splits = floor_splits;
-    if (splits > p.n_patches) splits = p.n_patches;
+    bool filled = false;
+    if (fill <= want && fill > floor_splits && fill * 3 <= cap * 4) { floor_splits = fill; filled = true; }
+    if (splits < floor_splits) {
+        splits = floor_splits;
+        // FLOOR names the clause, not the value: with want < 4 the floor is `want` itself, reached against the cap
+        p.split_rule = filled ? SPLIT_FILL : SPLIT_FLOOR;
+    }
+    if (splits > p.n_patches) { splits = p.n_patches; p.split_rule = SPLIT_PATCHES; }
     if (splits < 1) splits = 1;
     p.splits = (int)splits;
     p.slabs = p.splits * p.WK;
+    p.tree_reduce = p.slabs > 16;      // many slabs (small-channel layers): the sum over slabs is parallel as well
     p.ws_bytes = per_slab * p.slabs;
     return p;
 }
@@ -360,6 +372,21 @@ extern "C" {
 long ppea_conv_wgrad_workspace_bytes(int N, int Cin, int Cout, int R, int S, int stride, int Ho, int Wo) {
     if (R != S) return 0;
     return plan(N, Cin, Cout, R, stride, Ho, Wo).ws_bytes;
+}
+
+// The plan ppea_conv_wgrad_nhwc_bf16 launches by (the same plan(); no device call): conv_wgrad_kernel<stride, R, BM, BN>,
+// out[0..11] = BM, BN, WK, splits, slabs, rows_per_block, rgroups, TR, TC, n_patches, split_rule (0 want: two waves of
+// workgroups, 1 cap: the workspace cap, 2 floor: the floor min(want, 4) that a lower cap is raised to, 3 fill: one workgroup per CU, 4 patches:
+// one patch per workgroup), tree_reduce (1: conv_wgrad_reduce_kernel, 0: the flat reducer).
+int ppea_conv_wgrad_plan(int N, int Cin, int Cout, int R, int S, int stride, int Ho, int Wo, int* out) {
+    if (N <= 0 || Cin <= 0 || Cout <= 0 || Ho <= 0 || Wo <= 0 || !out) return PPEA_ERR_ARG;
+    if ((Cin % 8) != 0 || (Cout % 8) != 0 || R != S || (R != 1 && R != 3 && R != 7) || (stride != 1 && stride != 2))
+        return PPEA_ERR_UNSUPPORTED;
+    const WgPlan p = plan(N, Cin, Cout, R, stride, Ho, Wo);
+    const int v[12] = {p.BM, p.BN, p.WK, p.splits, p.slabs, p.rows_per_block, p.rgroups, p.TR, p.TC, p.n_patches,
+                       p.split_rule, p.tree_reduce};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return 0;
 }
 
 // dz [N][Ho][Wo][Cout], x [N][H][W][Cin] channels-last bf16 (Cin % 8 == 0, Cout % 8 == 0); dw [Cout][Cin][R][S] fp32 or
@@ -405,7 +432,7 @@ int ppea_conv_wgrad_nhwc_bf16(const void* dz, const void* x, void* dw, int dw_bf
     int err = launch_status();
     if (err) return err;
     const long total = (long)Cout * Cin * R * S;
-    if (p.slabs > 16) {
+    if (p.tree_reduce) {
         hipLaunchKernelGGL(conv_wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64, 16), 0, st,
                            (const float*)workspace, dw, dw_bf16, p.slabs, R * S, Cout, Cin, p.CoutP, p.CinP);
     } else {

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -159,6 +159,8 @@ SIGNATURES = {
     "ppea_conv_nhwc_bf16": [_vp, _vp, _vp, _i, _vp] + [_i] * 15 + [_vp],
     "ppea_conv_wgrad_workspace_bytes": [_i] * 8,
     "ppea_conv_wgrad_nhwc_bf16": [_vp, _vp, _vp, _i, _vp] + [_i] * 12 + [_vp],
+    "ppea_conv_nhwc_plan": [_i] * 14 + [_vp],
+    "ppea_conv_wgrad_plan": [_i] * 8 + [_vp],
     "ppea_nhwc_up2cat_fwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ppea_nhwc_up2cat_fwd_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ppea_nhwc_up2cat_bwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],

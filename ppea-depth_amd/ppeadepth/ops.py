@@ -2385,10 +2385,16 @@ def upsample2x_cat(a, b=None):
     return _Up2Cat.apply(a, b)
 
 
-def conv_nhwc_raw(x, wp, bias, Cout, R, S, stride, pad, reflect, dil, Ho, Wo, act, out_nchw):
-    """One launch of the implicit-GEMM kernel.  x: bf16, channels_last storage, logical [N,Cin,H,W]."""
+def conv_nhwc_raw(x, wp, bias, Cout, R, S, stride, pad, reflect, dil, Ho, Wo, act, out_nchw, out=None):
+    """One launch of the implicit-GEMM kernel.  x: bf16, channels_last storage, logical [N,Cin,H,W].  `out`: the result's
+    storage, a dense bf16 [N,Cout,Ho,Wo] tensor of the layout `out_nchw` names (default: a fresh one)."""
     N, Cin, H, W = x.shape
-    if out_nchw:
+    if out is not None:
+        fmt = torch.contiguous_format if out_nchw else torch.channels_last
+        if not (out.is_cuda and out.dtype == _BF16 and tuple(out.shape) == (N, Cout, Ho, Wo) and out.is_contiguous(memory_format=fmt)):
+            raise PpeaKernelError("conv_nhwc_raw: `out` must be a dense bf16 [N,Cout,Ho,Wo] tensor of the requested layout")
+        y = out
+    elif out_nchw:
         y = torch.empty(N, Cout, Ho, Wo, device=x.device, dtype=_BF16)
     else:
         y = torch.empty(N, Cout, Ho, Wo, device=x.device, dtype=_BF16, memory_format=torch.channels_last)
@@ -2396,6 +2402,28 @@ def conv_nhwc_raw(x, wp, bias, Cout, R, S, stride, pad, reflect, dil, Ho, Wo, ac
     call("ppea_conv_nhwc_bf16", _nhwc_raw(x), ptr(wp), bp, bflag, _nhwc_raw(y), N, H, W, Cin, Cout, R, S, stride, pad,
          int(reflect), dil, Ho, Wo, act, int(out_nchw), stream_ptr())
     return y
+
+
+WGRAD_SPLIT_RULES = ("want", "cap", "floor", "fill", "patches")
+
+
+def conv_nhwc_plan(N, H, W, Cin, Cout, K, stride, pad, reflect, dil, Ho, Wo, out_nchw):
+    """The kernel ppea_conv_nhwc_bf16 launches for these arguments (host only, works without a device):
+    dict(NTC, BN, RPS, TR, TC) -- NTC > 0: the persistent kernel, else conv_nhwc_kernel<BN, ., ., stride, out_nchw, K, RPS>."""
+    out = (_ct.c_int * 5)()
+    call("ppea_conv_nhwc_plan", N, H, W, Cin, Cout, K, K, stride, pad, int(reflect), dil, Ho, Wo, int(out_nchw), out)
+    return dict(zip(("NTC", "BN", "RPS", "TR", "TC"), out))
+
+
+def conv_wgrad_plan(N, Cin, Cout, K, stride, Ho, Wo):
+    """The plan ppea_conv_wgrad_nhwc_bf16 launches by (host only): conv_wgrad_kernel<stride, K, BM, BN>, its split over
+    output patches, what set it (`split_rule`, one of WGRAD_SPLIT_RULES) and the slab reducer."""
+    out = (_ct.c_int * 12)()
+    call("ppea_conv_wgrad_plan", N, Cin, Cout, K, K, stride, Ho, Wo, out)
+    p = dict(zip(("BM", "BN", "WK", "splits", "slabs", "rows_per_block", "rgroups", "TR", "TC", "n_patches", "split_rule",
+                  "tree_reduce"), out))
+    p["split_rule"] = WGRAD_SPLIT_RULES[p["split_rule"]]
+    return p
 
 
 def conv_supported(x, w):

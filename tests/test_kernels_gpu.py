@@ -1047,8 +1047,9 @@ CONV_CASES = [
 def test_conv2d_nhwc_mfma(device, case):
     """Forward, data gradient, weight gradient and bias gradient of the implicit-GEMM convolution kernels against a
     plain fp32 PyTorch reference of the same op on the same bf16-rounded operands (reflection / zero padding, stride
-    1 / 2, 1x1 / 3x3 / 7x7, fused bias + ReLU / ELU / sigmoid, channels_last and NCHW outputs, ragged sizes).
-    Tolerance: fp32 accumulation on both sides, ONE bf16 rounding of every output element -> 2^-7 of the tensor's max."""
+    1 / 2, 1x1 / 3x3 / 7x7, fused bias + ReLU / ELU / sigmoid, channels_last and NCHW outputs, ragged sizes) at the layer
+    shapes of the step, one max-norm figure per tensor.  The per-element bound, the float64 reference and a row for every
+    instantiation and plan outcome of these kernels are in tests/test_conv_arms_gpu.py (tables: oracle/conv_inputs.py)."""
     import torch.nn.functional as F
     from ppeadepth import ops
     name, N, Cin, H, W, Cout, k, stride, pad, reflect, act, has_bias, nchw = case
