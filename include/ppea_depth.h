@@ -491,6 +491,15 @@ int ppea_loss_select_f32(const float* reproj, const float* identity, const float
                          const float* warped_p1, const float* noise, float* sel,
                          uint8_t* src_idx, int64_t* frame_idx, int64_t* auto_idx,
                          int B, int C, int H, int W, int selec_reproj, void* stream);
+/* The same for S source frames, S in {1, 2}: reproj, identity [B,S,H,W].  S = 2 is ppea_loss_select_f32 bit for bit
+ * (warped_0 / warped_1 = warped_m1 / warped_p1, read for selec_reproj only and NULL otherwise).  S = 1 (frame_ids [0, -1],
+ * the two-frame items of DDAD): sel is the only channel, src_idx = 0 and frame_idx = 0 everywhere, the identity minimum is
+ * the only identity channel (+ noise), auto_idx by the same first-minimum / NaN rule; no warped frame is read, and
+ * selec_reproj != 0 is PPEA_ERR_UNSUPPORTED (the reference reads the warped frame +1 there, trainer.py:1077-1083). */
+int ppea_loss_select_n_f32(const float* reproj, const float* identity, const float* warped_0,
+                           const float* warped_1, const float* noise, float* sel,
+                           uint8_t* src_idx, int64_t* frame_idx, int64_t* auto_idx,
+                           int B, int S, int C, int H, int W, int selec_reproj, void* stream);
 
 /* Tail of compute_losses (trainer.py:1092-1139) after the per-pixel selection: mask (automask argmin == 0, or for the
  * multi-frame pass consistency_mask * (1 - augmentation_mask)), rl = sum(sel * mask) / (sum(mask) + 1e-7), and for the
@@ -506,6 +515,11 @@ int ppea_loss_tail_fwd_f32(const float* sel, const int64_t* auto_idx, const floa
 int ppea_loss_tail_bwd_f32(const float* mask, const uint8_t* src, const float* out, const float* g_rl, const float* g_con,
                            const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int H, int W,
                            void* stream);
+/* The backward for S source frames, S in {1, 2}: d_reproj [B][S][H][W]; S = 2 is ppea_loss_tail_bwd_f32 (the forward does
+ * not see the frames: it reads the selected loss). */
+int ppea_loss_tail_bwd_n_f32(const float* mask, const uint8_t* src, const float* out, const float* g_rl, const float* g_con,
+                             const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int S, int H,
+                             int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A12 / A14  Dense convolutions as implicit GEMMs on the matrix cores (csrc/conv_nhwc.hip, conv_wgrad.hip):

@@ -259,6 +259,9 @@ __global__ __launch_bounds__(256) void smooth_bwd(const float* __restrict__ disp
 }
 
 // ---- per-pixel selection ---------------------------------------------------------------------
+// S source frames (S = 2: frames -1 and +1; S = 1: frame -1 alone, the two-frame items of DDAD).  With one frame the minimum
+// over the frames is that frame: frame_idx = 0, src = 0, and selec_reproj (which trades one frame for the other) is undefined.
+template <int S>
 __global__ __launch_bounds__(256) void loss_select(const float* __restrict__ reproj,
                                                    const float* __restrict__ identity,
                                                    const float* __restrict__ wm1,
@@ -268,16 +271,17 @@ __global__ __launch_bounds__(256) void loss_select(const float* __restrict__ rep
                                                    int64_t* __restrict__ frame_idx,
                                                    int64_t* __restrict__ auto_idx, int B, int C, int H,
                                                    int W, int selec) {
+    static_assert(S == 1 || S == 2, "one or two source frames");
     const long hw = (long)H * W;
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= (long)B * hw) return;
     const long b = i / hw, p = i - b * hw;
-    const float r0 = reproj[b * 2 * hw + p], r1 = reproj[b * 2 * hw + hw + p];
+    const float r0 = reproj[b * S * hw + p], r1 = S == 2 ? reproj[b * S * hw + hw + p] : r0;
     // torch.min over dim=1: first minimum wins; NaN propagates (treated as smaller)
-    int fi = (r1 < r0 || (r1 != r1 && r0 == r0)) ? 1 : 0;
+    int fi = (S == 2 && (r1 < r0 || (r1 != r1 && r0 == r0))) ? 1 : 0;
     float v = fi ? r1 : r0;
     int si = fi;
-    if (selec) {
+    if (S == 2 && selec) {
         float s0 = 0.f, s1 = 0.f;
         for (int c = 0; c < C; ++c) {
             s0 += wm1[(b * C + c) * hw + p];
@@ -288,8 +292,8 @@ __global__ __launch_bounds__(256) void loss_select(const float* __restrict__ rep
         if (m1) { v = r0; si = 0; }
         if (m0 && m1) { v = 0.f; si = 2; }
     }
-    const float i0 = identity[b * 2 * hw + p], i1 = identity[b * 2 * hw + hw + p];
-    float idm = (i1 < i0 || (i1 != i1 && i0 == i0)) ? i1 : i0;
+    const float i0 = identity[b * S * hw + p], i1 = S == 2 ? identity[b * S * hw + hw + p] : i0;
+    float idm = (S == 2 && (i1 < i0 || (i1 != i1 && i0 == i0))) ? i1 : i0;
     if (noise != nullptr) idm += noise[i];
     sel[i] = v;
     src_idx[i] = (uint8_t)si;
@@ -371,8 +375,9 @@ __global__ __launch_bounds__(256) void loss_tail_finalize(const float* __restric
     }
 }
 
-// d_reproj[b][c][p] = g_rl * mask * inv_den if src[b][p] == c else 0 (c = 0, 1; src == 2: the selection forced zero);
+// d_reproj[b][c][p] = g_rl * mask * inv_den if src[b][p] == c else 0 (c < S; src == 2: the selection forced zero);
 // d_multi = g_con * sign(multi - mono) * (1 - mask) / total
+template <int S>
 __global__ __launch_bounds__(256) void loss_tail_bwd(const float* __restrict__ mask, const uint8_t* __restrict__ src,
                                                      const float* __restrict__ out, const float* __restrict__ g_rl,
                                                      const float* __restrict__ g_con, const float* __restrict__ multi,
@@ -385,8 +390,8 @@ __global__ __launch_bounds__(256) void loss_tail_bwd(const float* __restrict__ m
         const float g = (g_rl != nullptr ? g_rl[0] : 0.f) * m * out[2];
         const long b = i / hw, p = i - b * hw;
         const int sidx = src[i];
-        d_reproj[b * 2 * hw + p] = sidx == 0 ? g : 0.f;
-        d_reproj[b * 2 * hw + hw + p] = sidx == 1 ? g : 0.f;
+#pragma unroll
+        for (int c = 0; c < S; ++c) d_reproj[b * S * hw + c * hw + p] = sidx == c ? g : 0.f;
     }
     if (d_multi != nullptr) {
         const float d = multi[i] - mono[i];
@@ -439,13 +444,31 @@ int ppea_smooth_bwd_f32(const float* disp, const float* img, float gx, float gy,
     return launch_status();
 }
 
+// S source frames: reproj / identity [B][S][H][W]; warped_0 / warped_1 [B][C][H][W] are read for selec_reproj only (S = 2).
+int ppea_loss_select_n_f32(const float* reproj, const float* identity, const float* warped_0, const float* warped_1,
+                           const float* noise, float* sel, uint8_t* src_idx, int64_t* frame_idx, int64_t* auto_idx,
+                           int B, int S, int C, int H, int W, int selec_reproj, void* stream) {
+    if (B <= 0 || H <= 0 || W <= 0 || (S != 1 && S != 2)) return PPEA_ERR_UNSUPPORTED;
+    if (selec_reproj && S == 1) return PPEA_ERR_UNSUPPORTED;        // one frame has no other frame to fall back on
+    if (selec_reproj && (C <= 0 || warped_0 == nullptr || warped_1 == nullptr)) return PPEA_ERR_ARG;
+    const long total = (long)B * H * W;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (S == 2)
+        hipLaunchKernelGGL(loss_select<2>, grid, dim3(256), 0, (hipStream_t)stream, reproj, identity, warped_0, warped_1,
+                           noise, sel, src_idx, frame_idx, auto_idx, B, C, H, W, selec_reproj);
+    else
+        hipLaunchKernelGGL(loss_select<1>, grid, dim3(256), 0, (hipStream_t)stream, reproj, identity, warped_0, warped_1,
+                           noise, sel, src_idx, frame_idx, auto_idx, B, C, H, W, 0);
+    return launch_status();
+}
+
 int ppea_loss_select_f32(const float* reproj, const float* identity, const float* warped_m1,
                          const float* warped_p1, const float* noise, float* sel, uint8_t* src_idx,
                          int64_t* frame_idx, int64_t* auto_idx, int B, int C, int H, int W, int selec_reproj,
                          void* stream) {
     if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return PPEA_ERR_UNSUPPORTED;
     const long total = (long)B * H * W;
-    hipLaunchKernelGGL(loss_select, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(loss_select<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        reproj, identity, warped_m1, warped_p1, noise, sel, src_idx, frame_idx, auto_idx, B, C,
                        H, W, selec_reproj);
     return launch_status();
@@ -468,14 +491,24 @@ int ppea_loss_tail_fwd_f32(const float* sel, const int64_t* auto_idx, const floa
     hipLaunchKernelGGL(loss_tail_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nblk, total, out);
     return launch_status();
 }
+int ppea_loss_tail_bwd_n_f32(const float* mask, const uint8_t* src, const float* out, const float* g_rl, const float* g_con,
+                             const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int S, int H,
+                             int W, void* stream) {
+    if (B <= 0 || H <= 0 || W <= 0 || (S != 1 && S != 2)) return PPEA_ERR_UNSUPPORTED;
+    const long hw = (long)H * W, total = (long)B * hw;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (S == 2)
+        hipLaunchKernelGGL(loss_tail_bwd<2>, grid, dim3(256), 0, (hipStream_t)stream, mask, src, out, g_rl, g_con, multi,
+                           mono, d_reproj, d_multi, hw, total);
+    else
+        hipLaunchKernelGGL(loss_tail_bwd<1>, grid, dim3(256), 0, (hipStream_t)stream, mask, src, out, g_rl, g_con, multi,
+                           mono, d_reproj, d_multi, hw, total);
+    return launch_status();
+}
 int ppea_loss_tail_bwd_f32(const float* mask, const uint8_t* src, const float* out, const float* g_rl, const float* g_con,
                            const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int H, int W,
                            void* stream) {
-    if (B <= 0 || H <= 0 || W <= 0) return PPEA_ERR_UNSUPPORTED;
-    const long hw = (long)H * W, total = (long)B * hw;
-    hipLaunchKernelGGL(loss_tail_bwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, mask, src, out,
-                       g_rl, g_con, multi, mono, d_reproj, d_multi, hw, total);
-    return launch_status();
+    return ppea_loss_tail_bwd_n_f32(mask, src, out, g_rl, g_con, multi, mono, d_reproj, d_multi, B, 2, H, W, stream);
 }
 
 }  // extern "C"

@@ -132,6 +132,7 @@ SIGNATURES = {
     "ppea_smooth_fwd_f32": [_vp] * 3 + [_i] * 4 + [_vp],
     "ppea_smooth_bwd_f32": [_vp, _vp, _f, _f, _vp] + [_i] * 4 + [_vp],
     "ppea_loss_select_f32": [_vp] * 9 + [_i] * 5 + [_vp],
+    "ppea_loss_select_n_f32": [_vp] * 9 + [_i] * 6 + [_vp],
     "ppea_bn_fwd_channel_f32": [_vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
     "ppea_bn_fwd_channel_bf16": [_vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
     "ppea_bn_fwd_channel_sums_f32": [_vp, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
@@ -184,6 +185,7 @@ SIGNATURES = {
     "ppea_loss_tail_blocks": [_l],
     "ppea_loss_tail_fwd_f32": [_vp] * 10 + [_i] * 4 + [_vp],
     "ppea_loss_tail_bwd_f32": [_vp] * 9 + [_i] * 3 + [_vp],
+    "ppea_loss_tail_bwd_n_f32": [_vp] * 9 + [_i] * 4 + [_vp],
     "ppea_cost_volume_reduce_f32": [_vp] * 6 + [_i] * 4 + [_vp],
     "ppea_cost_volume_multi_fwd_f32": [_vp] * 7 + [_i] * 6 + [_f, _vp],
     "ppea_cost_volume_multi_fwd_bf16": [_vp] * 8 + [_i] * 6 + [_f, _vp],

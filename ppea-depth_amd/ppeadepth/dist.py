@@ -493,9 +493,11 @@ class TrainEngine:
         if module.pose_plan() is None:
             # the captured step's stream plan keeps ALL pose work (gradient passes, replays, the new no_grad passes and the
             # pose chain) on the adapter side stream, joined once where the cost volume asks for the relative poses: that is
-            # the batched pose path (repdepth.pose_pair_plan); the sequential one is not verified under capture
-            raise PpeaKernelError(f"the captured training step needs the batched pose path (frame_ids [0, -1, 1]); the "
-                                  f"model has frame_ids {list(self.trainer.opt.frame_ids)}, matching_ids {ids}: "
+            # the batched pose path (repdepth.pose_step_plan); the sequential one is not verified under capture
+            raise PpeaKernelError(f"the captured training step needs the batched pose path, which serves frame_ids [0, -1, 1] "
+                                  f"and the one-source-frame step (frame_ids [0, -1] with matching_ids [0, -1]); the model "
+                                  f"has frame_ids {list(self.trainer.opt.frame_ids)}, matching_ids {ids} -- other frame_ids, "
+                                  "and [0, -1] with --use_future_frame or more matching frames, are still unserved: "
                                   "train with eager steps (TrainEngine.step without capture)")
         if ids != [0, -1] and world_size() > 1:
             raise PpeaKernelError(f"the captured step with matching_ids {ids} is verified on one rank only: "

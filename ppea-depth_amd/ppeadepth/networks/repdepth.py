@@ -79,6 +79,23 @@ def pose_pair_plan(frame_ids, matching_ids):
     return PosePlan(pairs, frames, updates)
 
 
+def pose_step_plan(frame_ids, matching_ids):
+    """The pose plan of a training step: `pose_pair_plan` for frame_ids [0, -1, 1], and the one-source-frame step,
+    frame_ids [0, -1] with matching_ids [0, -1] (DDAD loads frames 0 and -1 only, ddad_dataset.py:127-129): one gradient
+    pass on the pair (-1, 0), and the lookup frame's no_grad pass is that pass again, so it is the replayed
+    running-statistics update -- the gradient pass's update first, then the replay, as in the reference.
+    Raises ValueError for everything else (one source frame with a future frame or further lookup frames among them)."""
+    frame_ids, matching_ids = [f for f in frame_ids], [int(f) for f in matching_ids]
+    if frame_ids == [0, -1, 1]:
+        return pose_pair_plan(frame_ids, matching_ids)
+    if frame_ids != [0, -1]:
+        raise ValueError(f"the batched pose path serves frame_ids [0, -1, 1] and [0, -1], not {frame_ids}")
+    if matching_ids != [0, -1]:
+        raise ValueError(f"frame_ids [0, -1] is served with matching_ids [0, -1], not {matching_ids}: --use_future_frame "
+                         "and further matching frames need frames the two-frame item does not have")
+    return PosePlan([(-1, 0)], [PoseFrame(-1, 0, True, -1, True)], [("grad", 0), ("replay", 0)])
+
+
 class RepDepth(nn.Module):
     def __init__(self, opt):
         super().__init__()
@@ -194,11 +211,11 @@ class RepDepth(nn.Module):
         return st
 
     def pose_plan(self):
-        """`pose_pair_plan` of this model, or None where the batched pose path does not serve it (other `frame_ids`)."""
+        """`pose_step_plan` of this model, or None where the batched pose path does not serve it (other `frame_ids`)."""
         key = (tuple(self.opt.frame_ids), tuple(self.matching_ids))
         if getattr(self, "_pose_plan_key", None) != key:
             try:
-                self._pose_plan = pose_pair_plan(self.opt.frame_ids, self.matching_ids)
+                self._pose_plan = pose_step_plan(self.opt.frame_ids, self.matching_ids)
             except ValueError:
                 self._pose_plan = None
             self._pose_plan_key = key
@@ -216,22 +233,24 @@ class RepDepth(nn.Module):
         changes is one more BatchNorm running-statistics update with that pass's batch statistics: the update is replayed
         (GroupBN.replay_update) and the pass itself is skipped.  Only the pairs (-k - 1, -k), k >= 1, are new passes
         (`pose_pair_plan`).  Replays and new passes happen in the reference's order.  One `ops.pose_chain` launch then
-        turns the per-pair outputs into every lookup frame's relative pose.  POSE_ONE_BATCH additionally sends both
-        gradient pairs through the network as one 2B batch with per-sub-batch statistics."""
+        turns the per-pair outputs into every lookup frame's relative pose.  POSE_ONE_BATCH additionally sends the
+        gradient pairs through the network as one batch with per-sub-batch statistics: two pairs as 2B with groups = 2,
+        the single pair of frame_ids [0, -1] (`pose_step_plan`) as B with groups = 1, recorded for its replay."""
         plan = self.pose_plan()
+        n_grad = len(self.opt.frame_ids) - 1                     # the gradient pairs lead `plan.pairs` and `plan.updates`
         outputs = {}
         f = {i: inputs[("color_aug", i, 0)] for i in {i for pr in plan.pairs for i in pr}}
         B = f[0].shape[0]
         pairs = [torch.cat([f[a], f[b]], 1) for a, b in plan.pairs]
         enc = self.pose_encoder
         if POSE_ONE_BATCH:
-            aa2, tt2 = self.pose([enc(torch.cat(pairs[:2], 0), groups=2, record=True)])
-            res = [(aa2[:B], tt2[:B]), (aa2[B:], tt2[B:])]
+            aa2, tt2 = self.pose([enc(torch.cat(pairs[:n_grad], 0) if n_grad > 1 else pairs[0], groups=n_grad, record=True)])
+            res = [(aa2[p * B:(p + 1) * B], tt2[p * B:(p + 1) * B]) for p in range(n_grad)] if n_grad > 1 else [(aa2, tt2)]
             recorded, enc.recorded, enc.recorded_groups = enc.recorded_groups, None, None
             stats = None
         else:
             res, stats = [], []
-            for p in range(2):                                   # (the batch statistics only of a pair that is replayed)
+            for p in range(n_grad):                              # (the batch statistics only of a pair that is replayed)
                 snap = enc.snapshot_running() if ("replay", p) in plan.updates else None
                 res.append(self.pose([enc(pairs[p])]))
                 stats.append(enc.batch_stats_since(snap) if snap is not None else None)
@@ -246,7 +265,7 @@ class RepDepth(nn.Module):
             # no replay sits between two new passes
             grouped = (NEW_PASSES_ONE_BATCH and len(new) > 1 and f[0].is_cuda
                        and all(kind == "new" for kind, _ in plan.updates[-len(new):]))
-            for kind, p in plan.updates[2:]:
+            for kind, p in plan.updates[n_grad:]:
                 if kind == "replay":
                     if stats is None:
                         replay_updates(recorded[p])

@@ -564,10 +564,58 @@ def loss_select(reproj, identity, warped_m1, warped_p1, noise, selec_reproj=True
     return _LossSelect.apply(reproj, identity, warped_m1, warped_p1, noise, selec_reproj)
 
 
+class _LossSelectN(torch.autograd.Function):
+    """`_LossSelect` for S = reproj.shape[1] source frames, S in {1, 2} (ppea_loss_select_n_f32)."""
+
+    @staticmethod
+    def forward(ctx, reproj, identity, noise, selec, *warped):
+        reproj = reproj.contiguous().float()
+        B, S, H, W = reproj.shape
+        dev = reproj.device
+        warped = [w.contiguous().float() for w in warped]
+        sel = torch.empty(B, 1, H, W, device=dev, dtype=_F32)
+        src = torch.empty(B, 1, H, W, device=dev, dtype=torch.uint8)
+        fidx = torch.empty(B, 1, H, W, device=dev, dtype=torch.int64)
+        aidx = torch.empty(B, 1, H, W, device=dev, dtype=torch.int64)
+        call("ppea_loss_select_n_f32", ptr(reproj), ptr(identity.contiguous().float()),
+             ptr(warped[0] if warped else None), ptr(warped[1] if warped else None),
+             ptr(None if noise is None else noise.contiguous().float()), ptr(sel), ptr(src), ptr(fidx),
+             ptr(aidx), B, S, warped[0].shape[1] if warped else 0, H, W, int(bool(selec)), stream_ptr())
+        ctx.save_for_backward(src)
+        ctx.n_src = S
+        ctx.mark_non_differentiable(src, fidx, aidx)
+        ctx.set_materialize_grads(False)
+        return sel, src, fidx, aidx
+
+    @staticmethod
+    def backward(ctx, d_sel, _a, _b, _c):
+        (src,) = ctx.saved_tensors
+        d = None
+        if d_sel is not None:
+            d = torch.cat([d_sel * (src == c) for c in range(ctx.n_src)], 1)
+        return (d,) + (None,) * (len(ctx.needs_input_grad) - 1)
+
+
+def loss_select_n(reproj, identity, warped, noise, selec_reproj=False):
+    """`loss_select` for S = reproj.shape[1] source frames, S in {1, 2}; `identity` [B,S,H,W]; `warped`: the S warped
+    frames, read for `selec_reproj` only, or None.  One frame (frame_ids [0, -1]): the selected loss is that frame's, the
+    source and frame indices are 0, and `selec_reproj` -- which falls back on the OTHER frame -- is refused."""
+    S = reproj.shape[1]
+    if S not in (1, 2) or identity.shape[1] != S:
+        raise ValueError(f"loss_select_n: reproj {tuple(reproj.shape)}, identity {tuple(identity.shape)}: one or two source "
+                         "frames, the same in both")
+    if selec_reproj and S == 1:
+        raise ValueError("loss_select_n: selec_reproj needs two source frames (train frame_ids [0, -1] with --selec_reproj, "
+                         "which switches it off)")
+    if selec_reproj and (warped is None or len(warped) != S):
+        raise ValueError("loss_select_n: selec_reproj reads the warped frame of every source frame")
+    return _LossSelectN.apply(reproj, identity, noise, selec_reproj, *(warped if selec_reproj else ()))
+
+
 class _LossTail(torch.autograd.Function):
     """Tail of compute_losses (trainer.py:1092-1139) in one pass per direction (csrc/photometric.hip loss_tail_*):
-    -> (rl, consistency_loss, mask, consistency_target).  `reproj` [B,2,H,W] is the differentiable input the selected loss
-    `sel` was taken from (`src`: which channel, 2 = forced zero); its gradient is produced directly."""
+    -> (rl, consistency_loss, mask, consistency_target).  `reproj` [B,S,H,W], S in {1, 2}, is the differentiable input the
+    selected loss `sel` was taken from (`src`: which channel, 2 = forced zero); its gradient is produced directly."""
 
     @staticmethod
     def forward(ctx, reproj, sel, src, auto_idx, cons, aug, multi, mono, is_multi):
@@ -586,6 +634,7 @@ class _LossTail(torch.autograd.Function):
              ptr(target), ptr(partial), ptr(out), B, H, W, int(bool(is_multi)), stream_ptr())
         ctx.save_for_backward(mask, src, out, multi_c, mono_c)
         ctx.dims = (B, H, W, bool(is_multi), multi is not None and multi.requires_grad)
+        ctx.n_src = int(reproj.shape[1])                     # source frames: d_reproj [B,S,H,W]
         ctx.set_materialize_grads(False)
         rl, cl = out[0], out[1]
         if target is not None:
@@ -599,11 +648,11 @@ class _LossTail(torch.autograd.Function):
         mask, src, out, multi, mono = ctx.saved_tensors
         B, H, W, is_multi, multi_grad = ctx.dims
         dev = mask.device
-        d_reproj = torch.empty(B, 2, H, W, device=dev, dtype=_F32) if ctx.needs_input_grad[0] else None
+        d_reproj = torch.empty(B, ctx.n_src, H, W, device=dev, dtype=_F32) if ctx.needs_input_grad[0] else None
         d_multi = torch.empty(B, 1, H, W, device=dev, dtype=_F32) if (is_multi and multi_grad and g_cl is not None) else None
-        call("ppea_loss_tail_bwd_f32", ptr(mask), ptr(src), ptr(out), ptr(None if g_rl is None else g_rl.contiguous().float()),
+        call("ppea_loss_tail_bwd_n_f32", ptr(mask), ptr(src), ptr(out), ptr(None if g_rl is None else g_rl.contiguous().float()),
              ptr(None if g_cl is None else g_cl.contiguous().float()), ptr(multi), ptr(mono), ptr(d_reproj), ptr(d_multi),
-             B, H, W, stream_ptr())
+             B, ctx.n_src, H, W, stream_ptr())
         return d_reproj, None, None, None, None, None, d_multi, None, None
 
 

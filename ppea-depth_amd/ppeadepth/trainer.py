@@ -423,6 +423,14 @@ class Trainer:
     def compute_losses(self, inputs, outputs, is_multi=False):
         opt = self.opt
         losses, total_loss = {}, 0
+        n_src = len(opt.frame_ids) - 1
+        if n_src == 1 and opt.selec_reproj:
+            # trainer.py:1077-1083 falls back on the OTHER source frame where one warps to nothing: with one source frame
+            # (DDAD loads frames 0 and -1, ddad_dataset.py:127-129) the reference dies on outputs[("color", 1, scale)]
+            raise ValueError(f"frame_ids {list(opt.frame_ids)}: selec_reproj needs two source frames; pass --selec_reproj "
+                             "(store_false: it switches the fallback off) to train with one")
+        if n_src > 2:
+            raise ValueError(f"frame_ids {list(opt.frame_ids)}: the loss kernels serve one or two source frames")
         for scale in range(opt.sclm + 1):
             disp = outputs[("disp", scale)].float()
             color = inputs[("color", 0, scale)]
@@ -435,9 +443,13 @@ class Trainer:
             noise = None
             if not opt.disable_automasking:
                 noise = rng.randn_like_cpu_order((B, 1, H, W), self.device) * 0.00001
-            reprojection_loss, _src, frame_idxs, auto_idx = ops.loss_select(
-                reprojection_losses, identity_losses, outputs[("color", fids[0], scale)].detach(),
-                outputs[("color", fids[1], scale)].detach(), noise, opt.selec_reproj)
+            if n_src == 2:
+                reprojection_loss, _src, frame_idxs, auto_idx = ops.loss_select(
+                    reprojection_losses, identity_losses, outputs[("color", fids[0], scale)].detach(),
+                    outputs[("color", fids[1], scale)].detach(), noise, opt.selec_reproj)
+            else:           # one source frame: the minimum over the frames is that frame, no warped frame is read
+                reprojection_loss, _src, frame_idxs, auto_idx = ops.loss_select_n(
+                    reprojection_losses, identity_losses, None, noise, False)
             outputs[("frame_idxs", scale)] = frame_idxs
             if not opt.disable_automasking:
                 outputs[("automask_idxs", scale)] = auto_idx
