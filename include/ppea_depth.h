@@ -570,6 +570,35 @@ int ppea_conv_nhwc_plan(int N, int H, int W, int Cin, int Cout, int R, int S, in
                         int Ho, int Wo, int out_nchw, int* plan);
 int ppea_conv_wgrad_plan(int N, int Cin, int Cout, int R, int S, int stride, int Ho, int Wo, int* plan);
 
+/* Plans of the large-kernel depthwise kernels (ABI 22).  Host only, no device call, no stream; each is answered by the
+ * function the launch itself goes by.
+ *   ppea_dwconv_lk_plan   what ppea_dwconv_lk_fwd_bf16p (mode 0, variant 0), _fwd_stats_bf16p (0, 1), _fwd_bn_bf16p (0, 2),
+ *        _fwd_bias_act_bf16p (0, 3; KS = 0) and _bwd_data_bf16p (mode 1, variant 0) launch for [N,C,H,W], K, KS.  plan[24]:
+ *          [0] family   0 no MFMA kernel serves the shape (the entry point returns PPEA_ERR_UNSUPPORTED; the rest is 0),
+ *                       1 row-band dwconv_mfma_kernel<K, KS, mode, NSEG, BN, WS, BA>,
+ *                       2 batch-major dwconv_bm_kernel<K, KS, mode, H, NY, NTX, RS, BN>
+ *          [1] partials statistics partials per channel (forward; = ppea_dwconv_lk_stats_partials; 0 for mode 1 and BA)
+ *          [2] lds_bytes  dynamic LDS of the launch
+ *          row-band:    [3] NSEG  [4] WS  [5] BN  [6] BA  [7] band  [8] G (planes stacked per item)  [9] bands per plane
+ *                       [10] segs (column segments)  [11] items_per_channel  [12] wpc (waves per channel)
+ *                       [13] ipw (items per wave)  [14] fast (1: prefetched staging)
+ *          batch-major: [5] BN  [15] H  [16] NY  [17] NTX  [18] RS  [19] VEC (8: W % 8 == 0, else 4)  [20] gi (images per
+ *                       group)  [21] ngroups  [22] wgpc (workgroups per channel block)  [23] cpw (column tiles per workgroup)
+ *        Returns 0 (also with family 0), PPEA_ERR_ARG for plan == NULL or a mode / variant outside the lists.
+ *   ppea_dwconv_lk_bwd_filter_plan   plan[0..5] = parts, rows_per_part, rounds (of a full part: ceil(rows_per_part / 4)),
+ *        vec (1: W % 8 == 0, 16-byte dy loads), dynamic LDS bytes, rows of the last part, of ppea_dwconv_lk_bwd_filter_bf16;
+ *        PPEA_ERR_UNSUPPORTED where that call returns it.
+ *   ppea_dwconv_lk_f32_plan   plan[0] = index into CFGS_<K> (csrc/dwconv_lk.hip) of the tile the fp32 vector kernel
+ *        (ppea_dwconv_lk_{fwd,bwd_data}_{f32,bf16}, KS in {0, 5}) picks for an H x W plane; -1: the generic kernel. */
+int ppea_dwconv_lk_plan(int N, int C, int H, int W, int K, int KS, int mode, int variant, int* plan);
+/* Test support, host only: ppea_dwconv_lk_plan over N 1..Nmax x C in Cs[nC] x H 1..Hmax x W 1..Wmax, folded into
+ * seen[1 << 14] (one byte per packed plan key; the packing is documented at the definition in csrc/dwconv_mfma.hip) and
+ * summary[4] = shapes served, largest lds_bytes, plans whose ipw / wpc do not cover the items exactly, shapes not served. */
+int ppea_dwconv_lk_plan_sweep(int K, int KS, int mode, int variant, int Nmax, const int* Cs, int nC, int Hmax, int Wmax,
+                              unsigned char* seen, long* summary);
+int ppea_dwconv_lk_bwd_filter_plan(int N, int C, int H, int W, int K, int KS, int* plan);
+int ppea_dwconv_lk_f32_plan(int H, int W, int K, int* plan);
+
 /* fp32 dense convolutions / linear layers on the fp32 matrix cores (csrc/conv_f32.hip, v_mfma_f32_32x32x2_f32): the
  * fp32 (parity, BASELINE config 1) step's replacement for every library convolution and GEMM behind
  *   RepLKBlock / ConvFFN 1x1 convs, B_Adapter / Adapter     networks/replknet_adapter.py:20-109, 264-326

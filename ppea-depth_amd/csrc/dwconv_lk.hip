@@ -291,17 +291,33 @@ inline long cover_cost(int H, int W, int RY, int RX, int LX, int LY) {
 #define CFGS_27(X) X(27, 1, 8, 5, 12) X(27, 1, 8, 4, 12) X(27, 2, 8, 8, 8)
 #define CFGS_13(X) X(13, 1, 4, 5, 6) X(13, 1, 4, 4, 6) X(13, 2, 4, 8, 8)
 
+// index of the cheapest CFGS_<K> entry for an H x W plane (the first of equals); -1: no tuned tile for K.  Host only:
+// `dispatch`, `dispatch_bias_act` and ppea_dwconv_lk_f32_plan all go by it.
+inline int pick_cfg(int K, int H, int W) {
+    const Shape s{0, 0, H, W};
+    long best = -1;
+    int pick = -1, idx = 0;
+    switch (K) {
+        case 31: { CFGS_31(PPEA_TRY) break; }
+        case 29: { CFGS_29(PPEA_TRY) break; }
+        case 27: { CFGS_27(PPEA_TRY) break; }
+        case 13: { CFGS_13(PPEA_TRY) break; }
+        default: break;
+    }
+    return pick;
+}
+
 template <typename T, bool BWD>
 int dispatch(const T* a, const T* b, const float* wb, const float* ws, T* o0, T* o1, Shape s, int K,
              int KS, hipStream_t st) {
     const bool KS5 = (KS == 5);
-    long best = -1;
-    int pick = -1, idx = 0;
+    const int pick = pick_cfg(K, s.H, s.W);
+    int idx = 0;
     switch (K) {
-        case 31: { CFGS_31(PPEA_TRY) idx = 0; CFGS_31(PPEA_RUN) break; }
-        case 29: { CFGS_29(PPEA_TRY) idx = 0; CFGS_29(PPEA_RUN) break; }
-        case 27: { CFGS_27(PPEA_TRY) idx = 0; CFGS_27(PPEA_RUN) break; }
-        case 13: { CFGS_13(PPEA_TRY) idx = 0; CFGS_13(PPEA_RUN) break; }
+        case 31: { CFGS_31(PPEA_RUN) break; }
+        case 29: { CFGS_29(PPEA_RUN) break; }
+        case 27: { CFGS_27(PPEA_RUN) break; }
+        case 13: { CFGS_13(PPEA_RUN) break; }
         default: break;
     }
     return PPEA_ERR_UNSUPPORTED;
@@ -314,13 +330,13 @@ int dispatch(const T* a, const T* b, const float* wb, const float* ws, T* o0, T*
 template <typename T>
 int dispatch_bias_act(const T* x, const float* w, const float* bias, int relu, T* y, Shape s, int K, hipStream_t st) {
     T* relu_tag = relu ? y : nullptr;
-    long best = -1;
-    int pick = -1, idx = 0;
+    const int pick = pick_cfg(K, s.H, s.W);
+    int idx = 0;
     switch (K) {
-        case 31: { CFGS_31(PPEA_TRY) idx = 0; CFGS_31(PPEA_RUN_BA) break; }
-        case 29: { CFGS_29(PPEA_TRY) idx = 0; CFGS_29(PPEA_RUN_BA) break; }
-        case 27: { CFGS_27(PPEA_TRY) idx = 0; CFGS_27(PPEA_RUN_BA) break; }
-        case 13: { CFGS_13(PPEA_TRY) idx = 0; CFGS_13(PPEA_RUN_BA) break; }
+        case 31: { CFGS_31(PPEA_RUN_BA) break; }
+        case 29: { CFGS_29(PPEA_RUN_BA) break; }
+        case 27: { CFGS_27(PPEA_RUN_BA) break; }
+        case 13: { CFGS_13(PPEA_RUN_BA) break; }
         default: break;
     }
     return PPEA_ERR_UNSUPPORTED;
@@ -407,6 +423,15 @@ int ppea_dwconv_lk_fwd_bias_act_bf16(const void* x, const float* w, const float*
 }
 
 int ppea_abi_version(void) { return PPEA_ABI_VERSION; }
+
+// Host only: plan[0] = index of the CFGS_<K> entry (csrc/dwconv_lk.hip) the fp32 vector kernel runs an H x W plane on with
+// KS in {0, 5}; -1: the generic kernel (other K, or KS == 3).
+int ppea_dwconv_lk_f32_plan(int H, int W, int K, int* plan) {
+    if (plan == nullptr) return PPEA_ERR_ARG;
+    if (H <= 0 || W <= 0) return PPEA_ERR_UNSUPPORTED;
+    plan[0] = pick_cfg(K, H, W);
+    return 0;
+}
 
 int ppea_timestamp(void* slot, void* stream) {
     if (slot == nullptr) return PPEA_ERR_ARG;

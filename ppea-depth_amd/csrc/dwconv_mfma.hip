@@ -280,6 +280,15 @@ __device__ __forceinline__ int stage_pieces(const Item& it, int H) {       // pe
     return it.G * ((hi - lo + RPI - 1) / RPI);
 }
 
+// Whether a launch stages with the prefetch: one band (every item covers whole planes: y0 = 0, rows = H, so an image needs
+// ceil(H / RPI) pieces per lane), aligned columns, and the pieces of a full group of G images fit the SU slots.  The same
+// value for every wave of a launch; the kernel and the host plan (plan_rb) both go by this function.
+template <int K, int NSEG>
+__host__ __device__ __forceinline__ bool fast_staging(int H, int W, int G, int bands) {
+    constexpr int RPI = 64 / (Seg<K, NSEG>::WL / 8);
+    return bands == 1 && (W & 7) == 0 && (G > 1 ? G : 1) * ((H + RPI - 1) / RPI) <= SU;
+}
+
 template <int K, int NSEG>
 __device__ __forceinline__ void stage_load(uint4 (&v)[SU], const uint16_t* __restrict__ src, const Item& it, int C,
                                            int c, int H, int W, int lane) {
@@ -668,7 +677,7 @@ __global__ __launch_bounds__(64 * WAVES, 1) void dwconv_mfma_kernel(
     Item it;
     bool have = make_item(first_item, it);
     // prefetched staging (see stage_load): whole planes per item, aligned columns, few enough pieces
-    const bool fast = have && bands == 1 && (W & 7) == 0 && stage_pieces<K, NSEG>(it, H) * (G > 1 ? G : 1) / it.G <= SU;
+    const bool fast = have && fast_staging<K, NSEG>(H, W, G, bands);
     uint4 pre[SU];
     if (fast) {
         for (int off = lane * 16; off < NT_IN * tile_bytes; off += 64 * 16)
@@ -1188,37 +1197,61 @@ __global__ __launch_bounds__(256, 1) void dwconv_bm_kernel(
     }
 }
 
+// ---- host plans ----------------------------------------------------------------------------------------------------------
+// Every host decision of a launch is made by ONE plain function per launcher (plan_bm, plan_rb: no device call); the launch
+// passes what it returns to the kernel, and ppea_dwconv_lk_plan reports it (`plan_out` below: do not launch, fill the
+// report).  Layout of the report: include/ppea_depth.h.
+constexpr int LK_PLAN_INTS = 24;
+
+struct BmPlan { int gi, tile_bytes, tile1_bytes, ngroups, wgpc, cpw, partials; size_t lds; };
+
 // returns PPEA_ERR_UNSUPPORTED when the shape is not this variant's (the caller falls back to the row-band kernel)
-template <int K, int KS, int MODE, int H, int NY, int NTX, int RS, bool BN>
-int launch_bm(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0, uint16_t* o1,
-              int N, int C, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn) {
+template <int K, int KS, int MODE, int H, int NY, int NTX>
+int plan_bm(int N, int C, int W, BmPlan& p) {
     using B = BmGeo<K, NTX>;
     using B1 = BmGeo<(KS > 0 ? KS : 5), NTX>;
     constexpr int SPLIT = H / NY, CPW = 4 / SPLIT;
     constexpr int NT_IN = (MODE == 1 && KS > 0) ? 2 : 1;
     if ((long)N * C * H * W >= (1L << 31) || (long)N * C * H * W < 8) return PPEA_ERR_UNSUPPORTED;   // (masked pieces read the tensor's first 16 bytes)
-    int gi = 0, tile_bytes = 0, tile1_bytes = 0;
+    p.gi = 0; p.tile_bytes = 0; p.tile1_bytes = 0;
     for (int cand : {16, 12, 8, 4}) {                            // images per group: the largest whose tiles fit
         const int alloc = N < cand ? N : cand;
         const int tb = H * alloc * B::STRIDE, tb1 = NT_IN == 2 ? H * alloc * B1::STRIDE : 0;
-        if (CPW * (tb + tb1) <= LDS_LIMIT) { gi = cand; tile_bytes = tb; tile1_bytes = tb1; break; }
+        if (CPW * (tb + tb1) <= LDS_LIMIT) { p.gi = cand; p.tile_bytes = tb; p.tile1_bytes = tb1; break; }
     }
-    if (!gi) return PPEA_ERR_UNSUPPORTED;
-    const int ngroups = (N + gi - 1) / gi;
+    if (!p.gi) return PPEA_ERR_UNSUPPORTED;
+    p.ngroups = (N + p.gi - 1) / p.gi;
     // column tiles per workgroup: whole planes on the small maps; on wide maps enough workgroups to fill the chip
     const int ntx_all = (W + 15) / 16;
     int wgpc = 1;
     if (ntx_all > NTX) {
-        const long base = (long)((C + CPW - 1) / CPW) * ngroups;
+        const long base = (long)((C + CPW - 1) / CPW) * p.ngroups;
         wgpc = (int)((256 + base - 1) / base);
         if (wgpc < 1) wgpc = 1;
         if (wgpc > ntx_all) wgpc = ntx_all;
     }
-    const int cpw = (ntx_all + wgpc - 1) / wgpc;
-    wgpc = (ntx_all + cpw - 1) / cpw;
-    if (wpc_out != nullptr) { *wpc_out = SPLIT * ngroups * wgpc; return 0; }
-    size_t lds = (size_t)CPW * (tile_bytes + tile1_bytes);
-    if (lds < (size_t)4 * frag_scratch_bytes(K, KS)) lds = (size_t)4 * frag_scratch_bytes(K, KS);
+    p.cpw = (ntx_all + wgpc - 1) / wgpc;
+    p.wgpc = (ntx_all + p.cpw - 1) / p.cpw;
+    p.partials = SPLIT * p.ngroups * p.wgpc;
+    p.lds = (size_t)CPW * (p.tile_bytes + p.tile1_bytes);
+    if (p.lds < (size_t)4 * frag_scratch_bytes(K, KS)) p.lds = (size_t)4 * frag_scratch_bytes(K, KS);
+    return 0;
+}
+
+template <int K, int KS, int MODE, int H, int NY, int NTX, int RS, bool BN>
+int launch_bm(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0, uint16_t* o1,
+              int N, int C, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn, int* plan_out) {
+    constexpr int SPLIT = H / NY, CPW = 4 / SPLIT;
+    BmPlan p;
+    const int perr = plan_bm<K, KS, MODE, H, NY, NTX>(N, C, W, p);
+    if (perr != 0) return perr;
+    if (wpc_out != nullptr) { *wpc_out = p.partials; return 0; }
+    if (plan_out != nullptr) {
+        const int rep[LK_PLAN_INTS] = {2, MODE == 0 ? p.partials : 0, (int)p.lds, 0, 0, BN ? 1 : 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+                                       H, NY, NTX, RS, (W & 7) == 0 ? 8 : 4, p.gi, p.ngroups, p.wgpc, p.cpw};
+        for (int i = 0; i < LK_PLAN_INTS; ++i) plan_out[i] = rep[i];
+        return 0;
+    }
     auto kern = dwconv_bm_kernel<K, KS, MODE, H, NY, NTX, RS, BN>;
     const BnIn bnv = bn != nullptr ? *bn : BnIn{nullptr, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static bool attr_done = false;
@@ -1226,31 +1259,31 @@ int launch_bm(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, cons
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         attr_done = true;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(((C + CPW - 1) / CPW) * ngroups * wgpc)), dim3(256), lds, st, in0, in1, wb, ws,
-                       o0, o1, N, C, W, gi, ngroups, wgpc, cpw, tile_bytes, tile1_bytes, stats, bnv);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(((C + CPW - 1) / CPW) * p.ngroups * p.wgpc)), dim3(256), p.lds, st, in0, in1, wb, ws,
+                       o0, o1, N, C, W, p.gi, p.ngroups, p.wgpc, p.cpw, p.tile_bytes, p.tile1_bytes, stats, bnv);
     return launch_status();
 }
 
 template <int K, int KS, int MODE, int H, int NY, int NTX, int RS>
 int launch_bm_n(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0, uint16_t* o1,
-                int N, int C, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn) {
+                int N, int C, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn, int* plan_out) {
     if constexpr (MODE == 0) {
-        if (bn != nullptr) return launch_bm<K, KS, MODE, H, NY, NTX, RS, true>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, bn);
+        if (bn != nullptr) return launch_bm<K, KS, MODE, H, NY, NTX, RS, true>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, bn, plan_out);
     }
     if (bn != nullptr) return PPEA_ERR_UNSUPPORTED;
-    return launch_bm<K, KS, MODE, H, NY, NTX, RS, false>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, nullptr);
+    return launch_bm<K, KS, MODE, H, NY, NTX, RS, false>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, nullptr, plan_out);
 }
 
 // The plane sizes this variant is built for: RepLKNet stages 0-3 of 192-row frames (48 x W in segments, 24 x {64, 80},
 // 12 x {8..48}, 6 x {4..48}).
 template <int K, int KS, int MODE>
 int launch_bm_w(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0, uint16_t* o1,
-                int N, int C, int H, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn) {
+                int N, int C, int H, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn, int* plan_out) {
     static const bool on = !(getenv("PPEA_DW_BM") != nullptr && getenv("PPEA_DW_BM")[0] == '0');
     if (!on || (W & 3) != 0) return PPEA_ERR_UNSUPPORTED;
     const int ntx = (W + 15) / 16;
 #define PPEA_BM_NTX(H_, NTX_)                                                                                          \
-    if (H == H_ && ntx == NTX_) return launch_bm_n<K, KS, MODE, H_, 6, NTX_, 1>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, bn);
+    if (H == H_ && ntx == NTX_) return launch_bm_n<K, KS, MODE, H_, 6, NTX_, 1>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, bn, plan_out);
     if constexpr (KS == 5 && K == 29) { PPEA_BM_NTX(24, 4) PPEA_BM_NTX(24, 5) }
     if constexpr (KS == 5 && K == 27) { PPEA_BM_NTX(12, 1) PPEA_BM_NTX(12, 2) PPEA_BM_NTX(12, 3) }
     if constexpr (KS == 5 && K == 13) { PPEA_BM_NTX(6, 1) PPEA_BM_NTX(6, 2) PPEA_BM_NTX(6, 3) }
@@ -1265,17 +1298,15 @@ int launch_bm_w(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, co
         static const bool on48 = !(getenv("PPEA_DW_BM48") != nullptr && getenv("PPEA_DW_BM48")[0] == '0');
         const int groups16 = (N + 15) / 16;
         if (on48 && H == 48 && (W & 7) == 0 && 10 * N >= 7 * 16 * groups16)
-            return launch_bm_n<K, KS, MODE, 48, 12, 2, 4>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, bn);
+            return launch_bm_n<K, KS, MODE, 48, 12, 2, 4>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, bn, plan_out);
     }
     return PPEA_ERR_UNSUPPORTED;
 }
 
-// stats / wpc_out: forward only -- per-wave partial sums for the BatchNorm pair (see the kernel); wpc_out != nullptr:
-// do not launch, return the number of waves per channel (= partials per channel) the launch would use
-template <int K, int KS, int MODE, int NSEG, bool BN = false, bool WS = false, bool BA = false>
-int launch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0,
-           uint16_t* o1, int N, int C, int H, int W, hipStream_t st, float* stats = nullptr, int* wpc_out = nullptr,
-           const BnIn* bn = nullptr) {
+struct RbPlan { int band, G, tile_bytes, region, bands, segs, items_per_channel, wpc, ipw, fast; long total_waves; size_t lds; };
+
+template <int K, int KS, int MODE, int NSEG, bool WS>
+int plan_rb(int N, int C, int H, int W, RbPlan& p) {
     constexpr int STRIDE_B = Seg<K, NSEG>::STRIDE;
     constexpr int NT_IN = (MODE == 1 && KS > 0) ? 2 : 1;
     if ((long)N * C * H * W >= (1L << 31)) return PPEA_ERR_UNSUPPORTED;      // 32-bit element offsets
@@ -1295,22 +1326,43 @@ int launch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const u
         if (band) break;
     }
     if (!band) return PPEA_ERR_UNSUPPORTED;
-    const int bands = (G > 1) ? 1 : (H + band - 1) / band;
-    const int segs = (W + 16 * NSEG - 1) / (16 * NSEG);
-    const int groups = (G > 1) ? (N + G - 1) / G : N * bands;
-    const int items_per_channel = groups * segs;
+    p.band = band; p.G = G; p.tile_bytes = tile_bytes; p.region = region;
+    p.bands = (G > 1) ? 1 : (H + band - 1) / band;
+    p.segs = (W + 16 * NSEG - 1) / (16 * NSEG);
+    const int groups = (G > 1) ? (N + G - 1) / G : N * p.bands;
+    p.items_per_channel = groups * p.segs;
     // waves per channel: ~one wave per SIMD over the whole chip (1024), each wave keeps its channel's
     // Toeplitz fragments in registers and walks `ipw` items
     int wpc = 1024 / C;
     if (wpc < 1) wpc = 1;
-    if (wpc > items_per_channel) wpc = items_per_channel;
-    const int ipw = (items_per_channel + wpc - 1) / wpc;
-    wpc = (items_per_channel + ipw - 1) / ipw;
-    if (wpc_out != nullptr) { *wpc_out = wpc; return 0; }
-    const long total_waves = (long)C * wpc;
-    const size_t lds = (size_t)WAVES * region;
+    if (wpc > p.items_per_channel) wpc = p.items_per_channel;
+    p.ipw = (p.items_per_channel + wpc - 1) / wpc;
+    p.wpc = (p.items_per_channel + p.ipw - 1) / p.ipw;
+    p.total_waves = (long)C * p.wpc;
+    p.lds = (size_t)WAVES * region;
+    p.fast = fast_staging<K, NSEG>(H, W, G, p.bands) ? 1 : 0;
     if constexpr (WS) {
         if (!(G == 1 && band == 48 && H % 48 == 0)) return PPEA_ERR_UNSUPPORTED;       // every item: one 48-row band
+    }
+    return 0;
+}
+
+// stats / wpc_out: forward only -- per-wave partial sums for the BatchNorm pair (see the kernel); wpc_out != nullptr:
+// do not launch, return the number of waves per channel (= partials per channel) the launch would use
+template <int K, int KS, int MODE, int NSEG, bool BN = false, bool WS = false, bool BA = false>
+int launch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0,
+           uint16_t* o1, int N, int C, int H, int W, hipStream_t st, float* stats = nullptr, int* wpc_out = nullptr,
+           const BnIn* bn = nullptr, int* plan_out = nullptr) {
+    RbPlan p;
+    const int perr = plan_rb<K, KS, MODE, NSEG, WS>(N, C, H, W, p);
+    if (perr != 0) return perr;
+    if (wpc_out != nullptr) { *wpc_out = p.wpc; return 0; }
+    if (plan_out != nullptr) {
+        const int rep[LK_PLAN_INTS] = {1, (MODE == 0 && !BA) ? p.wpc : 0, (int)p.lds, NSEG, WS ? 1 : 0, BN ? 1 : 0, BA ? 1 : 0,
+                                       p.band, p.G, p.bands, p.segs, p.items_per_channel, p.wpc, p.ipw, p.fast,
+                                       0, 0, 0, 0, 0, 0, 0, 0, 0};
+        for (int i = 0; i < LK_PLAN_INTS; ++i) plan_out[i] = rep[i];
+        return 0;
     }
     auto kern = dwconv_mfma_kernel<K, KS, MODE, NSEG, BN, WS, BA>;
     const BnIn bnv = bn != nullptr ? *bn : BnIn{nullptr, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -1319,9 +1371,9 @@ int launch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const u
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         attr_done = true;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((total_waves + WAVES - 1) / WAVES)), dim3(64 * WAVES), lds, st, in0,
-                       in1, wb, ws, o0, o1, N, C, H, W, G, band, bands, segs, items_per_channel, ipw, wpc,
-                       total_waves, tile_bytes, region, stats, bnv);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((p.total_waves + WAVES - 1) / WAVES)), dim3(64 * WAVES), p.lds, st, in0,
+                       in1, wb, ws, o0, o1, N, C, H, W, p.G, p.band, p.bands, p.segs, p.items_per_channel, p.ipw, p.wpc,
+                       p.total_waves, p.tile_bytes, p.region, stats, bnv);
     return launch_status();
 }
 
@@ -1334,9 +1386,9 @@ inline long staged_cols(int W, int nseg) {
 
 template <int K, int KS, int MODE>
 int launch_k(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0,
-             uint16_t* o1, int N, int C, int H, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn) {
+             uint16_t* o1, int N, int C, int H, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn, int* plan_out) {
     {                                                            // small planes: the batch-major variant
-        const int err = launch_bm_w<K, KS, MODE>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn);
+        const int err = launch_bm_w<K, KS, MODE>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
         if (err != PPEA_ERR_UNSUPPORTED) return err;
     }
 #ifdef PPEA_BM_ONLY                                              // (compile-time experiments with the batch-major variant alone)
@@ -1351,48 +1403,48 @@ int launch_k(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const
         if (ws_on && nseg == 5 && wpc_out == nullptr) {
             int err;
             if constexpr (MODE == 0) {
-                err = bn != nullptr ? launch<K, KS, MODE, 5, true, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, nullptr, bn)
-                                    : launch<K, KS, MODE, 5, false, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, nullptr, nullptr);
+                err = bn != nullptr ? launch<K, KS, MODE, 5, true, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, nullptr, bn, plan_out)
+                                    : launch<K, KS, MODE, 5, false, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, nullptr, nullptr, plan_out);
             } else {
                 err = bn != nullptr ? PPEA_ERR_UNSUPPORTED
-                                    : launch<K, KS, MODE, 5, false, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, nullptr, nullptr);
+                                    : launch<K, KS, MODE, 5, false, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, nullptr, nullptr, plan_out);
             }
             if (err != PPEA_ERR_UNSUPPORTED) return err;
         }
     }
     if constexpr (MODE == 0 && KS == 5) {
         if (bn != nullptr) {                                     // fused input BatchNorm + ReLU (RepLKBlock forward)
-            if (nseg == 5) return launch<K, KS, MODE, 5, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn);
-            if (nseg == 3) return launch<K, KS, MODE, 3, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn);
-            return launch<K, KS, MODE, 2, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn);
+            if (nseg == 5) return launch<K, KS, MODE, 5, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
+            if (nseg == 3) return launch<K, KS, MODE, 3, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
+            return launch<K, KS, MODE, 2, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
         }
     }
     if (bn != nullptr) return PPEA_ERR_UNSUPPORTED;
-    if (nseg == 5) return launch<K, KS, MODE, 5>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out);
-    if (nseg == 3) return launch<K, KS, MODE, 3>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out);
-    return launch<K, KS, MODE, 2>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out);
+    if (nseg == 5) return launch<K, KS, MODE, 5>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, nullptr, plan_out);
+    if (nseg == 3) return launch<K, KS, MODE, 3>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, nullptr, plan_out);
+    return launch<K, KS, MODE, 2>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, nullptr, plan_out);
 }
 
 // Merged filter + bias (+ ReLU), forward: the general kernel with the column-segment choice of launch_k.
 template <int K>
 int launch_bias_act(const uint16_t* x, const uint16_t* wb, uint16_t* y, const float* bias, int relu, int N, int C, int H,
-                    int W, hipStream_t st) {
+                    int W, hipStream_t st, int* plan_out = nullptr) {
     const long c5 = staged_cols<K>(W, 5), c3 = staged_cols<K>(W, 3), c2 = staged_cols<K>(W, 2);
     const int nseg = (c5 <= c3 && c5 <= c2) ? 5 : (c3 <= c2 ? 3 : 2);
     const BnIn ba{nullptr, relu ? 1 : 0, 0.f, 0.f, 0.f, nullptr, bias, nullptr, nullptr, nullptr, nullptr};
-    if (nseg == 5) return launch<K, 0, 0, 5, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba);
-    if (nseg == 3) return launch<K, 0, 0, 3, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba);
-    return launch<K, 0, 0, 2, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba);
+    if (nseg == 5) return launch<K, 0, 0, 5, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba, plan_out);
+    if (nseg == 3) return launch<K, 0, 0, 3, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba, plan_out);
+    return launch<K, 0, 0, 2, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba, plan_out);
 }
 
 template <int MODE>
 int dispatch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0,
              uint16_t* o1, int N, int C, int H, int W, int K, int KS, hipStream_t st, float* stats = nullptr,
-             int* wpc_out = nullptr, const BnIn* bn = nullptr) {
+             int* wpc_out = nullptr, const BnIn* bn = nullptr, int* plan_out = nullptr) {
 #define PPEA_CASE(K_)                                                                             \
     case K_:                                                                                      \
-        return KS == 5 ? launch_k<K_, 5, MODE>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn)   \
-                       : launch_k<K_, 0, MODE>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn);
+        return KS == 5 ? launch_k<K_, 5, MODE>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out)   \
+                       : launch_k<K_, 0, MODE>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
     switch (K) {
         PPEA_CASE(31) PPEA_CASE(29) PPEA_CASE(27) PPEA_CASE(13)
         default: return PPEA_ERR_UNSUPPORTED;
@@ -1498,6 +1550,74 @@ int ppea_dwconv_lk_bwd_data_bf16p(const uint16_t* dy_big, const uint16_t* dy_sma
     if (KS != 0 && KS != 5) return PPEA_ERR_UNSUPPORTED;
     return dispatch<1>(dy_big, dy_small, (const uint16_t*)packed_big_flip, (const uint16_t*)packed_small_flip, dx,
                        nullptr, N, C, H, W, K, KS, (hipStream_t)stream);
+}
+
+// Host only (no device call, no stream): the kernel and the launch geometry the entry points above go by for this shape,
+// answered by the launchers themselves (see plan_rb / plan_bm).  mode 0: forward, 1: data gradient; variant 0: plain,
+// 1: with statistics, 2: fused input BatchNorm, 3: bias + activation.  plan [24] as laid out in include/ppea_depth.h;
+// plan[0] == 0: no MFMA kernel serves the shape (the entry point returns PPEA_ERR_UNSUPPORTED).
+int ppea_dwconv_lk_plan(int N, int C, int H, int W, int K, int KS, int mode, int variant, int* plan) {
+    if (plan == nullptr || mode < 0 || mode > 1 || variant < 0 || variant > 3) return PPEA_ERR_ARG;
+    for (int i = 0; i < LK_PLAN_INTS; ++i) plan[i] = 0;
+    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (KS != 0 && KS != 5)) return 0;
+    if (mode == 1 && variant != 0) return 0;
+    if ((variant == 2 && KS != 5) || (variant == 3 && KS != 0)) return 0;
+    int err;
+    if (variant == 3) {
+        switch (K) {
+            case 31: err = launch_bias_act<31>(nullptr, nullptr, nullptr, nullptr, 0, N, C, H, W, nullptr, plan); break;
+            case 29: err = launch_bias_act<29>(nullptr, nullptr, nullptr, nullptr, 0, N, C, H, W, nullptr, plan); break;
+            case 27: err = launch_bias_act<27>(nullptr, nullptr, nullptr, nullptr, 0, N, C, H, W, nullptr, plan); break;
+            case 13: err = launch_bias_act<13>(nullptr, nullptr, nullptr, nullptr, 0, N, C, H, W, nullptr, plan); break;
+            default: err = PPEA_ERR_UNSUPPORTED;
+        }
+    } else {
+        const BnIn bn{nullptr, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // routes only
+        const BnIn* bnp = variant == 2 ? &bn : nullptr;
+        err = mode == 0 ? dispatch<0>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, C, H, W, K, KS, nullptr, nullptr, nullptr, bnp, plan)
+                        : dispatch<1>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, C, H, W, K, KS, nullptr, nullptr, nullptr, bnp, plan);
+    }
+    if (err == PPEA_ERR_UNSUPPORTED) {
+        for (int i = 0; i < LK_PLAN_INTS; ++i) plan[i] = 0;
+        return 0;
+    }
+    return err;
+}
+
+// Test support, host only: ppea_dwconv_lk_plan over the grid N 1..Nmax x C in Cs[nC] x H 1..Hmax x W 1..Wmax, folded.
+// seen [1 << 14] bytes: seen[key] = 1 for every plan met,
+//   row-band    key = 1 | nseg_i << 2 | WS << 4 | BN << 5 | BA << 6 | band_i << 7 | (G > 1) << 9 | (bands > 1) << 10 | fast << 11
+//                     | (ipw > 1) << 12                         nseg_i: 0, 1, 2 for NSEG 2, 3, 5;  band_i = band / 16 - 1
+//   batch-major key = 2 | h_i << 2 | NTX << 4 | BN << 7 | (VEC == 8) << 8 | gi_i << 9 | (wgpc > 1) << 11
+//                                                               h_i: 0..3 for H 6, 12, 24, 48;  gi_i = gi / 4 - 1
+// summary [4] = shapes served, largest lds_bytes, plans with !(ipw * wpc >= items_per_channel > ipw * (wpc - 1)), shapes not served.
+int ppea_dwconv_lk_plan_sweep(int K, int KS, int mode, int variant, int Nmax, const int* Cs, int nC, int Hmax, int Wmax,
+                              unsigned char* seen, long* summary) {
+    if (Cs == nullptr || seen == nullptr || summary == nullptr) return PPEA_ERR_ARG;
+    for (int i = 0; i < (1 << 14); ++i) seen[i] = 0;
+    summary[0] = summary[1] = summary[2] = summary[3] = 0;
+    int p[LK_PLAN_INTS];
+    for (int N = 1; N <= Nmax; ++N)
+        for (int ci = 0; ci < nC; ++ci)
+            for (int H = 1; H <= Hmax; ++H)
+                for (int W = 1; W <= Wmax; ++W) {
+                    const int err = ppea_dwconv_lk_plan(N, Cs[ci], H, W, K, KS, mode, variant, p);
+                    if (err != 0) return err;
+                    if (p[0] == 0) { ++summary[3]; continue; }
+                    ++summary[0];
+                    if (p[2] > summary[1]) summary[1] = p[2];
+                    int key;
+                    if (p[0] == 1) {
+                        key = 1 | (p[3] == 2 ? 0 : p[3] == 3 ? 1 : 2) << 2 | p[4] << 4 | p[5] << 5 | p[6] << 6 | (p[7] / 16 - 1) << 7 |
+                              (p[8] > 1) << 9 | (p[9] > 1) << 10 | p[14] << 11 | (p[13] > 1) << 12;
+                        if (!((long)p[13] * p[12] >= p[11] && p[11] > (long)p[13] * (p[12] - 1))) ++summary[2];
+                    } else {
+                        key = 2 | (p[15] == 6 ? 0 : p[15] == 12 ? 1 : p[15] == 24 ? 2 : 3) << 2 | p[17] << 4 | p[5] << 7 |
+                              (p[19] == 8) << 8 | (p[20] / 4 - 1) << 9 | (p[22] > 1) << 11;
+                    }
+                    seen[key & ((1 << 14) - 1)] = 1;
+                }
+    return 0;
 }
 
 }  // extern "C"

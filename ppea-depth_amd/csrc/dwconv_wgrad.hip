@@ -44,6 +44,19 @@ inline int lk_wgrad_rows_per_part(int N, int C, int H) {
 }
 __host__ __device__ inline int lk_row_elems(int W) { return ((W + 15) & ~15) + 40; }          // halo + row + the reach of the last fragment
 
+// The host decisions of a launch (no device call): the launch goes by them and ppea_dwconv_lk_bwd_filter_plan reports them.
+struct WgPlan { int parts, rows_per_part, rounds, vec, last_rows; size_t lds; };
+inline WgPlan lk_wgrad_plan(int N, int C, int H, int W) {
+    WgPlan p;
+    p.parts = lk_wgrad_parts(N, C, H);
+    p.rows_per_part = lk_wgrad_rows_per_part(N, C, H);
+    p.rounds = (p.rows_per_part + WAVES - 1) / WAVES;                        // of a full part (the kernel's `rounds`)
+    p.vec = (W & 7) == 0 ? 1 : 0;                                            // the kernel's `vec`
+    p.last_rows = (int)((long)N * H - (long)(p.parts - 1) * p.rows_per_part);
+    p.lds = (size_t)WAVES * lk_row_elems(W) * sizeof(uint16_t);
+    return p;
+}
+
 __device__ __forceinline__ void wave_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
@@ -177,8 +190,9 @@ int ppea_dwconv_lk_bwd_filter_bf16(const uint16_t* x, const uint16_t* dy_big, co
         (KS != 0) != (dy_small != nullptr) || (KS != 0) != (dw_small != nullptr))
         return PPEA_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    const int parts = lk_wgrad_parts(N, C, H), rpp = lk_wgrad_rows_per_part(N, C, H);
-    const size_t smem = (size_t)WAVES * lk_row_elems(W) * sizeof(uint16_t);
+    const WgPlan pl = lk_wgrad_plan(N, C, H, W);
+    const int parts = pl.parts, rpp = pl.rows_per_part;
+    const size_t smem = pl.lds;
     hipLaunchKernelGGL(dwconv_lk_bwd_filter_mfma, dim3((unsigned)C, (unsigned)parts), dim3(256), smem, st, x, dy_big, dy_small,
                        (float*)workspace, N, C, H, W, K, KS, rpp);
     const int r = launch_status();
@@ -187,6 +201,17 @@ int ppea_dwconv_lk_bwd_filter_bf16(const uint16_t* x, const uint16_t* dy_big, co
     hipLaunchKernelGGL(dwconv_lk_bwd_filter_sum, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const float*)workspace,
                        dw_big, dw_small, C, parts, K * K, KS * KS);
     return launch_status();
+}
+
+// Host only: plan[0..5] = parts, rows_per_part, rounds (of a full part), vec (W % 8 == 0), dynamic LDS bytes, rows of the
+// last part, as ppea_dwconv_lk_bwd_filter_bf16 launches; PPEA_ERR_UNSUPPORTED where that call returns it.
+int ppea_dwconv_lk_bwd_filter_plan(int N, int C, int H, int W, int K, int KS, int* plan) {
+    if (plan == nullptr) return PPEA_ERR_ARG;
+    if (!lk_wgrad_served(N, C, H, W, K, KS)) return PPEA_ERR_UNSUPPORTED;
+    const WgPlan pl = lk_wgrad_plan(N, C, H, W);
+    plan[0] = pl.parts; plan[1] = pl.rows_per_part; plan[2] = pl.rounds; plan[3] = pl.vec; plan[4] = (int)pl.lds;
+    plan[5] = pl.last_rows;
+    return 0;
 }
 
 }  // extern "C"

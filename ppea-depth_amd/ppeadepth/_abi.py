@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 21
+ABI_VERSION = 22
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -167,6 +167,10 @@ SIGNATURES = {
     "ppea_nhwc_up2cat_bwd_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ppea_nhwc_up2cat_bwd_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ppea_dwconv_lk_stats_partials": [_i] * 6,
+    "ppea_dwconv_lk_plan": [_i] * 8 + [_vp],
+    "ppea_dwconv_lk_plan_sweep": [_i] * 5 + [_vp, _i, _i, _i, _vp, _vp],
+    "ppea_dwconv_lk_bwd_filter_plan": [_i] * 6 + [_vp],
+    "ppea_dwconv_lk_f32_plan": [_i] * 3 + [_vp],
     "ppea_dwconv_lk_fwd_stats_bf16p": [_vp] * 6 + [_i] * 6 + [_vp],
     "ppea_pwconv_stats_partials": [_i] * 4,
     "ppea_pwconv_stats_bf16": [_vp] * 5 + [_i] * 4 + [_vp],

@@ -2475,6 +2475,57 @@ def conv_wgrad_plan(N, Cin, Cout, K, stride, Ho, Wo):
     return p
 
 
+DWCONV_LK_PLAN_FIELDS = ("family", "partials", "lds_bytes", "NSEG", "WS", "BN", "BA", "band", "G", "bands", "segs",
+                         "items_per_channel", "wpc", "ipw", "fast", "H", "NY", "NTX", "RS", "VEC", "gi", "ngroups", "wgpc", "cpw")
+DWCONV_LK_VARIANTS = ("plain", "stats", "bn", "bias_act")
+
+
+def dwconv_lk_plan(N, C, H, W, K, KS, mode=0, variant="plain"):
+    """The kernel and launch geometry the MFMA depthwise entry points go by (host only, works without a device), as a dict
+    of DWCONV_LK_PLAN_FIELDS.  mode 0 forward / 1 data gradient; variant one of DWCONV_LK_VARIANTS.  family 0: not served,
+    1: dwconv_mfma_kernel<K, KS, mode, NSEG, BN, WS, BA>, 2: dwconv_bm_kernel<K, KS, mode, H, NY, NTX, RS, BN>."""
+    out = (_ct.c_int * 24)()
+    call("ppea_dwconv_lk_plan", N, C, H, W, K, KS, mode, DWCONV_LK_VARIANTS.index(variant), out)
+    return dict(zip(DWCONV_LK_PLAN_FIELDS, out))
+
+
+def dwconv_lk_plan_sweep(K, KS, mode, variant, Nmax, Cs, Hmax, Wmax):
+    """dwconv_lk_plan over N 1..Nmax x Cs x H 1..Hmax x W 1..Wmax (host only) -> (set of the distinct plans met, each a
+    dict of the fields that tell arms and paths apart, summary dict)."""
+    seen = (_ct.c_ubyte * (1 << 14))()
+    summary = (_ct.c_long * 4)()
+    cs = (_ct.c_int * len(Cs))(*Cs)
+    call("ppea_dwconv_lk_plan_sweep", K, KS, mode, DWCONV_LK_VARIANTS.index(variant), Nmax, cs, len(Cs), Hmax, Wmax, seen, summary)
+    plans = []
+    for key in range(1 << 14):
+        if not seen[key]:
+            continue
+        if key & 3 == 1:
+            plans.append(dict(family=1, NSEG=(2, 3, 5)[(key >> 2) & 3], WS=(key >> 4) & 1, BN=(key >> 5) & 1, BA=(key >> 6) & 1,
+                              band=16 * (((key >> 7) & 3) + 1), stacked=(key >> 9) & 1, multiband=(key >> 10) & 1,
+                              fast=(key >> 11) & 1, multi_item=(key >> 12) & 1))
+        else:
+            plans.append(dict(family=2, H=(6, 12, 24, 48)[(key >> 2) & 3], NTX=(key >> 4) & 7, BN=(key >> 7) & 1,
+                              VEC=8 if (key >> 8) & 1 else 4, gi=4 * (((key >> 9) & 3) + 1), multi_wg=(key >> 11) & 1))
+    return plans, dict(zip(("served", "max_lds_bytes", "bad_item_split", "not_served"), summary))
+
+
+def dwconv_lk_bwd_filter_plan(N, C, H, W, K, KS):
+    """dict(parts, rows_per_part, rounds, vec, lds_bytes, last_rows) of ppea_dwconv_lk_bwd_filter_bf16 (host only), or None
+    where that kernel does not serve the shape."""
+    out = (_ct.c_int * 6)()
+    if not try_call("ppea_dwconv_lk_bwd_filter_plan", N, C, H, W, K, KS, out):
+        return None
+    return dict(zip(("parts", "rows_per_part", "rounds", "vec", "lds_bytes", "last_rows"), out))
+
+
+def dwconv_lk_f32_plan(H, W, K):
+    """Index of the CFGS_<K> tile (csrc/dwconv_lk.hip) the fp32 vector kernel runs an H x W plane on; -1: the generic kernel."""
+    out = (_ct.c_int * 1)()
+    call("ppea_dwconv_lk_f32_plan", H, W, K, out)
+    return out[0]
+
+
 def conv_supported(x, w):
     return (x.is_cuda and x.dtype == _BF16 and x.dim() == 4 and x.shape[1] % 8 == 0 and w.shape[2] <= 7
             and w.shape[3] <= 7)

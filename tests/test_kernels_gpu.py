@@ -97,6 +97,12 @@ def test_dwconv_bf16_mfma(device, K, N, C, H, W):
     """bf16 I/O on the matrix cores (banded-Toeplitz MFMA kernel): bf16 activations and bf16-rounded
     filters (what autocast feeds a conv), fp32 accumulation, one bf16 rounding of the output."""
     ops = _ops()
+    # the arms the parameter list's comments claim, from the library's own plan (family 1 row-band, 2 batch-major)
+    fwd, dgrad = (ops.dwconv_lk_plan(N, C, H, W, K, 5, mode) for mode in (0, 1))
+    if (K, H) in ((27, 12), (13, 6), (29, 24)) and W % 4 == 0 and W <= 80:
+        assert (fwd["family"], fwd["H"], dgrad["family"], dgrad["H"]) == (2, H, 2, H), (fwd, dgrad)
+    if (K, H) == (31, 48) and N >= 12:
+        assert (dgrad["family"], dgrad["H"], dgrad["NY"], dgrad["RS"]) == (2, 48, 12, 4) and fwd["family"] == 1, (fwd, dgrad)
     x = torch.randn(N, C, H, W, generator=_g(K + H)).bfloat16()
     wb = torch.randn(C, 1, K, K, generator=_g(8)) / K
     ws = torch.randn(C, 1, 5, 5, generator=_g(9)) / 5
@@ -154,6 +160,8 @@ def test_dwconv_bf16_mfma_full_size_vs_fp32_kernel(device, N, C, H, W, K):
     Tolerance: both accumulate in fp32; the MFMA path rounds its result to bf16 once (2^-8 relative) and sums the
     K*K taps in a different order (a few 1e-4 of the output scale)."""
     ops = _ops()
+    if H in (12, 6):                                     # "batch-major variant": so says the plan, in both directions
+        assert [ops.dwconv_lk_plan(N, C, H, W, K, 5, mode)["family"] for mode in (0, 1)] == [2, 2]
     g = torch.Generator(device="cpu").manual_seed(21)
     wb = (torch.randn(C, 1, K, K, generator=g) / K).bfloat16().float().to(device)
     ws = (torch.randn(C, 1, 5, 5, generator=g) / 5).bfloat16().float().to(device)
