@@ -823,6 +823,19 @@ int ppea_adam_flat_f32(float* p, const float* g, float* m, float* v, void* w16, 
 int ppea_adam_flat_scaled_f32(float* p, const float* g, float* m, float* v, void* w16, long n, long n_lo,
                               const float* state, float beta1, float beta2, float eps, float grad_scale, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Scattered state <-> one contiguous buffer in ONE launch (checkpoints).  table: device int64 [nseg][4] =
+ * {address of the segment, byte offset in the packed buffer, byte count, first work unit}; a work unit is
+ * ppea_pack_unit_bytes() bytes of one segment (the last unit of a segment may be shorter, an empty segment owns none),
+ * `first work unit` is the running sum of the units of the segments before, `units` their total (= the grid).  Packed
+ * offsets are multiples of 16; a segment's address needs the alignment of its elements only (1, 2, 4 or 8 bytes): a unit
+ * is copied with the widest access (<= 16 bytes) that both sides are aligned to, its last bytes one by one.  Byte-exact,
+ * dtype-agnostic; exactly the listed bytes are read and written.  pack: segments -> packed; unpack: packed -> segments.
+ * ---------------------------------------------------------------------------------------- */
+long ppea_pack_unit_bytes(void);
+int ppea_pack_segments(const void* table, int nseg, long units, void* packed, void* stream);
+int ppea_unpack_segments(const void* table, int nseg, long units, const void* packed, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

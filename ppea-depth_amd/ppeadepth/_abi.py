@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 22
+ABI_VERSION = 23
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -206,6 +206,9 @@ SIGNATURES = {
     "ppea_color_jitter_workspace_bytes": [_i, _i, _i],
     "ppea_color_jitter_u8": [_vp] * 6 + [_i] * 3 + [_vp],
     "ppea_repeat_rows_f32": [_vp, _vp, _i, _i, _i, _vp],
+    "ppea_pack_unit_bytes": [],
+    "ppea_pack_segments": [_vp, _i, _l, _vp, _vp],
+    "ppea_unpack_segments": [_vp, _i, _l, _vp, _vp],
 }
 
 

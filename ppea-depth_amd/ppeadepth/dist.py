@@ -13,7 +13,11 @@ stream that produced a range's gradients -- and on that stream's own communicato
 the last gradient of the range (`FlatGrads.install_hooks`; ranges = branches of the step, laid out in the order
 backward finishes them).
 """
+import contextlib
+import copy
 import os
+import random
+import threading
 
 import torch
 import torch.distributed as dist
@@ -309,6 +313,34 @@ def _branch_of(name):
     return "pose"            # pose_encoder, pose (and anything else: launched after backward if streams mix)
 
 
+class PendingCheckpoint:
+    """A checkpoint whose device work is enqueued and whose host work (waiting for the copy, re-ordering, writing) is
+    still to do: `wait()` does it -- or joins the writer thread that does -- and returns the documents."""
+
+    def __init__(self, finish, threaded=False):
+        self._finish, self._result, self._error, self._done = finish, None, None, False
+        self._thread = threading.Thread(target=self._run, daemon=True) if threaded else None
+        if self._thread is not None:
+            self._thread.start()
+
+    def _run(self):
+        try:
+            self._result = self._finish()
+        except BaseException as e:              # raised again by wait(), in the caller's thread
+            self._error = e
+
+    def wait(self):
+        if not self._done:
+            if self._thread is not None:
+                self._thread.join()
+            else:
+                self._run()
+            self._done, self._finish = True, None
+        if self._error is not None:
+            raise self._error
+        return self._result
+
+
 class TrainEngine:
     """process_batch -> backward -> gradient exchange -> Adam step (trainer.py:345-351)."""
 
@@ -380,6 +412,9 @@ class TrainEngine:
         # nodes remember the stream they were created on, and a captured backward must not touch the
         # legacy default stream.
         self.stream = torch.cuda.Stream(self.params[0].device) if on_gpu else None
+        # checkpoints (below): the pack layout and the staging buffers are built at the first save and kept
+        self._ckpt_layout = self._ckpt_stage = self._ckpt_host = self._ckpt_copy_stream = self._ckpt_pending = None
+        self._ckpt_frozen = {}
 
     # ---- bf16 parameters with fp32 masters -----------------------------------------------------------
     # Under autocast every dense conv / linear casts its fp32 weight to bf16 on each use (~730 cast kernels
@@ -570,6 +605,286 @@ class TrainEngine:
             t.copy_(s)
         self.trainer.depth_bin_tracker.updated = snap[1]
         torch.cuda.synchronize()
+
+    # ---- checkpoints: the reference's three documents (checkpoint.py) out of / into the live engine ----------------
+    # The engine's layout differs from torch's in everything a file cares about: the trainable tensors are views into one
+    # flat fp32 buffer in a branch-sorted, bf16-first order, their moments likewise, there is ONE step counter and the
+    # learning rate is a device scalar.  `checkpoint_state` translates that into `model.pth` / `track.pth` / `adam.pth`
+    # documents in the REFERENCE's parameter order (by parameter identity); `load_checkpoint_state` puts them back IN
+    # PLACE, so it is valid after `capture()` as well.  The mutable state -- P | M | V, the step / learning-rate scalars,
+    # the tracker and every buffer of the model (~1 300 tensors) -- crosses the bus as ONE packed buffer
+    # (ops.pack_segments: one launch on the step stream, one copy).  With several ranks every rank calls
+    # `checkpoint_state` (the tracker's `compute()` is a collective); that path is unverified, and only the calling
+    # rank's random streams are stored.
+    def _ckpt_order(self):
+        """-> perm: the engine index of the j-th tensor of `[p for p in model.parameters() if p.requires_grad]`
+        (trainer.py:141-142: what index j of the reference's adam.pth means)."""
+        from ._abi import PpeaKernelError
+        ref = [p for p in self.trainer._module().parameters() if p.requires_grad]
+        pos = {id(p): i for i, p in enumerate(self.params)}
+        if len(ref) != len(pos) or any(id(p) not in pos for p in ref):
+            raise PpeaKernelError("the model's trainable set is not the one this engine was built on")
+        return [pos[id(p)] for p in ref], pos
+
+    def _ckpt_entries(self):
+        """[(state_dict key, kind, tensor)]: kind "train" (Adam updates it), "frozen" (a parameter no step writes) or
+        "buffer" (written by forward passes: BatchNorm running statistics and counters; every buffer counts as mutable)."""
+        sd = self.trainer._module().state_dict(keep_vars=True)
+        return [(k, ("train" if v.requires_grad else "frozen") if isinstance(v, torch.nn.Parameter) else "buffer", v)
+                for k, v in sd.items()]
+
+    def _ckpt_frozen_copy(self, key, p, device):
+        """fp32 copy of a frozen parameter on `device`, made once per engine (again when the tensor was written or moved);
+        a frozen fp32 tensor that already lives on `device` is shared, not copied."""
+        hit = self._ckpt_frozen.get((key, device))
+        if hit is not None and hit[0] == p._version and hit[1] == p.data_ptr():
+            return hit[2]
+        t = p.detach() if (p.device == device and p.dtype == torch.float32) else p.detach().to(device).float()
+        self._ckpt_frozen[(key, device)] = (p._version, p.data_ptr(), t)
+        return t
+
+    def _ckpt_segments(self, entries, bins=None):
+        tr = self.trainer.depth_bin_tracker
+        mn, mx = bins if bins is not None else (tr.min_depth, tr.max_depth)
+        return [self.P, self.M, self.V, self.adam_state, mn.reshape(()), mx.reshape(())] + \
+               [v.detach() for _, kind, v in entries if kind == "buffer"]
+
+    def _ckpt_buffers(self, segs, device):
+        """Pack layout, device staging buffer and host (pinned) buffer: built once, kept while the state keeps its sizes."""
+        from . import ops
+        nbytes = [t.numel() * t.element_size() for t in segs]
+        if self._ckpt_layout is None or self._ckpt_layout.nbytes != nbytes:
+            self._ckpt_layout = ops.SegmentLayout(segs)
+            self._ckpt_stage = torch.zeros(max(self._ckpt_layout.total, 16), dtype=torch.uint8, device=self.P.device)
+            self._ckpt_host = None
+            self._ckpt_copy_stream = torch.cuda.Stream(self.P.device)
+        if self._ckpt_host is None or self._ckpt_host.device != device:
+            self._ckpt_host = torch.zeros(self._ckpt_stage.numel(), dtype=torch.uint8, device=device,
+                                          pin_memory=device.type == "cpu")
+        return self._ckpt_layout, self._ckpt_stage, self._ckpt_host
+
+    def _ckpt_wait_pending(self):
+        if self._ckpt_pending is not None:      # one staging buffer: a second save waits for the first
+            pending, self._ckpt_pending = self._ckpt_pending, None
+            pending.wait()
+
+    @torch.no_grad()
+    def checkpoint_state(self, device="cpu", blocking=True, then=None):
+        """-> checkpoint.Documents(model, track, adam) of the engine as it stands at this step boundary, on `device`.
+        Trainable parameters are the fp32 masters, moments and masters are re-ordered to the reference's parameter order,
+        every index carries step = the engine's one counter; a document of an engine that has not stepped has no state
+        (as torch's).  Frozen parameters may be shared between documents (and with the model, on its own device).
+        blocking=False: the pack launch is enqueued on the step stream now, the copy to pinned host memory runs on a copy
+        stream behind it, and a `PendingCheckpoint` is returned; later steps and replays may run before `wait()`, they
+        cannot change what it returns.  `then(documents)`: host work to run when the documents exist (with blocking=False
+        on a writer thread)."""
+        from . import checkpoint, rng
+        device = torch.device(device)
+        self._ckpt_wait_pending()
+        perm, pos = self._ckpt_order()
+        entries = self._ckpt_entries()
+        trainer, opt, tr = self.trainer, self.trainer.opt, self.trainer.depth_bin_tracker
+        bins_live = checkpoint.bins_live(opt, trainer.freeze_tp)
+        on_gpu = self.stream is not None
+        ppea = {"version": checkpoint.FORMAT_VERSION, "step": int(trainer.step), "epoch": int(getattr(trainer, "epoch", 0)),
+                "scheduler": copy.deepcopy(self.scheduler.state_dict()), "lr": float(self.optimizer.param_groups[0]["lr"]),
+                "bins_updated": bool(tr.updated), "rng_mode": rng.get_mode(), "python_random": random.getstate(),
+                "torch_cpu_rng": torch.get_rng_state(),
+                "device_rng": torch.cuda.get_rng_state(self.params[0].device) if on_gpu else None,
+                "world_size": world_size(), "bf16_params": self.masters is not None}
+        groups = copy.deepcopy(self.optimizer.state_dict()["param_groups"])
+        groups[0]["params"] = list(range(len(perm)))
+        frozen = {k: self._ckpt_frozen_copy(k, v, device) for k, kind, v in entries if kind == "frozen"}
+        index = {k: pos[id(v)] for k, kind, v in entries if kind == "train"}
+        kinds = [(k, kind) for k, kind, _ in entries]
+
+        if not self.flat_adam:
+            # torch's optimizer holds the state (CPU engine, fused_adam=False): per-tensor copies, made now
+            def to(t):
+                return t.detach().to(device, copy=True)
+            bins = tuple(to(b.reshape(())) for b in tr.compute()) if bins_live else None
+            model_sd = {k: to(self.opt_params[index[k]]) if kind == "train" else frozen[k] if kind == "frozen" else to(v)
+                        for k, kind, v in entries}
+            osd = self.optimizer.state_dict()
+            state = {i: {k: to(x) if torch.is_tensor(x) else x for k, x in st.items()} for i, st in osd["state"].items()}
+            adam_sd = checkpoint.remap_adam({"state": state, "param_groups": groups}, perm)
+            docs = checkpoint.Documents(model_sd, checkpoint.track_document(opt, trainer.freeze_tp, bins, ppea), adam_sd)
+            if then is not None:
+                then(docs)
+            return docs if blocking else PendingCheckpoint(lambda: docs)
+
+        cur = torch.cuda.current_stream()
+        self.stream.wait_stream(cur)
+        with torch.cuda.stream(self.stream):
+            segs = self._ckpt_segments(entries, tr.compute() if bins_live else None)
+            layout, stage, host = self._ckpt_buffers(segs, device)
+            from . import ops
+            ops.pack_segments(segs, out=stage, layout=layout)
+            packed = torch.cuda.Event()
+            packed.record(self.stream)
+        copies = self._ckpt_copy_stream
+        copies.wait_event(packed)
+        with torch.cuda.stream(copies):
+            host.copy_(stage, non_blocking=True)
+            copied = torch.cuda.Event()
+            copied.record(copies)
+        offsets = list(self.flat.offsets)
+        shapes = [tuple(t.shape) for t in self.opt_params]
+        buffer_keys = [k for k, kind in kinds if kind == "buffer"]
+
+        def finish():                           # host work only (and the wait for the copy)
+            copied.synchronize()
+            views = layout.views(host)
+            hP, hM, hV, hstate, hmn, hmx = views[:6]
+            hbuf = dict(zip(buffer_keys, views[6:]))
+
+            def cut(flat, i):
+                n = 1
+                for d in shapes[i]:
+                    n *= d
+                return flat[offsets[i]:offsets[i] + n].view(shapes[i]).clone()
+            model_sd = {k: cut(hP, index[k]) if kind == "train" else frozen[k] if kind == "frozen" else hbuf[k].clone()
+                        for k, kind in kinds}
+            step = float(hstate[0])
+            state = {}
+            if step > 0:
+                state = {j: {"step": torch.tensor(step, device=device), "exp_avg": cut(hM, i), "exp_avg_sq": cut(hV, i)}
+                         for j, i in enumerate(perm)}
+            bins = (hmn.clone(), hmx.clone()) if bins_live else None
+            docs = checkpoint.Documents(model_sd, checkpoint.track_document(opt, trainer.freeze_tp, bins, ppea),
+                                        {"state": state, "param_groups": groups})
+            if then is not None:
+                then(docs)
+            return docs
+
+        pending = PendingCheckpoint(finish, threaded=not blocking and then is not None)
+        if blocking:
+            return pending.wait()
+        self._ckpt_pending = pending
+        return pending
+
+    @torch.no_grad()
+    def load_checkpoint_state(self, docs):
+        """Put `(model, track, adam)` documents back IN PLACE: valid before and after `capture()` (the graph's addresses
+        stay valid).  model: applied like `load_state_dict(strict=False)` -- trainable tensors into the fp32 masters (P),
+        the bf16 working copies refreshed as W16 = bf16(P) with the Adam kernel's rounding (nearest even), BatchNorm
+        running statistics and counters.  adam (None: the optimizer is left as it is): moments by the reference's index,
+        the one step counter, the learning rate.  track (None: nothing else is touched): the tracker, and from its "ppea"
+        key the scheduler, `trainer.step`, the RNG mode and the three generator states.
+        ValueError -- before anything is written -- when adam disagrees with the trainable set in count or shapes, or
+        holds different step counts per index.  After `capture()` a frozen weight that differs from the loaded one is an
+        error: the captured step reads kernel-layout images of the frozen weights that were built before the capture.
+        -> (missing_keys, unexpected_keys) of the model document."""
+        from . import checkpoint, rng
+        from ._abi import PpeaKernelError
+        docs = checkpoint.Documents(*docs)
+        self._ckpt_wait_pending()
+        perm, pos = self._ckpt_order()
+        entries = self._ckpt_entries()
+        trainer, tr = self.trainer, self.trainer.depth_bin_tracker
+        step = None
+        if docs.adam is not None:
+            step = checkpoint.check_adam(docs.adam, [tuple(self.opt_params[i].shape) for i in perm])
+        known = {k: v for k, _, v in entries}
+        for k, v in docs.model.items():
+            if k in known and tuple(v.shape) != tuple(known[k].shape):
+                raise RuntimeError(f"size mismatch for {k}: checkpoint {tuple(v.shape)}, model {tuple(known[k].shape)}")
+        keys = torch.nn.modules.module._IncompatibleKeys([k for k in known if k not in docs.model],
+                                                         [k for k in docs.model if k not in known])
+        track = docs.track if docs.track is not None else {}
+        ppea = track.get("ppea")
+        bins = (track.get("min_depth_bin"), track.get("max_depth_bin"))
+        bins = bins if bins[0] is not None and bins[1] is not None else None
+        on_gpu = self.stream is not None
+        if on_gpu:
+            torch.cuda.synchronize()
+        for k, kind, v in entries:
+            if kind != "frozen" or k not in docs.model:
+                continue
+            if self.graph is None:
+                v.copy_(docs.model[k])
+            elif not torch.equal(v.detach(), docs.model[k].to(device=v.device, dtype=v.dtype)):
+                raise PpeaKernelError(f"load_checkpoint_state after capture(): the frozen weight {k} differs from the "
+                                      "engine's; load checkpoints with other frozen weights before capture()")
+        g0 = self.optimizer.param_groups[0]
+        if self.flat_adam:
+            if docs.adam is not None:
+                for k in ("lr", "betas", "eps", "initial_lr"):
+                    if k in docs.adam["param_groups"][0]:
+                        g0[k] = docs.adam["param_groups"][0][k]
+            if ppea is not None:
+                self.scheduler.load_state_dict(copy.deepcopy(ppea["scheduler"]))
+                g0["lr"] = float(ppea["lr"])
+            from . import ops
+            segs = self._ckpt_segments(entries)
+            layout, stage, _ = self._ckpt_buffers(segs, torch.device("cpu"))
+            ops.pack_segments(segs, out=stage, layout=layout)     # what the documents do not hold stays as it is
+            host = stage.cpu()
+            views = layout.views(host)
+            hP, hM, hV, hstate, hmn, hmx = views[:6]
+            hbuf = dict(zip([k for k, kind, _ in entries if kind == "buffer"], views[6:]))
+            offsets = self.flat.offsets
+
+            def put(flat, i, src):
+                t = self.opt_params[i]
+                flat[offsets[i]:offsets[i] + t.numel()].view(t.shape).copy_(src)
+            for k, kind, v in entries:
+                if k in docs.model and kind == "train":
+                    put(hP, pos[id(v)], docs.model[k])
+                elif k in docs.model and kind == "buffer":
+                    hbuf[k].copy_(docs.model[k])
+            if docs.adam is not None:
+                hM.zero_()
+                hV.zero_()
+                for j, st in docs.adam["state"].items():
+                    put(hM, perm[int(j)], st["exp_avg"])
+                    put(hV, perm[int(j)], st["exp_avg_sq"])
+                hstate[0] = step
+            hstate[1] = float(g0["lr"])
+            if bins is not None:
+                hmn.copy_(torch.as_tensor(bins[0]).reshape(()))
+                hmx.copy_(torch.as_tensor(bins[1]).reshape(()))
+                tr.updated = True
+            stage.copy_(host)
+            ops.unpack_segments(stage, layout, segs)
+            if self.n_lo:
+                self.W16[:self.n_lo].copy_(self.P[:self.n_lo])
+        else:
+            for k, kind, v in entries:
+                if k in docs.model and kind == "train":
+                    self.opt_params[pos[id(v)]].copy_(docs.model[k])
+                elif k in docs.model and kind == "buffer":
+                    v.copy_(docs.model[k])
+            if self._lo:
+                torch._foreach_copy_(self._lo, self._hi)
+            if docs.adam is not None:
+                inverse = [0] * len(perm)
+                for j, i in enumerate(perm):
+                    inverse[i] = j
+                sd = checkpoint.remap_adam(docs.adam, inverse)
+                for k in ("fused", "foreach", "capturable", "differentiable"):      # how THIS engine steps
+                    if k in g0:
+                        sd["param_groups"][0][k] = g0[k]
+                self.optimizer.load_state_dict(sd)
+                g0 = self.optimizer.param_groups[0]
+            if ppea is not None:
+                self.scheduler.load_state_dict(copy.deepcopy(ppea["scheduler"]))
+                g0["lr"] = float(ppea["lr"])
+            if bins is not None:
+                tr.load(*bins)
+        self.sync_lr()
+        if ppea is not None:
+            tr.updated = bool(ppea["bins_updated"])
+            trainer.step = int(ppea["step"])
+            trainer.epoch = int(ppea["epoch"])
+            rng.set_mode(ppea["rng_mode"])
+            random.setstate(ppea["python_random"])
+            torch.set_rng_state(ppea["torch_cpu_rng"])
+            if on_gpu and ppea["device_rng"] is not None:
+                torch.cuda.set_rng_state(ppea["device_rng"], self.params[0].device)
+        if on_gpu:
+            torch.cuda.synchronize()
+        return keys
 
     def mean_grads(self):
         """name -> gradient of this step as DDP would leave it (mean over ranks), whatever the exchange stored."""

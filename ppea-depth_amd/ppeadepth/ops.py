@@ -2783,3 +2783,84 @@ def nhwc_table_affine(x, ab, act=ACT_NONE, res=None):
     y = torch.empty_like(x)
     call(f"ppea_nhwc_bn_apply_{_suffix(x)}", _raw(x), _raw(res), ptr(ab), _raw(y), N * H * W, C, 1, int(act), stream_ptr())
     return y
+
+
+# ---------------------------------------------------------------------------------------------
+# scattered state <-> one contiguous buffer (checkpoints; csrc/state_pack.hip)
+# ---------------------------------------------------------------------------------------------
+class SegmentLayout:
+    """Where each tensor of a list sits in the packed buffer: `offsets` (bytes, multiples of 16), `nbytes`, `dtypes`,
+    `shapes`, `total` bytes.  The device table of (pointer, offset, bytes, first work unit) is built once and kept while the
+    tensors' addresses are the recorded ones -- state that is only ever updated in place keeps them -- and rebuilt when any
+    `data_ptr` differs at the next use."""
+
+    def __init__(self, tensors):
+        unit = int(_abi.lib.ppea_pack_unit_bytes())
+        self.dtypes = [t.dtype for t in tensors]
+        self.shapes = [tuple(t.shape) for t in tensors]
+        self.nbytes = [t.numel() * t.element_size() for t in tensors]
+        self.offsets, self.first_unit, at, units = [], [], 0, 0
+        for n in self.nbytes:
+            self.offsets.append(at)
+            self.first_unit.append(units)
+            at += (n + 15) // 16 * 16
+            units += (n + unit - 1) // unit
+        self.total, self.units = at, units
+        self._ptrs, self._table = None, None
+
+    def table(self, tensors):
+        if len(tensors) != len(self.nbytes):
+            raise PpeaKernelError(f"the layout describes {len(self.nbytes)} tensors, got {len(tensors)}")
+        dev = None
+        for t, n, dt in zip(tensors, self.nbytes, self.dtypes):
+            if not t.is_cuda:
+                raise PpeaKernelError("PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback); got a CPU tensor")
+            if not t.is_contiguous():
+                raise PpeaKernelError("non-contiguous tensor passed to a HIP kernel")
+            if t.numel() * t.element_size() != n or t.dtype != dt:
+                raise PpeaKernelError(f"tensor of {t.numel()} x {t.dtype} where the layout has {n} bytes of {dt}")
+            if dev is not None and t.device != dev:
+                raise PpeaKernelError("the segments of one launch live on one device")
+            dev = t.device
+        ptrs = tuple(t.data_ptr() for t in tensors)
+        if ptrs != self._ptrs:
+            rows = [[p, o, n, u] for p, o, n, u in zip(ptrs, self.offsets, self.nbytes, self.first_unit)]
+            self._table = torch.tensor(rows, dtype=torch.int64).to(dev)
+            self._ptrs = ptrs
+        return self._table
+
+    def views(self, buffer):
+        """The packed buffer (any device) as one tensor per segment, with the segment's dtype and shape."""
+        return [buffer[o:o + n].view(dt).view(shape)
+                for o, n, dt, shape in zip(self.offsets, self.nbytes, self.dtypes, self.shapes)]
+
+
+@torch.no_grad()
+def pack_segments(tensors, out=None, layout=None):
+    """Device tensors of any dtypes -> (uint8 buffer holding their bytes back to back at 16-byte aligned offsets, layout),
+    ONE launch.  `out`: a uint8 device buffer of at least `layout.total` bytes to write into (bytes past that, and the
+    padding between segments, are left alone); `layout`: the one an earlier call returned for these tensors."""
+    tensors = list(tensors)
+    if not tensors:
+        raise PpeaKernelError("pack_segments: no tensors")
+    if layout is None:
+        layout = SegmentLayout(tensors)
+    table = layout.table(tensors)
+    if out is None:
+        out = torch.zeros(max(layout.total, 16), dtype=torch.uint8, device=table.device)
+    if out.dtype != torch.uint8 or out.numel() < layout.total or out.device != table.device or out.data_ptr() % 16:
+        raise PpeaKernelError(f"pack_segments: out must be a 16-byte aligned uint8 buffer of >= {layout.total} bytes on {table.device}")
+    call("ppea_pack_segments", ptr(table), len(tensors), layout.units, ptr(out), stream_ptr())
+    return out, layout
+
+
+@torch.no_grad()
+def unpack_segments(buffer, layout, tensors):
+    """The reverse of `pack_segments`: the bytes of `buffer` written into `tensors` (in place), ONE launch."""
+    tensors = list(tensors)
+    table = layout.table(tensors)
+    if not buffer.is_cuda:
+        raise PpeaKernelError("PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback); got a CPU tensor")
+    if buffer.dtype != torch.uint8 or buffer.numel() < layout.total or buffer.device != table.device or buffer.data_ptr() % 16:
+        raise PpeaKernelError(f"unpack_segments: the buffer must be 16-byte aligned uint8 of >= {layout.total} bytes on {table.device}")
+    call("ppea_unpack_segments", ptr(table), len(tensors), layout.units, ptr(buffer), stream_ptr())

@@ -36,6 +36,10 @@ class MonodepthOptions:
         a("--dec_ratio", type=float, default=0.25)
         a("--pred_depth_scale_factor", type=float, default=1.0)
         a("--disable_median_scaling", action="store_true")
+        # checkpoints (options.py:174, 334, 468): the folder `Trainer.load_model` reads, model.pth only (--ktf), run name
+        a("--load_weights_folder", type=str)
+        a("--ktf", action="store_true")
+        a("--name", type=str, default="test")
         for flag in ("adapter", "use_checkpoint", "dc", "notadabins", "freeze_teacher_and_pose", "freeze_pose",
                      "no_ssim", "disable_automasking", "disable_motion_masking", "no_matching_augmentation",
                      "v1_multiscale", "use_future_frame", "train_cs", "ddad", "fullft_reb", "dec_only", "lps2",

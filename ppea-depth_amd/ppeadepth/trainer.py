@@ -119,6 +119,43 @@ class Trainer:
     def _module(self):
         return getattr(self.model, "module", self.model)
 
+    # ---- trainer.py:1290-1381: checkpoints (files: checkpoint.py; engine state: dist.TrainEngine) -------------------
+    def save_model_debug(self, save_folder, engine, blocking=True):
+        """model.pth / track.pth / adam.pth of the reference, from the live engine.  With several ranks EVERY rank calls this
+        (the tracker's `compute()` is a collective) and rank 0 writes.  blocking=False: the step loop goes on; the files
+        exist once `wait()` of the returned `PendingCheckpoint` has returned."""
+        from . import checkpoint
+        if getattr(self.opt, "debug", False):
+            print(f"save model at {save_folder}")
+        rank0 = not (torch.distributed.is_available() and torch.distributed.is_initialized()) \
+            or torch.distributed.get_rank() == 0
+        write = (lambda docs: checkpoint.write_folder(save_folder, *docs)) if rank0 else None
+        return engine.checkpoint_state(blocking=blocking, then=write)
+
+    def load_model(self, folder=None, engine=None, transfer=False):
+        """Load a checkpoint folder (default `opt.load_weights_folder`).  With an `engine`: model, tracker, optimizer,
+        schedule, step and random streams, in place (`TrainEngine.load_checkpoint_state`).  Without: model and tracker
+        only (inference, or a Stage-2 run that calls `dc_ft_init()` and builds its engine afterwards).  transfer (--ktf):
+        model.pth only.  An adam.pth that does not fit the trainable set is skipped with the reference's message."""
+        from . import checkpoint
+        folder = self.opt.load_weights_folder if folder is None else folder
+        docs = checkpoint.read_folder(folder, transfer)
+        module = self._module()
+        if engine is None:
+            keys = module.load_state_dict(docs.model, strict=False)
+            if docs.track is not None and docs.track.get("min_depth_bin") is not None \
+                    and docs.track.get("max_depth_bin") is not None:
+                self.depth_bin_tracker.load(docs.track["min_depth_bin"], docs.track["max_depth_bin"])
+        else:
+            try:
+                keys = engine.load_checkpoint_state(docs)
+            except ValueError:
+                print("Can't load Adam - using random")
+                keys = engine.load_checkpoint_state(docs._replace(adam=None))
+        if hasattr(module, "dc"):
+            module.dc = bool(getattr(self.opt, "dc", False))          # trainer.py:1358
+        return keys
+
     # ---- trainer.py:420-472 -----------------------------------------------------------------------
     def process_batch(self, inputs, is_train=False):
         tracker = self.depth_bin_tracker
