@@ -731,6 +731,13 @@ int ppea_depth_errors_mean_f64(const double* errors, double* mean, int n, void* 
  *   of all sources are numbered through and planes_per_item consecutive planes form an image.  flip [images] int32 or NULL:
  *   non-zero = the image is read mirrored (the flipped frame is never written); nonzero [images] int32 or NULL: set to
  *   whether the image holds a non-zero byte (one memset).  dst [planes][H][Wout].  One launch.
+ * ppea_lanczos_h_view_u8 (ABI 24): the same pass over VIEWS.  srcs = HOST array of nsrc <= 8 device pointers; image i of
+ *   source k is C channels of [H][Win] pixels, the byte of (c, y, x) at srcs[k] + i * item_stride + c * channel_stride +
+ *   y * row_stride + x * pixel_stride (all strides > 0; the window's x offset is folded into srcs[k]; a row's first to last
+ *   byte must fit row_stride).  The images of all sources are numbered through (flip / nonzero as above); dst
+ *   [images][C][H][Wout], planar.  C = 3, pixel_stride = 3, channel_stride = 1 (a decoder's HWC): one workgroup stages a
+ *   row's window once, in 16-byte loads wherever its address allows and byte by byte at the ends, and writes the three
+ *   channel rows; a row that does not fit the LDS is PPEA_ERR_UNSUPPORTED.  No byte outside the windows is read.  One launch.
  * ppea_lanczos_v_u8: columns of src [planes][Hin][W] -> dst [planes][Hout][W], planes <= 65535.  One launch.
  * ppea_color_jitter_u8: img [N][3][H][W] uint8 -> color = img / 255 and color_aug = jitter(img) / 255, both [N][3][H][W]
  *   fp32 (one correctly rounded division, as ToTensor).  params [N][10] int32: the order of the four operations
@@ -744,6 +751,9 @@ int ppea_depth_errors_mean_f64(const double* errors, double* mean, int n, void* 
 int ppea_lanczos_h_u8(const void* const* srcs, int nsrc, long planes_per_src, const int32_t* taps, int kmax,
                       const int32_t* flip, int planes_per_item, int32_t* nonzero, uint8_t* dst, int H, int Win, int Wout,
                       void* stream);
+int ppea_lanczos_h_view_u8(const void* const* srcs, int nsrc, int items_per_src, int C, long pixel_stride, long row_stride,
+                           long channel_stride, long item_stride, const int32_t* taps, int kmax, const int32_t* flip,
+                           int32_t* nonzero, uint8_t* dst, int H, int Win, int Wout, void* stream);
 int ppea_lanczos_v_u8(const uint8_t* src, const int32_t* taps, int kmax, uint8_t* dst, long planes, int Hin, int Hout,
                       int W, void* stream);
 long ppea_color_jitter_workspace_bytes(int N, int H, int W);

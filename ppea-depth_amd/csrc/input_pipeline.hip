@@ -6,6 +6,9 @@
 //               never materialised), then one thread per output pixel: int32 accumulator from 1 << 21 over the row's
 //               (xmin, n, coeffs[n]) entry of the tap table, >> 22, clip.  Every input byte is read exactly once, so the
 //               same pass marks the images that hold a non-zero byte (a missing neighbour frame is all zeros).
+//   lanczos_h_view3 / lanczos_h_view   the same pass over a window of a larger image given by byte strides: interleaved
+//               RGB (a JPEG decoder's HWC) staged once per row in 16-byte chunks and written as three channel rows, any
+//               other layout byte by byte; the planar output of lanczos_h, so everything downstream is unchanged.
 //   lanczos_v   the same arithmetic down the columns of the 8-bit intermediate, 4 columns per thread through 32-bit words
 //               when the row length allows.
 //   jitter_sum  the item's pointwise operations that precede contrast, then Pillow's RGB -> L; an exact integer sum per
@@ -86,6 +89,142 @@ __global__ __launch_bounds__(THREADS) void lanczos_h(Srcs srcs, long rows_per_sr
         const int r = i / Wout, x = i - r * Wout;
         const Taps t = taps_of(table, kmax, x, Win);
         const uint8_t* in = line + r * Win + t.lo;
+        int acc = 1 << (PRECISION_BITS - 1);
+        for (int k = 0; k < t.n; ++k) acc += (int)in[k] * t.c[k];
+        dst[(row0 + r) * Wout + x] = (uint8_t)clip8(acc);
+    }
+}
+
+// ---- horizontal pass over a VIEW: a window of a larger image, described by strides ---------------------------------
+// Rows of all images are numbered through; a workgroup's per-row bookkeeping lies behind the staged rows in the dynamic
+// LDS region (no static LDS: the region's base stays 16-byte aligned for the 128-bit writes).
+constexpr int VIEW_CHUNK = 16;                  // bytes per wide load
+constexpr int VIEW_META = MAX_RPB * (int)(sizeof(const uint8_t*) + 2 * sizeof(int));
+
+struct ViewRows {
+    const uint8_t** src;
+    int *flip, *nz;
+};
+__device__ __forceinline__ ViewRows view_rows(uint8_t* smem, size_t line_bytes) {
+    ViewRows v;
+    v.src = (const uint8_t**)(smem + line_bytes);           // line_bytes % 16 == 0
+    v.flip = (int*)(v.src + MAX_RPB);
+    v.nz = v.flip + MAX_RPB;
+    return v;
+}
+__device__ __forceinline__ const uint8_t* view_base(const Srcs& srcs, int s) {
+    const uint8_t* base = nullptr;
+#pragma unroll
+    for (int k = 0; k < MAX_SRCS; ++k) base = k == s ? srcs.p[k] : base;
+    return base;
+}
+
+// Interleaved pixels (pixel stride 3, channel stride 1): rows g = image * H + y.  The row's window, Win * 3 bytes, is
+// staged ONCE, as it lies in memory: 16-byte chunks at the alignment the source has (a window that starts at x0 * 3 is in
+// general not aligned), the partial chunk at either end byte by byte, so no byte outside the window is read.  One thread
+// per output pixel then writes the three channel rows; a flipped image is read mirrored.
+__global__ __launch_bounds__(THREADS) void lanczos_h_view3(Srcs srcs, int items_per_src, long row_stride, long item_stride,
+                                                           const int* __restrict__ table, int kmax,
+                                                           const int* __restrict__ flip, int* __restrict__ nonzero,
+                                                           uint8_t* __restrict__ dst, long rows, int H, int Win, int Wout,
+                                                           int rpb, int pitch) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];      // [rpb][pitch], then the rows' bookkeeping
+    const ViewRows vr = view_rows(smem, (size_t)rpb * pitch);
+    const long row0 = (long)blockIdx.x * rpb;
+    const int nr = (int)min((long)rpb, rows - row0);
+    if (threadIdx.x < nr) {
+        const long g = row0 + threadIdx.x;
+        const long n = g / H;
+        const int s = (int)(n / items_per_src);
+        vr.src[threadIdx.x] = view_base(srcs, s) + (n - (long)s * items_per_src) * item_stride + (g - n * H) * row_stride;
+        vr.flip[threadIdx.x] = flip && flip[n] != 0;
+        vr.nz[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    const int L = Win * 3, chunks = pitch / VIEW_CHUNK;
+    for (int i = threadIdx.x; i < nr * chunks; i += THREADS) {
+        const int r = i / chunks, j = i - r * chunks;
+        const uint8_t* p = vr.src[r];
+        const int b0 = j * VIEW_CHUNK - (int)((uintptr_t)p % VIEW_CHUNK);      // the chunk's first byte, window-relative
+        uint8_t* out = smem + (size_t)r * pitch + j * VIEW_CHUNK;
+        bool nz = false;
+        if (b0 >= 0 && b0 + VIEW_CHUNK <= L) {
+            const uint4 v = *(const uint4*)(p + b0);
+            *(uint4*)out = v;
+            nz = (v.x | v.y | v.z | v.w) != 0;
+        } else {
+            for (int q = 0; q < VIEW_CHUNK; ++q) {
+                const int b = b0 + q;
+                if (b >= 0 && b < L) {
+                    const uint8_t v = p[b];
+                    out[q] = v;
+                    nz |= v != 0;
+                }
+            }
+        }
+        if (nz) vr.nz[r] = 1;                   // every writer stores the same value
+    }
+    __syncthreads();
+    if (nonzero && threadIdx.x < nr && vr.nz[threadIdx.x]) {
+        int* flag = nonzero + (row0 + threadIdx.x) / H;
+        if (__atomic_load_n(flag, __ATOMIC_RELAXED) == 0) atomicOr(flag, 1);
+    }
+    const long plane = (long)H * Wout;
+    for (int i = threadIdx.x; i < nr * Wout; i += THREADS) {
+        const int r = i / Wout, x = i - r * Wout;
+        const Taps t = taps_of(table, kmax, x, Win);
+        const uint8_t* in = smem + (size_t)r * pitch + (int)((uintptr_t)vr.src[r] % VIEW_CHUNK);
+        const int first = vr.flip[r] ? Win - 1 - t.lo : t.lo, step = vr.flip[r] ? -3 : 3;
+        in += first * 3;
+        int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
+        for (int k = 0; k < t.n; ++k, in += step) {
+            const int c = t.c[k];
+            a0 += (int)in[0] * c, a1 += (int)in[1] * c, a2 += (int)in[2] * c;
+        }
+        const long g = row0 + r, n = g / H;
+        uint8_t* o = dst + (n * 3 * H + (g - n * H)) * Wout + x;
+        o[0] = (uint8_t)clip8(a0), o[plane] = (uint8_t)clip8(a1), o[2 * plane] = (uint8_t)clip8(a2);
+    }
+}
+
+// Any other strides: rows g = (image * C + c) * H + y, as the planar output numbers them; `lanczos_h` with the row's
+// bytes fetched one by one through the pixel stride.
+__global__ __launch_bounds__(THREADS) void lanczos_h_view(Srcs srcs, int items_per_src, int C, long pixel_stride,
+                                                          long row_stride, long channel_stride, long item_stride,
+                                                          const int* __restrict__ table, int kmax,
+                                                          const int* __restrict__ flip, int* __restrict__ nonzero,
+                                                          uint8_t* __restrict__ dst, long rows, int H, int Win, int Wout,
+                                                          int rpb, int pitch) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];      // [rpb][pitch], then the rows' bookkeeping
+    const ViewRows vr = view_rows(smem, (size_t)rpb * pitch);
+    const long row0 = (long)blockIdx.x * rpb;
+    const int nr = (int)min((long)rpb, rows - row0);
+    const long rows_per_item = (long)C * H;
+    if (threadIdx.x < nr) {
+        const long g = row0 + threadIdx.x;
+        const long n = g / rows_per_item, pl = g / H;
+        const int s = (int)(n / items_per_src);
+        vr.src[threadIdx.x] = view_base(srcs, s) + (n - (long)s * items_per_src) * item_stride +
+                              (pl - n * C) * channel_stride + (g - pl * H) * row_stride;
+        vr.flip[threadIdx.x] = flip && flip[n] != 0;
+        vr.nz[threadIdx.x] = 0;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < nr * Win; i += THREADS) {
+        const int r = i / Win, x = i - r * Win;
+        const uint8_t v = vr.src[r][x * pixel_stride];
+        smem[(size_t)r * pitch + (vr.flip[r] ? Win - 1 - x : x)] = v;
+        if (v) vr.nz[r] = 1;                    // every writer stores the same value
+    }
+    __syncthreads();
+    if (nonzero && threadIdx.x < nr && vr.nz[threadIdx.x]) {
+        int* flag = nonzero + (row0 + threadIdx.x) / rows_per_item;
+        if (__atomic_load_n(flag, __ATOMIC_RELAXED) == 0) atomicOr(flag, 1);
+    }
+    for (int i = threadIdx.x; i < nr * Wout; i += THREADS) {
+        const int r = i / Wout, x = i - r * Wout;
+        const Taps t = taps_of(table, kmax, x, Win);
+        const uint8_t* in = smem + (size_t)r * pitch + t.lo;
         int acc = 1 << (PRECISION_BITS - 1);
         for (int k = 0; k < t.n; ++k) acc += (int)in[k] * t.c[k];
         dst[(row0 + r) * Wout + x] = (uint8_t)clip8(acc);
@@ -366,6 +505,56 @@ extern "C" int ppea_lanczos_h_u8(const void* const* srcs, int nsrc, long planes_
     if (blocks > 0x7fffffffL) return PPEA_ERR_UNSUPPORTED;
     lanczos_h<<<(unsigned)blocks, THREADS, (size_t)rpb * Win, st>>>(s, planes_per_src * H, taps, kmax, flip,
                                                                   planes_per_item * H, nonzero, dst, rows, Win, Wout, rpb);
+    return launch_status();
+}
+
+// The horizontal pass over views: image i of source k is C channels of [H][Win] pixels at
+// srcs[k] + i * item_stride + c * channel_stride + y * row_stride + x * pixel_stride (bytes; the window's x offset is
+// folded into srcs[k]).  The images of all sources are numbered through (flip / nonzero index); dst [images][C][H][Wout].
+extern "C" int ppea_lanczos_h_view_u8(const void* const* srcs, int nsrc, int items_per_src, int C, long pixel_stride,
+                                      long row_stride, long channel_stride, long item_stride, const int32_t* taps, int kmax,
+                                      const int32_t* flip, int32_t* nonzero, uint8_t* dst, int H, int Win, int Wout,
+                                      void* stream) {
+    if (!srcs || !taps || !dst) return PPEA_ERR_ARG;
+    if (nsrc <= 0 || items_per_src <= 0 || C <= 0 || kmax <= 0 || H <= 0 || Win <= 0 || Wout <= 0) return PPEA_ERR_ARG;
+    if (pixel_stride <= 0 || row_stride <= 0 || channel_stride <= 0 || item_stride <= 0) return PPEA_ERR_ARG;
+    if (nsrc > MAX_SRCS) return PPEA_ERR_UNSUPPORTED;
+    const bool interleaved = channel_stride < pixel_stride;
+    if (interleaved && (long)C * channel_stride > pixel_stride) return PPEA_ERR_ARG;        // channels run into the next pixel
+    // bytes from a row's first to its last: the window must end before the next row begins
+    const long row_bytes = (long)(Win - 1) * pixel_stride + (interleaved ? (long)(C - 1) * channel_stride : 0) + 1;
+    if (row_bytes > row_stride) return PPEA_ERR_ARG;
+    const long images = (long)nsrc * items_per_src;
+    if (images > 0x7fffffffL / C || images * C > 0x7fffffffL / H) return PPEA_ERR_ARG;
+    Srcs s;
+    for (int i = 0; i < MAX_SRCS; ++i) {
+        s.p[i] = i < nsrc ? (const uint8_t*)srcs[i] : nullptr;
+        if (i < nsrc && !s.p[i]) return PPEA_ERR_ARG;
+    }
+    const bool rgb = C == 3 && pixel_stride == 3 && channel_stride == 1;
+    // a staged row: the window's bytes behind up to 15 bytes of misalignment, in whole chunks / Win bytes
+    const long pitch = rgb ? ((long)Win * 3 + 2 * (VIEW_CHUNK - 1)) / VIEW_CHUNK * VIEW_CHUNK
+                           : ((long)Win + VIEW_CHUNK - 1) / VIEW_CHUNK * VIEW_CHUNK;
+    if (pitch > LDS_LIMIT - VIEW_META) return PPEA_ERR_UNSUPPORTED;      // not even one row can be staged
+    hipStream_t st = (hipStream_t)stream;
+    if (nonzero) {
+        hipError_t e = hipMemsetAsync(nonzero, 0, (size_t)images * sizeof(int32_t), st);
+        if (e != hipSuccess) return (int)e;
+    }
+    const long rows = images * H * (rgb ? 1 : C);
+    int rpb = THREADS / Wout;
+    rpb = rpb < 1 ? 1 : (rpb > MAX_RPB ? MAX_RPB : rpb);
+    if (rpb > (LDS_LIMIT - VIEW_META) / pitch) rpb = (int)((LDS_LIMIT - VIEW_META) / pitch);
+    const long blocks = (rows + rpb - 1) / rpb;
+    if (blocks > 0x7fffffffL) return PPEA_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)rpb * pitch + VIEW_META;
+    if (rgb)
+        lanczos_h_view3<<<(unsigned)blocks, THREADS, lds, st>>>(s, items_per_src, row_stride, item_stride, taps, kmax, flip,
+                                                               nonzero, dst, rows, H, Win, Wout, rpb, (int)pitch);
+    else
+        lanczos_h_view<<<(unsigned)blocks, THREADS, lds, st>>>(s, items_per_src, C, pixel_stride, row_stride, channel_stride,
+                                                              item_stride, taps, kmax, flip, nonzero, dst, rows, H, Win,
+                                                              Wout, rpb, (int)pitch);
     return launch_status();
 }
 

@@ -16,6 +16,8 @@ draw per item shared by all its frames, `ToTensor`, and the per-scale intrinsics
 * On a GPU the pipeline runs in HIP kernels (csrc/input_pipeline.hip through ops.lanczos_resize_u8 / ops.color_jitter_u8):
   the same integer / IEEE arithmetic on uint8, every byte of output equal.  The torch formulation below stays as the CPU
   path, as `backend="torch"` on a GPU, and as the comparison target of tests/test_input_pipeline_gpu.py.
+* `DDADInputPipeline`, `CityscapesInputPipeline` and `CityscapesEvalPipeline` are the other loaders' image paths on the same
+  kernels; the Cityscapes ones read the decoder's HWC frames in place (ops.lanczos_resize_view_u8).
 """
 import math
 
@@ -126,6 +128,21 @@ class LanczosResize:
         if self.backend == "hip":
             from ppeadepth import ops
             return ops.lanczos_resize_u8(img_u8, self.out_hw, self.taps_h, self.taps_v, flip, nonzero)
+        return self._torch(img_u8)
+
+    def views(self, views, flip=None, nonzero=None):
+        """The same resize of uint8 [n,Hin,Win,C] HWC views (a list of them: as if concatenated) -> planar [N,C,Hout,Wout].
+        "hip": ops.lanczos_resize_view_u8 reads the views through their strides (`first` pipelines only: the horizontal pass
+        always runs); "torch": slice, permute, then the formulation above."""
+        if self.backend == "hip":
+            from ppeadepth import ops
+            return ops.lanczos_resize_view_u8(views, self.out_hw, self.taps_h, self.taps_v, flip, nonzero)
+        if flip is not None or nonzero is not None:
+            raise ValueError("backend 'torch' flips and marks blank frames in the pipeline")
+        views = list(views) if isinstance(views, (list, tuple)) else [views]
+        return self._torch(torch.cat([v.permute(0, 3, 1, 2) for v in views]))
+
+    def _torch(self, img_u8):
         x = img_u8.to(torch.float64)
         if self.in_hw[1] != self.out_hw[1]:
             x = self._clip8(x @ self.mh.t())                        # rows stay, columns resampled; 8-bit intermediate
@@ -271,6 +288,15 @@ def _jitter_of(jitter, f, s, B, generator):
     return jitter[(f, s)] if (f, s) in jitter else jitter
 
 
+def _backend_of(device, backend):
+    backend = backend or ("hip" if device.type == "cuda" else "torch")
+    if backend not in ("hip", "torch"):
+        raise ValueError(f"backend {backend!r}: expected 'hip' or 'torch'")
+    if backend == "hip" and device.type != "cuda":
+        raise ValueError("backend 'hip' needs a GPU device; the CPU path is backend 'torch'")
+    return backend
+
+
 class DeviceInputPipeline:
     """backend "hip" (the default on a GPU device; refused on the CPU) runs the whole call in HIP kernels, "torch" (the
     default on the CPU) in the torch formulation above; both return the same bytes.
@@ -283,11 +309,7 @@ class DeviceInputPipeline:
     def __init__(self, raw_hw, height, width, device, num_scales=4, frame_idxs=(0, -1, 1), K=KITTI_K, is_train=True,
                  backend=None):
         self.device = torch.device(device)
-        self.backend = backend or ("hip" if self.device.type == "cuda" else "torch")
-        if self.backend not in ("hip", "torch"):
-            raise ValueError(f"backend {backend!r}: expected 'hip' or 'torch'")
-        if self.backend == "hip" and self.device.type != "cuda":
-            raise ValueError("backend 'hip' needs a GPU device; the CPU path is backend 'torch'")
+        self.backend = _backend_of(self.device, backend)
         self.height, self.width, self.num_scales = height, width, num_scales
         self.frame_idxs, self.is_train = tuple(frame_idxs), is_train
         self.resize, prev = [], tuple(raw_hw)
@@ -295,6 +317,11 @@ class DeviceInputPipeline:
             hw = (height // 2 ** s, width // 2 ** s)
             self.resize.append(LanczosResize(prev, hw, self.device, self.backend, first=(s == 0)))
             prev = hw
+        # ToTensor's divisor as a tensor: a true division on every device (the GPU folds a Python scalar into a multiplication
+        # by its reciprocal, which is not the same fp32 value for 126 of the 256 levels)
+        self.unit = torch.full((), 255.0, device=self.device)
+        if K is None:                                      # a subclass with per-sample intrinsics
+            return
         self.K, self.inv_K = [], []
         for s in range(num_scales):                        # mono_dataset.py:173-182
             k = np.array(K, dtype=np.float32)
@@ -302,9 +329,6 @@ class DeviceInputPipeline:
             k[1, :] *= height // (2 ** s)
             self.K.append(torch.from_numpy(k).to(self.device))
             self.inv_K.append(torch.from_numpy(np.linalg.pinv(k)).to(self.device))
-        # ToTensor's divisor as a tensor: a true division on every device (the GPU folds a Python scalar into a multiplication
-        # by its reciprocal, which is not the same fp32 value for 126 of the 256 levels)
-        self.unit = torch.full((), 255.0, device=self.device)
         self.K_rows = torch.stack(self.K + self.inv_K)          # [2 * scales, 4, 4]: repeated over the batch in one launch
 
     @torch.no_grad()
@@ -314,12 +338,30 @@ class DeviceInputPipeline:
         backend "hip": these flags and the jitter parameters are host tensors (as draw_jitter_params returns them); they go
         to the device in one table, and a device tensor is refused rather than copied back."""
         B = raw[self.frame_idxs[0]].shape[0]
+        do_color_aug, do_flip = self._draw_flags(B, do_color_aug, do_flip, generator)
+        if self.backend == "hip":
+            inputs, _ = self._colors_hip(raw, B, do_color_aug, do_flip, jitter, generator)
+            from ppeadepth import ops
+            KK = ops.repeat_rows(self.K_rows, B)
+            for s in range(self.num_scales):
+                inputs[("K", s)] = KK[s]
+                inputs[("inv_K", s)] = KK[self.num_scales + s]
+            return inputs
+        inputs = self._colors_torch(raw, B, do_color_aug, do_flip, jitter, generator)
+        for s in range(self.num_scales):
+            inputs[("K", s)] = self.K[s][None].repeat(B, 1, 1)
+            inputs[("inv_K", s)] = self.inv_K[s][None].repeat(B, 1, 1)
+        return inputs
+
+    def _draw_flags(self, B, do_color_aug, do_flip, generator):
         if do_color_aug is None:
             do_color_aug = (torch.rand(B, generator=generator) > 0.5) if self.is_train else torch.zeros(B, dtype=torch.bool)
         if do_flip is None:
             do_flip = (torch.rand(B, generator=generator) > 0.5) if self.is_train else torch.zeros(B, dtype=torch.bool)
-        if self.backend == "hip":
-            return self._call_hip(raw, B, do_color_aug, do_flip, jitter, generator)
+        return do_color_aug, do_flip
+
+    def _colors_torch(self, raw, B, do_color_aug, do_flip, jitter, generator):
+        """("color" | "color_aug", f, s) of planar raw frames in the torch formulation."""
         flip = do_flip.to(self.device).reshape(-1, 1, 1, 1)
         inputs = {}
         for f in self.frame_idxs:
@@ -332,12 +374,12 @@ class DeviceInputPipeline:
                 aug = color_jitter(img, prm, do_color_aug.to(self.device) & ~blank)
                 inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
                 inputs[("color_aug", f, s)] = aug.to(torch.float32) / self.unit
-        for s in range(self.num_scales):
-            inputs[("K", s)] = self.K[s][None].repeat(B, 1, 1)
-            inputs[("inv_K", s)] = self.inv_K[s][None].repeat(B, 1, 1)
         return inputs
 
-    def _call_hip(self, raw, B, do_color_aug, do_flip, jitter, generator):
+    def _colors_hip(self, raw, B, do_color_aug, do_flip, jitter, generator, extra=None, level0=None):
+        """("color" | "color_aug", f, s) on the HIP kernels.  extra: host int32 words that ride on the call's one parameter
+        copy (returned as a device tensor); level0(flip, nonzero): the first level from another source than dense planar
+        `raw` frames."""
         from ppeadepth import ops
         F, S = len(self.frame_idxs), self.num_scales
         N = F * B                                                   # all frames stacked, frame-major: image n = fi * B + b
@@ -351,25 +393,25 @@ class DeviceInputPipeline:
             if t.device.type != "cpu":             # a device tensor would cost a device-to-host copy inside the call
                 raise ValueError("backend 'hip' takes do_color_aug, do_flip and the jitter parameters as host tensors")
         table = pack_jitter_params(by_scale, do_color_aug.repeat(S * F))                  # [S * N, 10]
-        host = torch.cat([do_flip.to(torch.int32).repeat(F), table.reshape(-1)])
+        host = torch.cat([do_flip.to(torch.int32).repeat(F), table.reshape(-1)] + ([] if extra is None else [extra]))
         dev = host.to(self.device)
-        flip, params = dev[:N], dev[N:].view(S, N, table.shape[1])
+        flip, params = dev[:N], dev[N:N + table.numel()].view(S, N, table.shape[1])
         nonzero = torch.empty(N, device=self.device, dtype=torch.int32)      # 0: a blank (missing) frame, never jittered
-        img = [raw[f].to(self.device).contiguous() for f in self.frame_idxs]
         levels = []
         for s in range(S):
-            img = self.resize[s](img, flip, nonzero) if s == 0 else self.resize[s](img)
+            if s > 0:
+                img = self.resize[s](img)
+            elif level0 is not None:
+                img = level0(flip, nonzero)
+            else:
+                img = self.resize[0]([raw[f].to(self.device).contiguous() for f in self.frame_idxs], flip, nonzero)
             levels.append(ops.color_jitter_u8(img, params[s], nonzero))
         inputs = {}
         for fi, f in enumerate(self.frame_idxs):
             for s, (color, aug) in enumerate(levels):
                 inputs[("color", f, s)] = color[fi * B:(fi + 1) * B]
                 inputs[("color_aug", f, s)] = aug[fi * B:(fi + 1) * B]
-        KK = ops.repeat_rows(self.K_rows, B)
-        for s in range(S):
-            inputs[("K", s)] = KK[s]
-            inputs[("inv_K", s)] = KK[S + s]
-        return inputs
+        return inputs, dev[N + table.numel():]
 
 
 DDAD_RAW_HW = (1216, 1936)                      # ddad_dataset.py:137-138
@@ -392,11 +434,7 @@ class DDADInputPipeline:
 
     def __init__(self, device, height=384, width=640, raw_hw=DDAD_RAW_HW, num_scales=4, frame_idxs=(0, -1), backend=None):
         self.device = torch.device(device)
-        self.backend = backend or ("hip" if self.device.type == "cuda" else "torch")
-        if self.backend not in ("hip", "torch"):
-            raise ValueError(f"backend {backend!r}: expected 'hip' or 'torch'")
-        if self.backend == "hip" and self.device.type != "cuda":
-            raise ValueError("backend 'hip' needs a GPU device; the CPU path is backend 'torch'")
+        self.backend = _backend_of(self.device, backend)
         self.height, self.width, self.raw_hw, self.num_scales = height, width, tuple(raw_hw), num_scales
         self.frame_idxs = tuple(frame_idxs)
         self.resize, prev = [], self.raw_hw
@@ -456,6 +494,156 @@ class DDADInputPipeline:
                     inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
                     inputs[("color_aug", f, s)] = inputs[("color", f, s)].clone()
             KK = kk[None].repeat(S, 1, 1, 1, 1)
+        for s in range(S):
+            inputs[("K", s)] = KK[s, 0]
+            inputs[("inv_K", s)] = KK[s, 1]
+        return inputs
+
+
+# ---- Cityscapes: the training triplets and the evaluation frames, read as views ---------------------------------------
+CITYSCAPES_TRIPLET_HW = (384, 1024)             # cityscapes_preprocessed_dataset.py:18-19, one frame of the wide image
+CITYSCAPES_RAW_HW = (1024, 2048)                # cityscapes_evaldataset.py:19-20
+
+
+def read_cityscapes_cam_txt(path):
+    """`<frame>_cam.txt` of the preprocessed triplets (cityscapes_preprocessed_dataset.py:40-45): nine comma-separated
+    values, fx = v[0], u0 = v[2], fy = v[4], v0 = v[5] -> float64 [3,3]."""
+    v = np.loadtxt(path, delimiter=",").reshape(-1)
+    return np.array([[v[0], 0, v[2]], [0, v[4], v[5]], [0, 0, 1]], dtype=np.float64)
+
+
+def read_cityscapes_camera_json(path):
+    """`<frame>_camera.json` of the raw dataset (cityscapes_evaldataset.py:45-50) -> float64 [3,3]."""
+    import json
+    with open(path, "r") as f:
+        c = json.load(f)["intrinsic"]
+    return np.array([[c["fx"], 0, c["u0"]], [0, c["fy"], c["v0"]], [0, 0, 1]], dtype=np.float64)
+
+
+def cityscapes_intrinsics(cameras, raw_width, raw_height, width, height, num_scales):
+    """[B,3,3] camera matrices -> float32 [scales,2,B,4,4]: ("K", s) and ("inv_K", s) of the two Cityscapes loaders, per
+    sample AND per level: the float32 4x4 of fx, fy, u0, v0 with row 0 / raw_width and row 1 / raw_height (`load_intrinsics`;
+    the evaluation loader passes the Python float 1024 * 0.75), then rows 0 and 1 times width // 2**s and height // 2**s
+    (mono_dataset.py:173-182), the inverse `np.linalg.pinv` of that float32 matrix.  In numpy on the host, in the loader's
+    operations and order, for the reason `DDADInputPipeline` gives."""
+    cam = cameras.cpu().numpy() if torch.is_tensor(cameras) else np.asarray(cameras)
+    if cam.ndim != 3 or cam.shape[1:] != (3, 3):
+        raise ValueError(f"cameras: [B,3,3] camera matrices, got {cam.shape}")
+    out = np.zeros((num_scales, 2, len(cam), 4, 4), np.float32)
+    for b, c in enumerate(cam):
+        for s in range(num_scales):
+            K = np.array([[c[0, 0], 0, c[0, 2], 0], [0, c[1, 1], c[1, 2], 0], [0, 0, 1, 0], [0, 0, 0, 1]]).astype(np.float32)
+            K[0, :] /= raw_width
+            K[1, :] /= raw_height
+            K[0, :] *= width // (2 ** s)
+            K[1, :] *= height // (2 ** s)
+            out[s, 0, b], out[s, 1, b] = K, np.linalg.pinv(K)
+    return out
+
+
+class CityscapesInputPipeline(DeviceInputPipeline):
+    """The preprocessed-Cityscapes loader (datasets/cityscapes_preprocessed_dataset.py through MonoDataset) for a whole
+    batch: one wide image per item that holds frames -1, 0, +1 side by side, uint8 [B, Hraw, 3 * Wraw, 3] as the JPEG
+    decoder returns it (HWC), and the item's camera -> the row-P dictionary.
+      * frame -1 is columns [0, w), frame 0 [w, 2w), frame +1 [2w, 3w) (:62-66); the flip mirrors each third on its own;
+      * pyramid, ColorJitter (same draw order), blank-frame rule and ToTensor are `DeviceInputPipeline`'s, by its code;
+      * ("K", s) / ("inv_K", s) are per sample and per level (`cityscapes_intrinsics`), uploaded with the call's one
+        parameter copy.
+    backend "hip": the first horizontal pass reads the three windows in place (ops.lanczos_resize_view_u8: no third is
+    sliced out, permuted or copied); 16 kernels, one memset and one host-to-device copy, whatever the batch size.
+    backend "torch": slices and permutes, then the torch formulation.  Both return the same bytes."""
+
+    def __init__(self, device, height=192, width=512, raw_hw=CITYSCAPES_TRIPLET_HW, num_scales=4, frame_idxs=(0, -1, 1),
+                 is_train=True, backend=None):
+        if any(f not in (-1, 0, 1) for f in frame_idxs):
+            raise ValueError(f"frame_idxs {tuple(frame_idxs)}: the wide image holds frames -1, 0 and 1")
+        super().__init__(raw_hw, height, width, device, num_scales, frame_idxs, K=None, is_train=is_train, backend=backend)
+        self.raw_hw = tuple(raw_hw)
+
+    @torch.no_grad()
+    def __call__(self, triplets, cameras, do_color_aug=None, do_flip=None, jitter=None, generator=None):
+        """triplets: uint8 [B, Hraw, 3 * Wraw, 3]; cameras: [B,3,3] (host tensor or array); the rest as the parent's."""
+        Hraw, Wraw = self.raw_hw
+        if triplets.dim() != 4 or tuple(triplets.shape[1:]) != (Hraw, 3 * Wraw, 3) or triplets.dtype != torch.uint8:
+            raise ValueError(f"expected uint8 [B, {Hraw}, {3 * Wraw}, 3] (three frames side by side, HWC), got "
+                             f"{triplets.dtype} {tuple(triplets.shape)}")
+        B, S = triplets.shape[0], self.num_scales
+        kk = cityscapes_intrinsics(cameras, Wraw, Hraw, self.width, self.height, S)
+        if kk.shape[2] != B:
+            raise ValueError(f"{kk.shape[2]} camera matrices for a batch of {B}")
+        do_color_aug, do_flip = self._draw_flags(B, do_color_aug, do_flip, generator)
+        triplets = triplets.to(self.device)
+        thirds = {f: triplets[:, :, (f + 1) * Wraw:(f + 2) * Wraw] for f in self.frame_idxs}
+        if self.backend == "hip":
+            inputs, kdev = self._colors_hip(
+                None, B, do_color_aug, do_flip, jitter, generator, extra=torch.from_numpy(kk).view(torch.int32).reshape(-1),
+                level0=lambda flip, nonzero: self.resize[0].views([thirds[f] for f in self.frame_idxs], flip, nonzero))
+            KK = kdev.view(torch.float32).view(S, 2, B, 4, 4)
+        else:
+            planar = {f: v.permute(0, 3, 1, 2) for f, v in thirds.items()}
+            inputs = self._colors_torch(planar, B, do_color_aug, do_flip, jitter, generator)
+            KK = torch.from_numpy(kk).to(self.device)
+        for s in range(S):
+            inputs[("K", s)] = KK[s, 0]
+            inputs[("inv_K", s)] = KK[s, 1]
+        return inputs
+
+
+class CityscapesEvalPipeline:
+    """The Cityscapes evaluation loader (datasets/cityscapes_evaldataset.py through MonoDataset) for a whole batch: the raw
+    frames 0 and -1, uint8 [B, Hraw, Wraw, 3] (HWC), and the item's camera -> the row-P dictionary.
+      * the frame is cropped to its top Hraw * 3 // 4 rows (:66-68) before the resize: in HWC a prefix of each image, so
+        nothing is copied;
+      * LANCZOS pyramid, level s from level s-1; no flip, no jitter: color_aug holds the bytes of color;
+      * K row 1 is divided by Hraw * 0.75, the Python float of :56, not by the integer crop height.
+    Backends as `CityscapesInputPipeline`; "hip" is the two resize passes and the two jitter launches per level, a fill
+    of the parameter table and one host-to-device copy (the intrinsics)."""
+
+    def __init__(self, device, height=192, width=512, raw_hw=CITYSCAPES_RAW_HW, num_scales=4, frame_idxs=(0, -1),
+                 backend=None):
+        self.device = torch.device(device)
+        self.backend = _backend_of(self.device, backend)
+        self.height, self.width, self.raw_hw, self.num_scales = height, width, tuple(raw_hw), num_scales
+        self.frame_idxs = tuple(frame_idxs)
+        self.crop_h = self.raw_hw[0] * 3 // 4
+        self.resize, prev = [], (self.crop_h, self.raw_hw[1])
+        for s in range(num_scales):
+            hw = (height // 2 ** s, width // 2 ** s)
+            self.resize.append(LanczosResize(prev, hw, self.device, self.backend, first=(s == 0)))
+            prev = hw
+        self.unit = torch.full((), 255.0, device=self.device)          # see DeviceInputPipeline
+
+    @torch.no_grad()
+    def __call__(self, raw, cameras):
+        """raw: {frame id: uint8 [B,Hraw,Wraw,3]}; cameras: [B,3,3] (host tensor or array)."""
+        B = raw[self.frame_idxs[0]].shape[0]
+        for f in self.frame_idxs:
+            if tuple(raw[f].shape) != (B,) + self.raw_hw + (3,) or raw[f].dtype != torch.uint8:
+                raise ValueError(f"frame {f}: expected uint8 {(B,) + self.raw_hw + (3,)}, got {raw[f].dtype} "
+                                 f"{tuple(raw[f].shape)}")
+        F, S = len(self.frame_idxs), self.num_scales
+        kk = cityscapes_intrinsics(cameras, self.raw_hw[1], self.raw_hw[0] * 0.75, self.width, self.height, S)
+        if kk.shape[2] != B:
+            raise ValueError(f"{kk.shape[2]} camera matrices for a batch of {B}")
+        KK = torch.from_numpy(kk).to(self.device)                      # the call's parameter copy
+        top = [raw[f].to(self.device)[:, :self.crop_h] for f in self.frame_idxs]
+        inputs = {}
+        if self.backend == "hip":
+            from ppeadepth import ops
+            params = torch.zeros(F * B, ops.JITTER_PARAM_WORDS, device=self.device, dtype=torch.int32)      # see DDADInputPipeline
+            for s in range(S):
+                img = self.resize[0].views(top) if s == 0 else self.resize[s](img)
+                color, aug = ops.color_jitter_u8(img, params)
+                for fi, f in enumerate(self.frame_idxs):
+                    inputs[("color", f, s)] = color[fi * B:(fi + 1) * B]
+                    inputs[("color_aug", f, s)] = aug[fi * B:(fi + 1) * B]
+        else:
+            for fi, f in enumerate(self.frame_idxs):
+                img = top[fi]
+                for s in range(S):
+                    img = self.resize[0].views(img) if s == 0 else self.resize[s](img)
+                    inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
+                    inputs[("color_aug", f, s)] = inputs[("color", f, s)].clone()
         for s in range(S):
             inputs[("K", s)] = KK[s, 0]
             inputs[("inv_K", s)] = KK[s, 1]

@@ -894,6 +894,45 @@ def lanczos_resize_u8(src, out_hw, taps_h=None, taps_v=None, flip=None, nonzero=
 
 
 @torch.no_grad()
+def lanczos_resize_view_u8(src, out_hw, taps_h, taps_v=None, flip=None, nonzero=None):
+    """`lanczos_resize_u8` over VIEWS: src is a uint8 [n,Hin,Win,C] tensor as a decoder returns it (HWC), or any view of
+    that shape (a window of a wider image, the top rows of a taller one, `planar.permute(0, 2, 3, 1)`), or a list of such
+    views of one shape and one set of strides (read as if concatenated along n) -> uint8 [N,C,Hout,Wout], planar.  Nothing
+    is copied: the horizontal pass reads the views through their strides, so taps_h is always given
+    (input_pipeline.identity_taps when the width stays).  taps_v / flip / nonzero as in `lanczos_resize_u8`."""
+    srcs = list(src) if isinstance(src, (list, tuple)) else [src]
+    if not srcs or any(s.dim() != 4 or s.shape != srcs[0].shape or s.stride() != srcs[0].stride() for s in srcs):
+        raise _abi.PpeaKernelError("expected uint8 [n,H,W,C] views of one shape and one set of strides")
+    for s in srcs:
+        if not s.is_cuda:
+            raise _abi.PpeaKernelError("PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback); got a CPU tensor")
+        if s.dtype != torch.uint8:
+            raise _abi.PpeaKernelError(f"expected torch.uint8, got {s.dtype}")
+    n, Hin, Win, C = srcs[0].shape
+    N, (Hout, Wout) = n * len(srcs), out_hw
+    dev = srcs[0].device
+    if taps_h is None:
+        raise _abi.PpeaKernelError("a view is read by the horizontal pass: give its tap table")
+    if taps_v is None and Hin != Hout:
+        raise _abi.PpeaKernelError("a change of height needs the vertical pass")
+    for t in (flip, nonzero):
+        if t is not None and tuple(t.shape) != (N,):
+            raise _abi.PpeaKernelError(f"expected one flag per image ({N}), got {tuple(t.shape)}")
+    item, row, pixel, channel = srcs[0].stride()              # uint8: elements are bytes
+    tp, kmax = _taps(taps_h, Wout, "horizontal")
+    ptrs = (_ct.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+    cur = torch.empty(N, C, Hin, Wout, device=dev, dtype=torch.uint8)
+    call("ppea_lanczos_h_view_u8", ptrs, len(srcs), n, C, pixel, row, channel, item, tp, kmax,
+         ptr(flip, torch.int32), ptr(nonzero, torch.int32), ptr(cur), Hin, Win, Wout, stream_ptr())
+    if taps_v is not None:
+        tp, kmax = _taps(taps_v, Hout, "vertical")
+        out = torch.empty(N, C, Hout, Wout, device=dev, dtype=torch.uint8)
+        call("ppea_lanczos_v_u8", ptr(cur, torch.uint8), tp, kmax, ptr(out), N * C, Hin, Hout, Wout, stream_ptr())
+        cur = out
+    return cur
+
+
+@torch.no_grad()
 def color_jitter_u8(img, params, nonzero=None):
     """img uint8 [N,3,H,W]; params int32 [N,10] (input_pipeline.pack_jitter_params); nonzero [N] int32 or None (0 = the
     image is blank and is never jittered) -> (color, color_aug) fp32 [N,3,H,W] = img / 255, jitter(img) / 255."""

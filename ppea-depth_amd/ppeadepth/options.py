@@ -58,6 +58,21 @@ class MonodepthOptions:
         return self.options
 
 
+def apply_train_cs(opt):
+    """What `--train_cs` means (reference trainer.py:90-96): dataset and split "cityscapes_preprocessed", eval_split
+    "cityscapes", at 192x512.  The reference builds its model inside the trainer, after this rewrite; here the caller builds
+    the model, so a caller that sizes anything from `opt.height` / `opt.width` applies this to the parsed options BEFORE
+    building the model.  `Trainer.__init__` applies it too (before `apply_ddad`, the reference's order: with both flags DDAD
+    wins); applying it twice changes nothing, and without `--train_cs` it changes nothing."""
+    if getattr(opt, "train_cs", False):
+        opt.dataset = "cityscapes_preprocessed"
+        opt.height = 192
+        opt.width = 512
+        opt.split = "cityscapes_preprocessed"
+        opt.eval_split = "cityscapes"
+    return opt
+
+
 def apply_ddad(opt):
     """What `--ddad` means (reference trainer.py:98-103): dataset, split and eval_split "ddad" at 384x640.  The reference
     builds its model inside the trainer, after this rewrite; here the caller builds the model, so a caller that sizes anything

@@ -92,9 +92,11 @@ class _NullAccelerator:
 class Trainer:
     def __init__(self, options, model, device, acc=None, amp_dtype=None):
         self.opt = options
-        # trainer.py:98-103, before anything is sized from them; validation is then `val_ddad` (trainer.py:372-394).  The
-        # model was built by the caller: under `--ddad` from options that `options.apply_ddad` had already rewritten.
-        from .options import apply_ddad
+        # trainer.py:90-103, before anything is sized from them and in that order (`--train_cs`, then `--ddad`, which wins);
+        # under `--ddad` validation is then `val_ddad` (trainer.py:372-394).  The model was built by the caller: from options
+        # that `options.apply_train_cs` / `options.apply_ddad` had already rewritten.
+        from .options import apply_ddad, apply_train_cs
+        apply_train_cs(self.opt)
         apply_ddad(self.opt)
         assert self.opt.height % 32 == 0 and self.opt.width % 32 == 0
         assert self.opt.frame_ids[0] == 0 and len(self.opt.frame_ids) > 1
