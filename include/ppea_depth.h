@@ -722,6 +722,30 @@ int ppea_depth_errors_f32(const float* pred_disp, const float* gt, long gt_len, 
 int ppea_depth_errors_mean_f64(const double* errors, double* mean, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * KITTI ground truth from raw LiDAR (kitti_utils.py:50-102 generate_depth_map, export_gt_depth.py), ABI 25: B velodyne scans
+ * projected into B sparse depth maps, written into the flat layout ppea_depth_errors_f32 reads.  csrc/kitti_gt.hip.
+ *   points [sum N][4] fp32 (device): the scans one after another, x forward; column 3 is ignored (the reference sets it to 1);
+ *   point_offsets [B+1] int64, HOST: scan b is points[point_offsets[b] .. point_offsets[b+1]); ascending, an empty scan is fine;
+ *   P [B][3][4] fp64 (device): P_rect @ R_cam2rect @ velo2cam of each scan's drive;
+ *   table [B][3] int64, HOST: (offset, H, W) of each map in out_flat -- the values of DeviceGroundTruth's table.  The launcher
+ *   reads both host arrays to refuse bad arguments and to size its grids without a device round trip; the scans' descriptors
+ *   travel to the kernels as launch arguments;
+ *   vel_depth != 0: the depth is the point's own fp32 x (export_gt_depth.py), else q2 = (P p)[2] rounded to fp32;
+ *   out_flat (device): fp32, every pixel of every map is written (0 = no return); it must hold max(offset + H * W) values;
+ *   workspace: ppea_velodyne_depth_workspace_bytes(sum H * W) bytes, cleared by the call itself on `stream`.
+ * Per scan: points with x < 0 are dropped; u = rint(q0 / q2) - 1, v = rint(q1 / q2) - 1 in fp64; valid when 0 <= u < W and
+ * 0 <= v < H (a NaN fails; q2 < 0 is not filtered); the last valid point in scan order on a pixel sets it; for every sub2ind
+ * key v * (W - 1) + u - 1 held by more than one valid point, the pixel of the key's first point is set to the minimum depth of
+ * the key's points (the key is shared by (v, W-1) and (v+1, 0): the reference's behaviour, kept); negative depths become 0.
+ * One memset + 2 launches per 32 scans; integer atomics on ordered words only: bitwise reproducible.  No host synchronisation.
+ * PPEA_ERR_ARG: B <= 0, a NULL array, offsets that do not ascend, a negative offset / H / W; PPEA_ERR_UNSUPPORTED: a scan of
+ * more than 2^31 - 2 points or a map of more than 2^31 - 1 pixels.
+ * ---------------------------------------------------------------------------------------- */
+long ppea_velodyne_depth_workspace_bytes(long total_pixels);
+int ppea_velodyne_depth_f32(const float* points, const int64_t* point_offsets, int B, const double* P, const int64_t* table,
+                            int vel_depth, float* out_flat, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Input pipeline on uint8 frames (datasets/mono_dataset.py:89-112, 143-190 through PIL / torchvision), bit for bit:
  * Pillow's LANCZOS resize of 8-bit images (Resample.c) and torchvision's PIL-path ColorJitter (ImageEnhance blends,
  * Convert.c RGB <-> HSV).  ppeadepth/input_pipeline.py holds the readable restatement and builds the tables.

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 24
+ABI_VERSION = 25
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -201,6 +201,8 @@ SIGNATURES = {
     "ppea_depth_errors_workspace_bytes": [_i, _l],
     "ppea_depth_errors_f32": [_vp, _vp, _l, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _l, _i, _i, _f, _vp],
     "ppea_depth_errors_mean_f64": [_vp, _vp, _i, _vp],
+    "ppea_velodyne_depth_workspace_bytes": [_l],
+    "ppea_velodyne_depth_f32": [_vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "ppea_lanczos_h_u8": [_vp, _i, _l, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
     "ppea_lanczos_h_view_u8": [_vp, _i, _i, _i, _l, _l, _l, _l, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
     "ppea_lanczos_v_u8": [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp],

@@ -143,7 +143,7 @@ class DeviceGroundTruth:
                   shapes, device)
 
     def _set(self, flat, table, shapes, device):
-        """Everything an instance holds, for both constructors."""
+        """Everything an instance holds, for every constructor."""
         self.flat, self.table, self.shapes, self.device = flat, table, list(shapes), device
 
     @classmethod
@@ -161,6 +161,18 @@ class DeviceGroundTruth:
                              torch.full((B,), H, device=device, dtype=torch.int64),
                              torch.full((B,), W, device=device, dtype=torch.int64)], 1)
         self._set(depth.to(device, torch.float32).contiguous().reshape(-1), table, [(H, W)] * B, device)
+        return self
+
+    @classmethod
+    def from_velodyne(cls, clouds, matrices, shapes, device, vel_depth=True):
+        """The ground truth projected from raw LiDAR where it will be scored (export_gt_depth.py without the file): B velodyne
+        scans [N_i,4], their `kitti_utils.velo_to_image_matrix` matrices and (H, W) -> the maps of
+        `kitti_utils.generate_depth_map(..., vel_depth)`, written by `ops.velodyne_depth_maps` into this layout; they are never
+        on the host."""
+        from . import kitti_utils
+        self = cls.__new__(cls)
+        device = torch.device(device)
+        self._set(*kitti_utils.project_depth_maps(clouds, matrices, shapes, vel_depth, device), device)
         return self
 
     def __len__(self):

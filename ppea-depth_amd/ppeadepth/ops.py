@@ -843,6 +843,52 @@ def depth_errors_mean(errors):
 
 
 # ---------------------------------------------------------------------------------------------
+# KITTI ground truth from raw LiDAR: kitti_utils.generate_depth_map for a ragged batch of scans   (csrc/kitti_gt.hip)
+# ---------------------------------------------------------------------------------------------
+def _host_i64(t, what):
+    """Address of a host array the launcher reads itself (grid sizes, refusals): a contiguous int64 CPU tensor."""
+    if not torch.is_tensor(t) or t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous():
+        raise _abi.PpeaKernelError(f"{what}: a contiguous int64 tensor on the host")
+    return _ct.c_void_p(t.data_ptr())
+
+
+@torch.no_grad()
+def velodyne_depth_maps(points, point_offsets, P, table, vel_depth=True):
+    """points [sum N,4] fp32 (device): B velodyne scans one after another (column 3 is ignored); point_offsets [B+1] int64 on
+    the HOST; P [B,3,4] fp64 (device): each scan's velodyne -> image matrix; table [B,3] int64 on the HOST: (offset, H, W) of
+    each map in the result -- the values of `DeviceGroundTruth.table`.  vel_depth: the depth is the point's own x
+    (export_gt_depth.py), else the projected q2.
+    -> flat fp32 [max(offset + H * W)] on the device: the sparse depth maps of kitti_utils.generate_depth_map (last point per
+    pixel, minimum per duplicated sub2ind key at its first point's pixel, negatives to 0), every pixel written."""
+    if points.dim() != 2 or points.shape[1] != 4:
+        raise _abi.PpeaKernelError(f"expected [N,4] velodyne points, got {tuple(points.shape)}")
+    if P.dim() != 3 or tuple(P.shape[1:]) != (3, 4):
+        raise _abi.PpeaKernelError(f"expected [B,3,4] projection matrices, got {tuple(P.shape)}")
+    B = P.shape[0]
+    if tuple(table.shape) != (B, 3) or tuple(point_offsets.shape) != (B + 1,):
+        raise _abi.PpeaKernelError(f"table {tuple(table.shape)} / point offsets {tuple(point_offsets.shape)} do not describe "
+                                   f"{B} scans")
+    po, tb = _host_i64(point_offsets, "point_offsets"), _host_i64(table, "table")
+    if P.device != points.device:
+        raise _abi.PpeaKernelError("points and P live on different devices")
+    pp, pm = ptr(points, _F32), ptr(P, torch.float64)
+    # what the launcher cannot see: the buffers' lengths.  (Its own refusals -- B <= 0, descending offsets, negative sizes --
+    # come back as PPEA_ERR_ARG before anything is launched.)
+    if B and int(point_offsets.max()) > points.shape[0]:
+        raise _abi.PpeaKernelError(f"point offsets reach {int(point_offsets.max())}, the buffer holds {points.shape[0]} points")
+    sizes = table[:, 1] * table[:, 2]
+    pixels = int(sizes.clamp(min=0).sum()) if B else 0
+    length = int((table[:, 0] + sizes).max()) if B else 0
+    nbytes = _abi.lib.ppea_velodyne_depth_workspace_bytes(pixels)
+    if nbytes < 0:
+        _abi.check(int(nbytes), "ppea_velodyne_depth_workspace_bytes")
+    out = torch.empty(max(length, 0), device=points.device, dtype=_F32)
+    ws = torch.empty(nbytes, device=points.device, dtype=torch.uint8)
+    call("ppea_velodyne_depth_f32", pp, po, B, pm, tb, int(bool(vel_depth)), ptr(out), ptr(ws), stream_ptr())
+    return out
+
+
+# ---------------------------------------------------------------------------------------------
 # Input pipeline on uint8 frames: Pillow's LANCZOS resize and the PIL-path ColorJitter   (csrc/input_pipeline.hip)
 # ---------------------------------------------------------------------------------------------
 JITTER_PARAM_WORDS = 10
