@@ -751,17 +751,23 @@ int ppea_velodyne_depth_f32(const float* points, const int64_t* point_offsets, i
  * Convert.c RGB <-> HSV).  ppeadepth/input_pipeline.py holds the readable restatement and builds the tables.
  *   taps [out][2 + kmax] int32: per output column / row (first input index, tap count n <= kmax, n 22-bit fixed-point
  *   coefficients).  Accumulator int32 from 1 << 21, >> 22 (arithmetic), clip to 0..255.
- * ppea_lanczos_h_u8: rows.  srcs = HOST array of nsrc <= 8 device pointers, each planes_per_src planes [H][Win]; the planes
- *   of all sources are numbered through and planes_per_item consecutive planes form an image.  flip [images] int32 or NULL:
- *   non-zero = the image is read mirrored (the flipped frame is never written); nonzero [images] int32 or NULL: set to
- *   whether the image holds a non-zero byte (one memset).  dst [planes][H][Wout].  One launch.
- * ppea_lanczos_h_view_u8 (ABI 24): the same pass over VIEWS.  srcs = HOST array of nsrc <= 8 device pointers; image i of
- *   source k is C channels of [H][Win] pixels, the byte of (c, y, x) at srcs[k] + i * item_stride + c * channel_stride +
- *   y * row_stride + x * pixel_stride (all strides > 0; the window's x offset is folded into srcs[k]; a row's first to last
- *   byte must fit row_stride).  The images of all sources are numbered through (flip / nonzero as above); dst
- *   [images][C][H][Wout], planar.  C = 3, pixel_stride = 3, channel_stride = 1 (a decoder's HWC): one workgroup stages a
- *   row's window once, in 16-byte loads wherever its address allows and byte by byte at the ends, and writes the three
- *   channel rows; a row that does not fit the LDS is PPEA_ERR_UNSUPPORTED.  No byte outside the windows is read.  One launch.
+ * ppea_lanczos_h_u8 / ppea_lanczos_h_view_u8: rows, through one launcher and one strided kernel; the two entry points
+ *   differ in how the sources are described.  Common: srcs = HOST array of nsrc <= 8 device pointers, the images of all
+ *   sources numbered through; flip [images] int32 or NULL: non-zero = the image is read mirrored (the flipped frame is never
+ *   written); nonzero [images] int32 or NULL: set to whether the image holds a non-zero byte (one memset); dst
+ *   [images][C][H][Wout], planar.  A workgroup stages whole rows in LDS, each padded to 16 bytes, with 512 bytes of per-row
+ *   bookkeeping behind them; a row that does not fit 60 KiB with it is PPEA_ERR_UNSUPPORTED.  One launch.
+ * ppea_lanczos_h_u8: dense planar sources, each planes_per_src planes [H][Win]; planes_per_item consecutive planes form an
+ *   image (C = planes_per_item): the views of pixel_stride 1, row_stride Win, channel_stride H * Win, item_stride
+ *   C * H * Win.  The widest row is 60 928 bytes (61 440 before the entry points shared a launcher).  Every source holds
+ *   whole images: planes_per_src that is no multiple of planes_per_item is PPEA_ERR_ARG (before, only the total of all
+ *   sources was checked).
+ * ppea_lanczos_h_view_u8 (ABI 24): VIEWS.  Image i of source k is C channels of [H][Win] pixels, the byte of (c, y, x) at
+ *   srcs[k] + i * item_stride + c * channel_stride + y * row_stride + x * pixel_stride (all strides > 0; the window's x
+ *   offset is folded into srcs[k]; a row's first to last byte must fit row_stride), items_per_src images per source.
+ *   C = 3, pixel_stride = 3, channel_stride = 1 (a decoder's HWC) has a kernel of its own: one workgroup stages a row's
+ *   window once, in 16-byte loads wherever its address allows and byte by byte at the ends, and writes the three channel
+ *   rows.  No byte outside the windows is read.
  * ppea_lanczos_v_u8: columns of src [planes][Hin][W] -> dst [planes][Hout][W], planes <= 65535.  One launch.
  * ppea_color_jitter_u8: img [N][3][H][W] uint8 -> color = img / 255 and color_aug = jitter(img) / 255, both [N][3][H][W]
  *   fp32 (one correctly rounded division, as ToTensor).  params [N][10] int32: the order of the four operations

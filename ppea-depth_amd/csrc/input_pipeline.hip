@@ -2,13 +2,14 @@
 // ColorJitter (ImageEnhance blends, Convert.c RGB <-> HSV), bit for bit (ppeadepth/input_pipeline.py is the readable
 // restatement; tests/test_input_pipeline_gpu.py compares every byte).
 //
-//   lanczos_h   one workgroup stages `rpb` whole input rows in LDS (mirrored when the item is flipped, so a flipped frame is
-//               never materialised), then one thread per output pixel: int32 accumulator from 1 << 21 over the row's
-//               (xmin, n, coeffs[n]) entry of the tap table, >> 22, clip.  Every input byte is read exactly once, so the
-//               same pass marks the images that hold a non-zero byte (a missing neighbour frame is all zeros).
-//   lanczos_h_view3 / lanczos_h_view   the same pass over a window of a larger image given by byte strides: interleaved
-//               RGB (a JPEG decoder's HWC) staged once per row in 16-byte chunks and written as three channel rows, any
-//               other layout byte by byte; the planar output of lanczos_h, so everything downstream is unchanged.
+//   lanczos_h_view   the horizontal pass; every source is a window of a larger image given by byte strides (dense planar
+//               frames are the strides pixel 1, row Win, channel H * Win, image C * H * Win).  One workgroup stages `rpb`
+//               whole input rows in LDS (mirrored when the item is flipped, so a flipped frame is never materialised),
+//               then one thread per output pixel: int32 accumulator from 1 << 21 over the row's (xmin, n, coeffs[n])
+//               entry of the tap table, >> 22, clip.  Every input byte is read exactly once, so the same pass marks the
+//               images that hold a non-zero byte (a missing neighbour frame is all zeros).  Planar output.
+//   lanczos_h_view3   its specialisation for interleaved RGB (a JPEG decoder's HWC): a row's window staged once in 16-byte
+//               chunks and written as three channel rows.  One host function launches either for both entry points.
 //   lanczos_v   the same arithmetic down the columns of the 8-bit intermediate, 4 columns per thread through 32-bit words
 //               when the row length allows.
 //   jitter_sum  the item's pointwise operations that precede contrast, then Pillow's RGB -> L; an exact integer sum per
@@ -54,48 +55,7 @@ __device__ __forceinline__ Taps taps_of(const int* __restrict__ table, int kmax,
     return r;
 }
 
-__global__ __launch_bounds__(THREADS) void lanczos_h(Srcs srcs, long rows_per_src, const int* __restrict__ table, int kmax,
-                                                     const int* __restrict__ flip, int rows_per_item,
-                                                     int* __restrict__ nonzero, uint8_t* __restrict__ dst, long rows,
-                                                     int Win, int Wout, int rpb) {
-    extern __shared__ uint8_t line[];           // [rpb][Win]
-    __shared__ const uint8_t* row_src[MAX_RPB];
-    __shared__ int row_flip[MAX_RPB], row_nz[MAX_RPB];
-    const long row0 = (long)blockIdx.x * rpb;
-    const int nr = (int)min((long)rpb, rows - row0);
-    if (threadIdx.x < nr) {
-        const long g = row0 + threadIdx.x;
-        const int s = (int)(g / rows_per_src);
-        const uint8_t* base = nullptr;
-#pragma unroll
-        for (int k = 0; k < MAX_SRCS; ++k) base = k == s ? srcs.p[k] : base;
-        row_src[threadIdx.x] = base + (g - s * rows_per_src) * Win;
-        row_flip[threadIdx.x] = flip && flip[g / rows_per_item] != 0;
-        row_nz[threadIdx.x] = 0;
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nr * Win; i += THREADS) {
-        const int r = i / Win, x = i - r * Win;
-        const uint8_t v = row_src[r][x];
-        line[r * Win + (row_flip[r] ? Win - 1 - x : x)] = v;
-        if (v) row_nz[r] = 1;                   // every writer stores the same value
-    }
-    __syncthreads();
-    if (nonzero && threadIdx.x < nr && row_nz[threadIdx.x]) {
-        int* flag = nonzero + (row0 + threadIdx.x) / rows_per_item;
-        if (__atomic_load_n(flag, __ATOMIC_RELAXED) == 0) atomicOr(flag, 1);
-    }
-    for (int i = threadIdx.x; i < nr * Wout; i += THREADS) {
-        const int r = i / Wout, x = i - r * Wout;
-        const Taps t = taps_of(table, kmax, x, Win);
-        const uint8_t* in = line + r * Win + t.lo;
-        int acc = 1 << (PRECISION_BITS - 1);
-        for (int k = 0; k < t.n; ++k) acc += (int)in[k] * t.c[k];
-        dst[(row0 + r) * Wout + x] = (uint8_t)clip8(acc);
-    }
-}
-
-// ---- horizontal pass over a VIEW: a window of a larger image, described by strides ---------------------------------
+// ---- horizontal pass: every source is a window of a larger image, described by byte strides ------------------------
 // Rows of all images are numbered through; a workgroup's per-row bookkeeping lies behind the staged rows in the dynamic
 // LDS region (no static LDS: the region's base stays 16-byte aligned for the 128-bit writes).
 constexpr int VIEW_CHUNK = 16;                  // bytes per wide load
@@ -187,8 +147,9 @@ __global__ __launch_bounds__(THREADS) void lanczos_h_view3(Srcs srcs, int items_
     }
 }
 
-// Any other strides: rows g = (image * C + c) * H + y, as the planar output numbers them; `lanczos_h` with the row's
-// bytes fetched one by one through the pixel stride.
+// Any other strides, dense planar frames among them (pixel stride 1, row stride Win, channel stride H * Win): rows
+// g = (image * C + c) * H + y, as the planar output numbers them.  One workgroup stages `rpb` whole rows, fetched byte by
+// byte through the pixel stride and written mirrored when the image is flipped, then one thread per output pixel.
 __global__ __launch_bounds__(THREADS) void lanczos_h_view(Srcs srcs, int items_per_src, int C, long pixel_stride,
                                                           long row_stride, long channel_stride, long item_stride,
                                                           const int* __restrict__ table, int kmax,
@@ -474,56 +435,12 @@ inline long jitter_chunks(long HW, int vec) {
 }
 inline int jitter_vec(long HW) { return HW % 4 == 0 ? 4 : 1; }
 
-}  // namespace
-
-// srcs: HOST array of nsrc device pointers, each `planes_per_src` planes of [H][Win]; the planes of all sources are
-// numbered through, `planes_per_item` consecutive planes form an image (flip / nonzero index).
-extern "C" int ppea_lanczos_h_u8(const void* const* srcs, int nsrc, long planes_per_src, const int32_t* taps, int kmax,
-                                 const int32_t* flip, int planes_per_item, int32_t* nonzero, uint8_t* dst, int H, int Win,
-                                 int Wout, void* stream) {
-    if (!srcs || !taps || !dst) return PPEA_ERR_ARG;
-    if (nsrc <= 0 || planes_per_src <= 0 || planes_per_item <= 0 || kmax <= 0 || H <= 0 || Win <= 0 || Wout <= 0)
-        return PPEA_ERR_ARG;
-    if (nsrc > MAX_SRCS || Win > LDS_LIMIT) return PPEA_ERR_UNSUPPORTED;
-    const long planes = planes_per_src * nsrc;
-    if (planes % planes_per_item != 0 || planes > 0x7fffffffL / H) return PPEA_ERR_ARG;
-    Srcs s;
-    for (int i = 0; i < MAX_SRCS; ++i) {
-        s.p[i] = i < nsrc ? (const uint8_t*)srcs[i] : nullptr;
-        if (i < nsrc && !s.p[i]) return PPEA_ERR_ARG;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    if (nonzero) {
-        hipError_t e = hipMemsetAsync(nonzero, 0, (size_t)(planes / planes_per_item) * sizeof(int32_t), st);
-        if (e != hipSuccess) return (int)e;
-    }
-    const long rows = planes * H;
-    int rpb = THREADS / Wout;
-    rpb = rpb < 1 ? 1 : (rpb > MAX_RPB ? MAX_RPB : rpb);
-    if (rpb > LDS_LIMIT / Win) rpb = LDS_LIMIT / Win;
-    const long blocks = (rows + rpb - 1) / rpb;
-    if (blocks > 0x7fffffffL) return PPEA_ERR_UNSUPPORTED;
-    lanczos_h<<<(unsigned)blocks, THREADS, (size_t)rpb * Win, st>>>(s, planes_per_src * H, taps, kmax, flip,
-                                                                  planes_per_item * H, nonzero, dst, rows, Win, Wout, rpb);
-    return launch_status();
-}
-
-// The horizontal pass over views: image i of source k is C channels of [H][Win] pixels at
-// srcs[k] + i * item_stride + c * channel_stride + y * row_stride + x * pixel_stride (bytes; the window's x offset is
-// folded into srcs[k]).  The images of all sources are numbered through (flip / nonzero index); dst [images][C][H][Wout].
-extern "C" int ppea_lanczos_h_view_u8(const void* const* srcs, int nsrc, int items_per_src, int C, long pixel_stride,
-                                      long row_stride, long channel_stride, long item_stride, const int32_t* taps, int kmax,
-                                      const int32_t* flip, int32_t* nonzero, uint8_t* dst, int H, int Win, int Wout,
-                                      void* stream) {
-    if (!srcs || !taps || !dst) return PPEA_ERR_ARG;
-    if (nsrc <= 0 || items_per_src <= 0 || C <= 0 || kmax <= 0 || H <= 0 || Win <= 0 || Wout <= 0) return PPEA_ERR_ARG;
-    if (pixel_stride <= 0 || row_stride <= 0 || channel_stride <= 0 || item_stride <= 0) return PPEA_ERR_ARG;
+// The horizontal pass of both entry points, their arguments checked: the pointer table, the memset of the marks, the
+// staged row's pitch, the rows a workgroup takes, and the launch.
+int launch_lanczos_h(const void* const* srcs, int nsrc, int items_per_src, int C, long pixel_stride, long row_stride,
+                     long channel_stride, long item_stride, const int32_t* taps, int kmax, const int32_t* flip,
+                     int32_t* nonzero, uint8_t* dst, int H, int Win, int Wout, void* stream) {
     if (nsrc > MAX_SRCS) return PPEA_ERR_UNSUPPORTED;
-    const bool interleaved = channel_stride < pixel_stride;
-    if (interleaved && (long)C * channel_stride > pixel_stride) return PPEA_ERR_ARG;        // channels run into the next pixel
-    // bytes from a row's first to its last: the window must end before the next row begins
-    const long row_bytes = (long)(Win - 1) * pixel_stride + (interleaved ? (long)(C - 1) * channel_stride : 0) + 1;
-    if (row_bytes > row_stride) return PPEA_ERR_ARG;
     const long images = (long)nsrc * items_per_src;
     if (images > 0x7fffffffL / C || images * C > 0x7fffffffL / H) return PPEA_ERR_ARG;
     Srcs s;
@@ -556,6 +473,42 @@ extern "C" int ppea_lanczos_h_view_u8(const void* const* srcs, int nsrc, int ite
                                                               item_stride, taps, kmax, flip, nonzero, dst, rows, H, Win,
                                                               Wout, rpb, (int)pitch);
     return launch_status();
+}
+
+}  // namespace
+
+// srcs: HOST array of nsrc device pointers, each `planes_per_src` planes of [H][Win]; the planes of all sources are
+// numbered through, `planes_per_item` consecutive planes form an image (flip / nonzero index) and every source holds
+// whole images: the views of pixel stride 1, row stride Win, channel stride H * Win.
+extern "C" int ppea_lanczos_h_u8(const void* const* srcs, int nsrc, long planes_per_src, const int32_t* taps, int kmax,
+                                 const int32_t* flip, int planes_per_item, int32_t* nonzero, uint8_t* dst, int H, int Win,
+                                 int Wout, void* stream) {
+    if (!srcs || !taps || !dst) return PPEA_ERR_ARG;
+    if (nsrc <= 0 || planes_per_src <= 0 || planes_per_item <= 0 || kmax <= 0 || H <= 0 || Win <= 0 || Wout <= 0)
+        return PPEA_ERR_ARG;
+    if (planes_per_src % planes_per_item != 0 || planes_per_src > 0x7fffffffL) return PPEA_ERR_ARG;
+    const long plane = (long)H * Win;
+    return launch_lanczos_h(srcs, nsrc, (int)(planes_per_src / planes_per_item), planes_per_item, 1, Win, plane,
+                            planes_per_item * plane, taps, kmax, flip, nonzero, dst, H, Win, Wout, stream);
+}
+
+// The horizontal pass over views: image i of source k is C channels of [H][Win] pixels at
+// srcs[k] + i * item_stride + c * channel_stride + y * row_stride + x * pixel_stride (bytes; the window's x offset is
+// folded into srcs[k]).  The images of all sources are numbered through (flip / nonzero index); dst [images][C][H][Wout].
+extern "C" int ppea_lanczos_h_view_u8(const void* const* srcs, int nsrc, int items_per_src, int C, long pixel_stride,
+                                      long row_stride, long channel_stride, long item_stride, const int32_t* taps, int kmax,
+                                      const int32_t* flip, int32_t* nonzero, uint8_t* dst, int H, int Win, int Wout,
+                                      void* stream) {
+    if (!srcs || !taps || !dst) return PPEA_ERR_ARG;
+    if (nsrc <= 0 || items_per_src <= 0 || C <= 0 || kmax <= 0 || H <= 0 || Win <= 0 || Wout <= 0) return PPEA_ERR_ARG;
+    if (pixel_stride <= 0 || row_stride <= 0 || channel_stride <= 0 || item_stride <= 0) return PPEA_ERR_ARG;
+    const bool interleaved = channel_stride < pixel_stride;
+    if (interleaved && (long)C * channel_stride > pixel_stride) return PPEA_ERR_ARG;        // channels run into the next pixel
+    // bytes from a row's first to its last: the window must end before the next row begins
+    const long row_bytes = (long)(Win - 1) * pixel_stride + (interleaved ? (long)(C - 1) * channel_stride : 0) + 1;
+    if (row_bytes > row_stride) return PPEA_ERR_ARG;
+    return launch_lanczos_h(srcs, nsrc, items_per_src, C, pixel_stride, row_stride, channel_stride, item_stride, taps, kmax,
+                            flip, nonzero, dst, H, Win, Wout, stream);
 }
 
 extern "C" int ppea_lanczos_v_u8(const uint8_t* src, const int32_t* taps, int kmax, uint8_t* dst, long planes, int Hin,

@@ -16,8 +16,10 @@ draw per item shared by all its frames, `ToTensor`, and the per-scale intrinsics
 * On a GPU the pipeline runs in HIP kernels (csrc/input_pipeline.hip through ops.lanczos_resize_u8 / ops.color_jitter_u8):
   the same integer / IEEE arithmetic on uint8, every byte of output equal.  The torch formulation below stays as the CPU
   path, as `backend="torch"` on a GPU, and as the comparison target of tests/test_input_pipeline_gpu.py.
-* `DDADInputPipeline`, `CityscapesInputPipeline` and `CityscapesEvalPipeline` are the other loaders' image paths on the same
-  kernels; the Cityscapes ones read the decoder's HWC frames in place (ops.lanczos_resize_view_u8).
+* `_PyramidPipeline` is the one core of the four pipelines: the pyramid, the backend choice and, per backend, the way from
+  the level-0 sources of every frame to the colour entries, with or without augmentation.  `DeviceInputPipeline` (KITTI),
+  `DDADInputPipeline`, `CityscapesInputPipeline` and `CityscapesEvalPipeline` supply their level-0 sources, whether they
+  augment and their intrinsics; the Cityscapes ones read the decoder's HWC frames in place (ops.lanczos_resize_view_u8).
 """
 import math
 
@@ -297,31 +299,146 @@ def _backend_of(device, backend):
     return backend
 
 
-class DeviceInputPipeline:
-    """backend "hip" (the default on a GPU device; refused on the CPU) runs the whole call in HIP kernels, "torch" (the
-    default on the CPU) in the torch formulation above; both return the same bytes.
+def _k4_and_pinv(k3, scale_rows):
+    """3x3 camera matrix -> (K, inv_K): the float32 4x4 with rows 0 and 1 scaled in place by `scale_rows(row0, row1)`, and
+    `np.linalg.pinv` of that float32 matrix, in numpy on the host as the loaders do (a float32 SVD is not reproducible bit
+    for bit in a kernel)."""
+    K = np.zeros((4, 4), np.float32)
+    K[:3, :3] = k3
+    K[3][3] = 1
+    scale_rows(K[0, :], K[1, :])
+    return K, np.linalg.pinv(K)
 
-    A "hip" call launches, whatever the batch size: per pyramid level the horizontal and the vertical resize pass and the
-    two ColorJitter launches, all frames stacked (4 kernels per level, 16 for the 4 levels), plus one launch that
-    repeats K / inv_K over the batch: 17 kernels, one memset (the blank-frame marks) and one host-to-device copy (flip flags
-    and the jitter parameters of every frame and scale in one table).  Nothing is copied back to the host."""
 
-    def __init__(self, raw_hw, height, width, device, num_scales=4, frame_idxs=(0, -1, 1), K=KITTI_K, is_train=True,
-                 backend=None):
+def _camera_matrices(cameras, what):
+    cam = cameras.cpu().numpy() if torch.is_tensor(cameras) else np.asarray(cameras)
+    if cam.ndim != 3 or cam.shape[1:] != (3, 3):
+        raise ValueError(f"{what}: [B,3,3] camera matrices, got {cam.shape}")
+    return cam
+
+
+def _put_intrinsics(inputs, KK):
+    """[S,2,B,4,4] -> the ("K", s) and ("inv_K", s) entries."""
+    for s in range(KK.shape[0]):
+        inputs[("K", s)] = KK[s, 0]
+        inputs[("inv_K", s)] = KK[s, 1]
+    return inputs
+
+
+class _PyramidPipeline:
+    """What the four pipelines share: the pyramid of `LanczosResize` levels (level 0 from `src_hw` with `level0_filter`,
+    level s >= 1 LANCZOS from level s-1), ToTensor's divisor, the backend, and per backend one method from the level-0
+    sources of every frame to the ("color" | "color_aug", f, s) entries.  A subclass supplies its level-0 sources (dense
+    planar frames, or with `hwc` uint8 [B,H,W,3] views that are read in place), whether it augments, and its intrinsics.
+
+    A "hip" call launches, whatever the batch size: per level the horizontal and the vertical resize pass and the two
+    ColorJitter launches, all frames stacked frame-major (image n = fi * B + b): 4 kernels per level, 16 for the 4 levels;
+    one memset (the blank-frame marks) or, without augmentation, one fill (the all-zero parameter table); and ONE
+    host-to-device copy: flip flags, the jitter parameters of every frame and scale and the subclass's per-sample
+    intrinsics in one buffer.  Nothing is copied back to the host."""
+
+    def __init__(self, src_hw, height, width, device, num_scales, frame_idxs, backend, level0_filter="lanczos", hwc=False):
         self.device = torch.device(device)
         self.backend = _backend_of(self.device, backend)
-        self.height, self.width, self.num_scales = height, width, num_scales
-        self.frame_idxs, self.is_train = tuple(frame_idxs), is_train
-        self.resize, prev = [], tuple(raw_hw)
+        self.height, self.width, self.num_scales, self.frame_idxs, self.hwc = height, width, num_scales, tuple(frame_idxs), hwc
+        self.resize, prev = [], tuple(src_hw)
         for s in range(num_scales):
             hw = (height // 2 ** s, width // 2 ** s)
-            self.resize.append(LanczosResize(prev, hw, self.device, self.backend, first=(s == 0)))
+            self.resize.append(LanczosResize(prev, hw, self.device, self.backend, first=(s == 0),
+                                             filter=level0_filter if s == 0 else "lanczos"))
             prev = hw
         # ToTensor's divisor as a tensor: a true division on every device (the GPU folds a Python scalar into a multiplication
         # by its reciprocal, which is not the same fp32 value for 126 of the 256 levels)
         self.unit = torch.full((), 255.0, device=self.device)
-        if K is None:                                      # a subclass with per-sample intrinsics
-            return
+
+    def _draw_flags(self, B, do_color_aug, do_flip, generator):
+        if do_color_aug is None:
+            do_color_aug = (torch.rand(B, generator=generator) > 0.5) if self.is_train else torch.zeros(B, dtype=torch.bool)
+        if do_flip is None:
+            do_flip = (torch.rand(B, generator=generator) > 0.5) if self.is_train else torch.zeros(B, dtype=torch.bool)
+        return do_color_aug, do_flip
+
+    def _colors(self, level0, B, aug=None, kk=None):
+        """level0: the level-0 source of every frame, in the order of frame_idxs.  aug: None (nothing is flipped, jittered or
+        marked blank: color_aug holds the bytes of color) or (do_color_aug, do_flip, jitter, generator).  kk: host float32
+        array of intrinsics, or None.  -> (the colour entries, kk on the device)."""
+        return (self._colors_hip if self.backend == "hip" else self._colors_torch)(level0, B, aug, kk)
+
+    def _colors_torch(self, level0, B, aug, kk):
+        inputs = {}
+        for f, img in zip(self.frame_idxs, level0):
+            img = img.to(self.device)
+            img = img.permute(0, 3, 1, 2) if self.hwc else img
+            if aug is not None:
+                do_color_aug, do_flip, jitter, generator = aug
+                img = torch.where(do_flip.to(self.device).reshape(-1, 1, 1, 1), img.flip(-1), img)
+                blank = (img.reshape(B, -1).sum(1) == 0)
+            for s in range(self.num_scales):
+                img = self.resize[s](img)                               # uint8, chained from the previous scale
+                color = inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
+                if aug is None:
+                    inputs[("color_aug", f, s)] = color.clone()
+                    continue
+                prm = _jitter_of(jitter, f, s, B, generator)
+                jit = color_jitter(img, prm, do_color_aug.to(self.device) & ~blank)
+                inputs[("color_aug", f, s)] = jit.to(torch.float32) / self.unit
+        return inputs, None if kk is None else torch.from_numpy(kk).to(self.device)
+
+    def _colors_hip(self, level0, B, aug, kk):
+        from ppeadepth import ops
+        F, S = len(self.frame_idxs), self.num_scales
+        N = F * B                                                   # all frames stacked, frame-major: image n = fi * B + b
+        host, words = [], 0
+        if aug is not None:
+            do_color_aug, do_flip, jitter, generator = aug
+            # parameters in the torch path's order (frame outer, scale inner), then one table for the whole call
+            prms = [_jitter_of(jitter, f, s, B, generator) for f in self.frame_idxs for s in range(S)]
+            by_scale = [prms[fi * S + s] for s in range(S) for fi in range(F)]
+            for t in [do_color_aug, do_flip] + [v for p in prms for v in p.values()]:
+                if t.device.type != "cpu":             # a device tensor would cost a device-to-host copy inside the call
+                    raise ValueError("backend 'hip' takes do_color_aug, do_flip and the jitter parameters as host tensors")
+            table = pack_jitter_params(by_scale, do_color_aug.repeat(S * F))                  # [S * N, 10]
+            host, words = [do_flip.to(torch.int32).repeat(F), table.reshape(-1)], N + table.numel()
+        if kk is not None:
+            host.append(torch.from_numpy(kk).view(torch.int32).reshape(-1))
+        dev = torch.cat(host).to(self.device)                       # the call's one host-to-device copy
+        if aug is None:
+            # no jitter: an all-zero parameter table (apply = 0, written on the device) turns the ColorJitter launch into the
+            # uint8 -> fp32 conversion of both outputs
+            flip = nonzero = None
+            params = [torch.zeros(N, ops.JITTER_PARAM_WORDS, device=self.device, dtype=torch.int32)] * S
+        else:
+            flip, params = dev[:N], dev[N:words].view(S, N, -1)
+            nonzero = torch.empty(N, device=self.device, dtype=torch.int32)      # 0: a blank (missing) frame, never jittered
+        level0 = [v.to(self.device) for v in level0]
+        levels = []
+        for s in range(S):
+            if s > 0:
+                img = self.resize[s](img)
+            elif self.hwc:
+                img = self.resize[0].views(level0, flip, nonzero)
+            else:
+                img = self.resize[0]([v.contiguous() for v in level0], flip, nonzero)
+            levels.append(ops.color_jitter_u8(img, params[s], nonzero))
+        inputs = {}
+        for fi, f in enumerate(self.frame_idxs):                   # the torch arm's key order
+            for s, (color, jit) in enumerate(levels):
+                inputs[("color", f, s)] = color[fi * B:(fi + 1) * B]
+                inputs[("color_aug", f, s)] = jit[fi * B:(fi + 1) * B]
+        return inputs, None if kk is None else dev[words:].view(torch.float32).view(kk.shape)
+
+
+class DeviceInputPipeline(_PyramidPipeline):
+    """The KITTI loader's image path.  backend "hip" (the default on a GPU device; refused on the CPU) runs the whole call
+    in HIP kernels, "torch" (the default on the CPU) in the torch formulation above; both return the same bytes.
+
+    A "hip" call is the core's 16 kernels, memset and copy (flip flags and jitter parameters) plus one launch that repeats
+    K / inv_K over the batch: 17 kernels."""
+
+    def __init__(self, raw_hw, height, width, device, num_scales=4, frame_idxs=(0, -1, 1), K=KITTI_K, is_train=True,
+                 backend=None):
+        super().__init__(raw_hw, height, width, device, num_scales, frame_idxs, backend)
+        self.is_train = is_train
         self.K, self.inv_K = [], []
         for s in range(num_scales):                        # mono_dataset.py:173-182
             k = np.array(K, dtype=np.float32)
@@ -329,7 +446,7 @@ class DeviceInputPipeline:
             k[1, :] *= height // (2 ** s)
             self.K.append(torch.from_numpy(k).to(self.device))
             self.inv_K.append(torch.from_numpy(np.linalg.pinv(k)).to(self.device))
-        self.K_rows = torch.stack(self.K + self.inv_K)          # [2 * scales, 4, 4]: repeated over the batch in one launch
+        self.K_rows = torch.stack([torch.stack(p) for p in zip(self.K, self.inv_K)])      # [scales, 2, 4, 4]
 
     @torch.no_grad()
     def __call__(self, raw, do_color_aug=None, do_flip=None, jitter=None, generator=None):
@@ -339,85 +456,19 @@ class DeviceInputPipeline:
         to the device in one table, and a device tensor is refused rather than copied back."""
         B = raw[self.frame_idxs[0]].shape[0]
         do_color_aug, do_flip = self._draw_flags(B, do_color_aug, do_flip, generator)
+        inputs, _ = self._colors([raw[f] for f in self.frame_idxs], B, (do_color_aug, do_flip, jitter, generator))
         if self.backend == "hip":
-            inputs, _ = self._colors_hip(raw, B, do_color_aug, do_flip, jitter, generator)
             from ppeadepth import ops
-            KK = ops.repeat_rows(self.K_rows, B)
-            for s in range(self.num_scales):
-                inputs[("K", s)] = KK[s]
-                inputs[("inv_K", s)] = KK[self.num_scales + s]
-            return inputs
-        inputs = self._colors_torch(raw, B, do_color_aug, do_flip, jitter, generator)
-        for s in range(self.num_scales):
-            inputs[("K", s)] = self.K[s][None].repeat(B, 1, 1)
-            inputs[("inv_K", s)] = self.inv_K[s][None].repeat(B, 1, 1)
-        return inputs
-
-    def _draw_flags(self, B, do_color_aug, do_flip, generator):
-        if do_color_aug is None:
-            do_color_aug = (torch.rand(B, generator=generator) > 0.5) if self.is_train else torch.zeros(B, dtype=torch.bool)
-        if do_flip is None:
-            do_flip = (torch.rand(B, generator=generator) > 0.5) if self.is_train else torch.zeros(B, dtype=torch.bool)
-        return do_color_aug, do_flip
-
-    def _colors_torch(self, raw, B, do_color_aug, do_flip, jitter, generator):
-        """("color" | "color_aug", f, s) of planar raw frames in the torch formulation."""
-        flip = do_flip.to(self.device).reshape(-1, 1, 1, 1)
-        inputs = {}
-        for f in self.frame_idxs:
-            img = raw[f].to(self.device)
-            img = torch.where(flip, img.flip(-1), img)
-            blank = (img.reshape(B, -1).sum(1) == 0)
-            for s in range(self.num_scales):
-                img = self.resize[s](img)                               # uint8, chained from the previous scale
-                prm = _jitter_of(jitter, f, s, B, generator)
-                aug = color_jitter(img, prm, do_color_aug.to(self.device) & ~blank)
-                inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
-                inputs[("color_aug", f, s)] = aug.to(torch.float32) / self.unit
-        return inputs
-
-    def _colors_hip(self, raw, B, do_color_aug, do_flip, jitter, generator, extra=None, level0=None):
-        """("color" | "color_aug", f, s) on the HIP kernels.  extra: host int32 words that ride on the call's one parameter
-        copy (returned as a device tensor); level0(flip, nonzero): the first level from another source than dense planar
-        `raw` frames."""
-        from ppeadepth import ops
-        F, S = len(self.frame_idxs), self.num_scales
-        N = F * B                                                   # all frames stacked, frame-major: image n = fi * B + b
-        # parameters in the torch path's order (frame outer, scale inner), then one table and one copy for the whole call
-        prms = []
-        for f in self.frame_idxs:
-            for s in range(S):
-                prms.append(_jitter_of(jitter, f, s, B, generator))
-        by_scale = [p for s in range(S) for fi in range(F) for p in [prms[fi * S + s]]]
-        for t in [do_color_aug, do_flip] + [v for p in prms for v in p.values()]:
-            if t.device.type != "cpu":             # a device tensor would cost a device-to-host copy inside the call
-                raise ValueError("backend 'hip' takes do_color_aug, do_flip and the jitter parameters as host tensors")
-        table = pack_jitter_params(by_scale, do_color_aug.repeat(S * F))                  # [S * N, 10]
-        host = torch.cat([do_flip.to(torch.int32).repeat(F), table.reshape(-1)] + ([] if extra is None else [extra]))
-        dev = host.to(self.device)
-        flip, params = dev[:N], dev[N:N + table.numel()].view(S, N, table.shape[1])
-        nonzero = torch.empty(N, device=self.device, dtype=torch.int32)      # 0: a blank (missing) frame, never jittered
-        levels = []
-        for s in range(S):
-            if s > 0:
-                img = self.resize[s](img)
-            elif level0 is not None:
-                img = level0(flip, nonzero)
-            else:
-                img = self.resize[0]([raw[f].to(self.device).contiguous() for f in self.frame_idxs], flip, nonzero)
-            levels.append(ops.color_jitter_u8(img, params[s], nonzero))
-        inputs = {}
-        for fi, f in enumerate(self.frame_idxs):
-            for s, (color, aug) in enumerate(levels):
-                inputs[("color", f, s)] = color[fi * B:(fi + 1) * B]
-                inputs[("color_aug", f, s)] = aug[fi * B:(fi + 1) * B]
-        return inputs, dev[N + table.numel():]
+            KK = ops.repeat_rows(self.K_rows.view(-1, 4, 4), B).view(self.num_scales, 2, B, 4, 4)      # one launch
+        else:
+            KK = self.K_rows[:, :, None].repeat(1, 1, B, 1, 1)
+        return _put_intrinsics(inputs, KK)
 
 
 DDAD_RAW_HW = (1216, 1936)                      # ddad_dataset.py:137-138
 
 
-class DDADInputPipeline:
+class DDADInputPipeline(_PyramidPipeline):
     """The DDAD loader's image path (datasets/ddad_dataset.py:116-167) for a whole batch: raw uint8 frames 0 and -1 and the
     per-sample intrinsics -> the row-P dictionary.  Not the KITTI pipeline with other sizes:
       * level 0 is Pillow's BILINEAR resize of the raw frame (:121); the loader's LANCZOS resize to that same size (:77) is
@@ -426,78 +477,44 @@ class DDADInputPipeline:
         applied, so nothing is flipped;
       * ("K", s) / ("inv_K", s) are per sample and the SAME matrix at every scale (:132-143): rows 0 and 1 of the 4x4
         float32 matrix times width / raw width and height / raw height, the inverse `np.linalg.pinv` of that float32 matrix.
-        These B small matrices are computed on the host with numpy, exactly as the loader does (a float32 SVD is not
-        reproducible bit for bit in a kernel), and uploaded with the call's one host-to-device copy.
-    backend "hip" (the default on a GPU device; refused on the CPU): per level the horizontal and the vertical resize pass
-    and the uint8 -> fp32 conversion on the kernels of csrc/input_pipeline.hip, all frames stacked, plus one launch that
-    repeats the intrinsics over the scales; "torch": the formulation above.  Both return the same bytes."""
+        These B small matrices are computed on the host with numpy, exactly as the loader does, and are the call's one
+        host-to-device copy.
+    backend "hip": the core's 16 kernels, fill and copy plus one launch that repeats the intrinsics over the scales;
+    "torch": the formulation above.  Both return the same bytes."""
 
     def __init__(self, device, height=384, width=640, raw_hw=DDAD_RAW_HW, num_scales=4, frame_idxs=(0, -1), backend=None):
-        self.device = torch.device(device)
-        self.backend = _backend_of(self.device, backend)
-        self.height, self.width, self.raw_hw, self.num_scales = height, width, tuple(raw_hw), num_scales
-        self.frame_idxs = tuple(frame_idxs)
-        self.resize, prev = [], self.raw_hw
-        for s in range(num_scales):
-            hw = (height // 2 ** s, width // 2 ** s)
-            self.resize.append(LanczosResize(prev, hw, self.device, self.backend, first=(s == 0),
-                                             filter="bilinear" if s == 0 else "lanczos"))
-            prev = hw
-        self.unit = torch.full((), 255.0, device=self.device)          # see DeviceInputPipeline
+        super().__init__(raw_hw, height, width, device, num_scales, frame_idxs, backend, level0_filter="bilinear")
+        self.raw_hw = tuple(raw_hw)
 
     def intrinsics(self, intrinsics):
         """[B,3,3] camera matrices -> float32 [2,B,4,4]: K and inv_K of ddad_dataset.py:132-143, in numpy on the host."""
-        intr = intrinsics.cpu().numpy() if torch.is_tensor(intrinsics) else np.asarray(intrinsics)
-        if intr.ndim != 3 or intr.shape[1:] != (3, 3):
-            raise ValueError(f"intrinsics: [B,3,3] camera matrices, got {intr.shape}")
+        intr = _camera_matrices(intrinsics, "intrinsics")
+
+        def scale(row0, row1):
+            row0 *= self.width / self.raw_hw[1]
+            row1 *= self.height / self.raw_hw[0]
         out = np.zeros((2, len(intr), 4, 4), np.float32)
         for b in range(len(intr)):
-            K = np.zeros((4, 4), np.float32)
-            K[:3, :3] = intr[b].copy()
-            K[3][3] = 1
-            K[0, :] *= self.width / self.raw_hw[1]
-            K[1, :] *= self.height / self.raw_hw[0]
-            out[0, b], out[1, b] = K, np.linalg.pinv(K)
+            out[0, b], out[1, b] = _k4_and_pinv(intr[b], scale)
         return out
 
     @torch.no_grad()
     def __call__(self, raw, intrinsics):
         """raw: {frame id: uint8 [B,3,Hraw,Wraw]}; intrinsics: [B,3,3] (host tensor or array)."""
-        B = raw[self.frame_idxs[0]].shape[0]
+        B, S = raw[self.frame_idxs[0]].shape[0], self.num_scales
         for f in self.frame_idxs:
             if tuple(raw[f].shape) != (B, 3) + self.raw_hw or raw[f].dtype != torch.uint8:
                 raise ValueError(f"frame {f}: expected uint8 {(B, 3) + self.raw_hw}, got {raw[f].dtype} {tuple(raw[f].shape)}")
         kk = self.intrinsics(intrinsics)
         if kk.shape[1] != B:
             raise ValueError(f"{kk.shape[1]} camera matrices for a batch of {B}")
-        kk = torch.from_numpy(kk).to(self.device)                      # the call's parameter copy
-        F, S = len(self.frame_idxs), self.num_scales
-        inputs = {}
+        inputs, kk = self._colors([raw[f] for f in self.frame_idxs], B, kk=kk)
         if self.backend == "hip":
             from ppeadepth import ops
-            img = [raw[f].to(self.device).contiguous() for f in self.frame_idxs]
-            # no jitter: an all-zero parameter table (apply = 0, written on the device) turns the ColorJitter launch into the
-            # uint8 -> fp32 conversion of both outputs
-            params = torch.zeros(F * B, ops.JITTER_PARAM_WORDS, device=self.device, dtype=torch.int32)
-            for s in range(S):
-                img = self.resize[s](img)
-                color, aug = ops.color_jitter_u8(img, params)
-                for fi, f in enumerate(self.frame_idxs):
-                    inputs[("color", f, s)] = color[fi * B:(fi + 1) * B]
-                    inputs[("color_aug", f, s)] = aug[fi * B:(fi + 1) * B]
             KK = ops.repeat_rows(kk.reshape(1, -1), S).reshape(S, 2, B, 4, 4)
         else:
-            for f in self.frame_idxs:
-                img = raw[f].to(self.device)
-                for s in range(S):
-                    img = self.resize[s](img)
-                    inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
-                    inputs[("color_aug", f, s)] = inputs[("color", f, s)].clone()
             KK = kk[None].repeat(S, 1, 1, 1, 1)
-        for s in range(S):
-            inputs[("K", s)] = KK[s, 0]
-            inputs[("inv_K", s)] = KK[s, 1]
-        return inputs
+        return _put_intrinsics(inputs, KK)
 
 
 # ---- Cityscapes: the training triplets and the evaluation frames, read as views ---------------------------------------
@@ -525,28 +542,26 @@ def cityscapes_intrinsics(cameras, raw_width, raw_height, width, height, num_sca
     sample AND per level: the float32 4x4 of fx, fy, u0, v0 with row 0 / raw_width and row 1 / raw_height (`load_intrinsics`;
     the evaluation loader passes the Python float 1024 * 0.75), then rows 0 and 1 times width // 2**s and height // 2**s
     (mono_dataset.py:173-182), the inverse `np.linalg.pinv` of that float32 matrix.  In numpy on the host, in the loader's
-    operations and order, for the reason `DDADInputPipeline` gives."""
-    cam = cameras.cpu().numpy() if torch.is_tensor(cameras) else np.asarray(cameras)
-    if cam.ndim != 3 or cam.shape[1:] != (3, 3):
-        raise ValueError(f"cameras: [B,3,3] camera matrices, got {cam.shape}")
+    operations and order."""
+    cam = _camera_matrices(cameras, "cameras")
     out = np.zeros((num_scales, 2, len(cam), 4, 4), np.float32)
     for b, c in enumerate(cam):
         for s in range(num_scales):
-            K = np.array([[c[0, 0], 0, c[0, 2], 0], [0, c[1, 1], c[1, 2], 0], [0, 0, 1, 0], [0, 0, 0, 1]]).astype(np.float32)
-            K[0, :] /= raw_width
-            K[1, :] /= raw_height
-            K[0, :] *= width // (2 ** s)
-            K[1, :] *= height // (2 ** s)
-            out[s, 0, b], out[s, 1, b] = K, np.linalg.pinv(K)
+            def scale(row0, row1):
+                row0 /= raw_width
+                row1 /= raw_height
+                row0 *= width // (2 ** s)
+                row1 *= height // (2 ** s)
+            out[s, 0, b], out[s, 1, b] = _k4_and_pinv([[c[0, 0], 0, c[0, 2]], [0, c[1, 1], c[1, 2]], [0, 0, 1]], scale)
     return out
 
 
-class CityscapesInputPipeline(DeviceInputPipeline):
+class CityscapesInputPipeline(_PyramidPipeline):
     """The preprocessed-Cityscapes loader (datasets/cityscapes_preprocessed_dataset.py through MonoDataset) for a whole
     batch: one wide image per item that holds frames -1, 0, +1 side by side, uint8 [B, Hraw, 3 * Wraw, 3] as the JPEG
     decoder returns it (HWC), and the item's camera -> the row-P dictionary.
       * frame -1 is columns [0, w), frame 0 [w, 2w), frame +1 [2w, 3w) (:62-66); the flip mirrors each third on its own;
-      * pyramid, ColorJitter (same draw order), blank-frame rule and ToTensor are `DeviceInputPipeline`'s, by its code;
+      * pyramid, ColorJitter (same draw order), blank-frame rule and ToTensor are `DeviceInputPipeline`'s, by the core's code;
       * ("K", s) / ("inv_K", s) are per sample and per level (`cityscapes_intrinsics`), uploaded with the call's one
         parameter copy.
     backend "hip": the first horizontal pass reads the three windows in place (ops.lanczos_resize_view_u8: no third is
@@ -557,39 +572,28 @@ class CityscapesInputPipeline(DeviceInputPipeline):
                  is_train=True, backend=None):
         if any(f not in (-1, 0, 1) for f in frame_idxs):
             raise ValueError(f"frame_idxs {tuple(frame_idxs)}: the wide image holds frames -1, 0 and 1")
-        super().__init__(raw_hw, height, width, device, num_scales, frame_idxs, K=None, is_train=is_train, backend=backend)
-        self.raw_hw = tuple(raw_hw)
+        super().__init__(raw_hw, height, width, device, num_scales, frame_idxs, backend, hwc=True)
+        self.raw_hw, self.is_train = tuple(raw_hw), is_train
 
     @torch.no_grad()
     def __call__(self, triplets, cameras, do_color_aug=None, do_flip=None, jitter=None, generator=None):
-        """triplets: uint8 [B, Hraw, 3 * Wraw, 3]; cameras: [B,3,3] (host tensor or array); the rest as the parent's."""
+        """triplets: uint8 [B, Hraw, 3 * Wraw, 3]; cameras: [B,3,3] (host tensor or array); the rest as
+        `DeviceInputPipeline`'s."""
         Hraw, Wraw = self.raw_hw
         if triplets.dim() != 4 or tuple(triplets.shape[1:]) != (Hraw, 3 * Wraw, 3) or triplets.dtype != torch.uint8:
             raise ValueError(f"expected uint8 [B, {Hraw}, {3 * Wraw}, 3] (three frames side by side, HWC), got "
                              f"{triplets.dtype} {tuple(triplets.shape)}")
-        B, S = triplets.shape[0], self.num_scales
-        kk = cityscapes_intrinsics(cameras, Wraw, Hraw, self.width, self.height, S)
+        B = triplets.shape[0]
+        kk = cityscapes_intrinsics(cameras, Wraw, Hraw, self.width, self.height, self.num_scales)
         if kk.shape[2] != B:
             raise ValueError(f"{kk.shape[2]} camera matrices for a batch of {B}")
         do_color_aug, do_flip = self._draw_flags(B, do_color_aug, do_flip, generator)
         triplets = triplets.to(self.device)
-        thirds = {f: triplets[:, :, (f + 1) * Wraw:(f + 2) * Wraw] for f in self.frame_idxs}
-        if self.backend == "hip":
-            inputs, kdev = self._colors_hip(
-                None, B, do_color_aug, do_flip, jitter, generator, extra=torch.from_numpy(kk).view(torch.int32).reshape(-1),
-                level0=lambda flip, nonzero: self.resize[0].views([thirds[f] for f in self.frame_idxs], flip, nonzero))
-            KK = kdev.view(torch.float32).view(S, 2, B, 4, 4)
-        else:
-            planar = {f: v.permute(0, 3, 1, 2) for f, v in thirds.items()}
-            inputs = self._colors_torch(planar, B, do_color_aug, do_flip, jitter, generator)
-            KK = torch.from_numpy(kk).to(self.device)
-        for s in range(S):
-            inputs[("K", s)] = KK[s, 0]
-            inputs[("inv_K", s)] = KK[s, 1]
-        return inputs
+        thirds = [triplets[:, :, (f + 1) * Wraw:(f + 2) * Wraw] for f in self.frame_idxs]
+        return _put_intrinsics(*self._colors(thirds, B, (do_color_aug, do_flip, jitter, generator), kk))
 
 
-class CityscapesEvalPipeline:
+class CityscapesEvalPipeline(_PyramidPipeline):
     """The Cityscapes evaluation loader (datasets/cityscapes_evaldataset.py through MonoDataset) for a whole batch: the raw
     frames 0 and -1, uint8 [B, Hraw, Wraw, 3] (HWC), and the item's camera -> the row-P dictionary.
       * the frame is cropped to its top Hraw * 3 // 4 rows (:66-68) before the resize: in HWC a prefix of each image, so
@@ -601,17 +605,9 @@ class CityscapesEvalPipeline:
 
     def __init__(self, device, height=192, width=512, raw_hw=CITYSCAPES_RAW_HW, num_scales=4, frame_idxs=(0, -1),
                  backend=None):
-        self.device = torch.device(device)
-        self.backend = _backend_of(self.device, backend)
-        self.height, self.width, self.raw_hw, self.num_scales = height, width, tuple(raw_hw), num_scales
-        self.frame_idxs = tuple(frame_idxs)
+        self.raw_hw = tuple(raw_hw)
         self.crop_h = self.raw_hw[0] * 3 // 4
-        self.resize, prev = [], (self.crop_h, self.raw_hw[1])
-        for s in range(num_scales):
-            hw = (height // 2 ** s, width // 2 ** s)
-            self.resize.append(LanczosResize(prev, hw, self.device, self.backend, first=(s == 0)))
-            prev = hw
-        self.unit = torch.full((), 255.0, device=self.device)          # see DeviceInputPipeline
+        super().__init__((self.crop_h, self.raw_hw[1]), height, width, device, num_scales, frame_idxs, backend, hwc=True)
 
     @torch.no_grad()
     def __call__(self, raw, cameras):
@@ -621,30 +617,9 @@ class CityscapesEvalPipeline:
             if tuple(raw[f].shape) != (B,) + self.raw_hw + (3,) or raw[f].dtype != torch.uint8:
                 raise ValueError(f"frame {f}: expected uint8 {(B,) + self.raw_hw + (3,)}, got {raw[f].dtype} "
                                  f"{tuple(raw[f].shape)}")
-        F, S = len(self.frame_idxs), self.num_scales
-        kk = cityscapes_intrinsics(cameras, self.raw_hw[1], self.raw_hw[0] * 0.75, self.width, self.height, S)
+        kk = cityscapes_intrinsics(cameras, self.raw_hw[1], self.raw_hw[0] * 0.75, self.width, self.height, self.num_scales)
         if kk.shape[2] != B:
             raise ValueError(f"{kk.shape[2]} camera matrices for a batch of {B}")
-        KK = torch.from_numpy(kk).to(self.device)                      # the call's parameter copy
         top = [raw[f].to(self.device)[:, :self.crop_h] for f in self.frame_idxs]
-        inputs = {}
-        if self.backend == "hip":
-            from ppeadepth import ops
-            params = torch.zeros(F * B, ops.JITTER_PARAM_WORDS, device=self.device, dtype=torch.int32)      # see DDADInputPipeline
-            for s in range(S):
-                img = self.resize[0].views(top) if s == 0 else self.resize[s](img)
-                color, aug = ops.color_jitter_u8(img, params)
-                for fi, f in enumerate(self.frame_idxs):
-                    inputs[("color", f, s)] = color[fi * B:(fi + 1) * B]
-                    inputs[("color_aug", f, s)] = aug[fi * B:(fi + 1) * B]
-        else:
-            for fi, f in enumerate(self.frame_idxs):
-                img = top[fi]
-                for s in range(S):
-                    img = self.resize[0].views(img) if s == 0 else self.resize[s](img)
-                    inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
-                    inputs[("color_aug", f, s)] = inputs[("color", f, s)].clone()
-        for s in range(S):
-            inputs[("K", s)] = KK[s, 0]
-            inputs[("inv_K", s)] = KK[s, 1]
-        return inputs
+        return _put_intrinsics(*self._colors(top, B, kk=kk))
+

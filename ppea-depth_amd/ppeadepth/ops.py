@@ -900,6 +900,36 @@ def _taps(table, outsize, what):
     return ptr(table, torch.int32), table.shape[1] - 2
 
 
+def _lanczos_resize(srcs, dims, out_hw, taps_h, taps_v, flip, nonzero, horizontal):
+    """The body of `lanczos_resize_u8` and `lanczos_resize_view_u8`: the checks they share, the horizontal pass over srcs
+    (each `dims` = (n, C, Hin, Win); `horizontal(ptrs, taps, kmax, *rest)` calls the entry point of their layout; skipped
+    when taps_h is None) and the vertical pass."""
+    n, C, Hin, Win = dims
+    N, (Hout, Wout) = n * len(srcs), out_hw
+    for s in srcs:
+        if not s.is_cuda:
+            raise _abi.PpeaKernelError("PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback); got a CPU tensor")
+        if s.dtype != torch.uint8:
+            raise _abi.PpeaKernelError(f"expected torch.uint8, got {s.dtype}")
+    if taps_v is None and Hin != Hout:
+        raise _abi.PpeaKernelError("a change of height needs the vertical pass")
+    for t in (flip, nonzero):
+        if t is not None and tuple(t.shape) != (N,):
+            raise _abi.PpeaKernelError(f"expected one flag per image ({N}), got {tuple(t.shape)}")
+    cur = srcs[0]
+    if taps_h is not None:
+        tp, kmax = _taps(taps_h, Wout, "horizontal")
+        ptrs = (_ct.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
+        cur = torch.empty(N, C, Hin, Wout, device=cur.device, dtype=torch.uint8)
+        horizontal(ptrs, tp, kmax, ptr(flip, torch.int32), ptr(nonzero, torch.int32), ptr(cur), Hin, Win, Wout, stream_ptr())
+    if taps_v is not None:
+        tp, kmax = _taps(taps_v, Hout, "vertical")
+        out = torch.empty(N, C, Hout, Wout, device=cur.device, dtype=torch.uint8)
+        call("ppea_lanczos_v_u8", ptr(cur, torch.uint8), tp, kmax, ptr(out), N * C, Hin, Hout, Wout, stream_ptr())
+        cur = out
+    return cur
+
+
 @torch.no_grad()
 def lanczos_resize_u8(src, out_hw, taps_h=None, taps_v=None, flip=None, nonzero=None):
     """src: uint8 [N,C,Hin,Win], or a list of such tensors of one shape (read as if concatenated along N, without the
@@ -910,33 +940,16 @@ def lanczos_resize_u8(src, out_hw, taps_h=None, taps_v=None, flip=None, nonzero=
     srcs = list(src) if isinstance(src, (list, tuple)) else [src]
     if not srcs or any(s.dim() != 4 or s.shape != srcs[0].shape for s in srcs):
         raise _abi.PpeaKernelError("expected uint8 [N,C,H,W] images of one shape")
+    if not all(s.is_contiguous() for s in srcs):
+        raise _abi.PpeaKernelError("non-contiguous tensor passed to a HIP kernel")
     n, C, Hin, Win = srcs[0].shape
-    N, (Hout, Wout) = n * len(srcs), out_hw
-    dev = srcs[0].device
-    if taps_h is None and (Win != Wout or flip is not None or nonzero is not None):
+    if taps_h is None and (Win != out_hw[1] or flip is not None or nonzero is not None):
         raise _abi.PpeaKernelError("the flip, the non-zero mark and a change of width need the horizontal pass")
-    if taps_v is None and Hin != Hout:
-        raise _abi.PpeaKernelError("a change of height needs the vertical pass")
-    for t in (flip, nonzero):
-        if t is not None and tuple(t.shape) != (N,):
-            raise _abi.PpeaKernelError(f"expected one flag per image ({N}), got {tuple(t.shape)}")
-    cur = None
-    if taps_h is not None:
-        tp, kmax = _taps(taps_h, Wout, "horizontal")
-        ptrs = (_ct.c_void_p * len(srcs))(*[ptr(s, torch.uint8).value for s in srcs])
-        cur = torch.empty(N, C, Hin, Wout, device=dev, dtype=torch.uint8)
-        call("ppea_lanczos_h_u8", ptrs, len(srcs), n * C, tp, kmax, ptr(flip, torch.int32), C, ptr(nonzero, torch.int32),
-             ptr(cur), Hin, Win, Wout, stream_ptr())
-    elif len(srcs) != 1:
+    if taps_h is None and len(srcs) != 1:
         raise _abi.PpeaKernelError("several sources are read by the horizontal pass only")
-    else:
-        cur = srcs[0]
-    if taps_v is not None:
-        tp, kmax = _taps(taps_v, Hout, "vertical")
-        out = torch.empty(N, C, Hout, Wout, device=dev, dtype=torch.uint8)
-        call("ppea_lanczos_v_u8", ptr(cur, torch.uint8), tp, kmax, ptr(out), N * C, Hin, Hout, Wout, stream_ptr())
-        cur = out
-    return cur
+    return _lanczos_resize(srcs, (n, C, Hin, Win), out_hw, taps_h, taps_v, flip, nonzero,
+                           lambda ptrs, tp, kmax, fl, nz, *rest: call("ppea_lanczos_h_u8", ptrs, len(srcs), n * C, tp, kmax, fl,
+                                                                     C, nz, *rest))
 
 
 @torch.no_grad()
@@ -949,33 +962,13 @@ def lanczos_resize_view_u8(src, out_hw, taps_h, taps_v=None, flip=None, nonzero=
     srcs = list(src) if isinstance(src, (list, tuple)) else [src]
     if not srcs or any(s.dim() != 4 or s.shape != srcs[0].shape or s.stride() != srcs[0].stride() for s in srcs):
         raise _abi.PpeaKernelError("expected uint8 [n,H,W,C] views of one shape and one set of strides")
-    for s in srcs:
-        if not s.is_cuda:
-            raise _abi.PpeaKernelError("PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback); got a CPU tensor")
-        if s.dtype != torch.uint8:
-            raise _abi.PpeaKernelError(f"expected torch.uint8, got {s.dtype}")
-    n, Hin, Win, C = srcs[0].shape
-    N, (Hout, Wout) = n * len(srcs), out_hw
-    dev = srcs[0].device
     if taps_h is None:
         raise _abi.PpeaKernelError("a view is read by the horizontal pass: give its tap table")
-    if taps_v is None and Hin != Hout:
-        raise _abi.PpeaKernelError("a change of height needs the vertical pass")
-    for t in (flip, nonzero):
-        if t is not None and tuple(t.shape) != (N,):
-            raise _abi.PpeaKernelError(f"expected one flag per image ({N}), got {tuple(t.shape)}")
+    n, Hin, Win, C = srcs[0].shape
     item, row, pixel, channel = srcs[0].stride()              # uint8: elements are bytes
-    tp, kmax = _taps(taps_h, Wout, "horizontal")
-    ptrs = (_ct.c_void_p * len(srcs))(*[s.data_ptr() for s in srcs])
-    cur = torch.empty(N, C, Hin, Wout, device=dev, dtype=torch.uint8)
-    call("ppea_lanczos_h_view_u8", ptrs, len(srcs), n, C, pixel, row, channel, item, tp, kmax,
-         ptr(flip, torch.int32), ptr(nonzero, torch.int32), ptr(cur), Hin, Win, Wout, stream_ptr())
-    if taps_v is not None:
-        tp, kmax = _taps(taps_v, Hout, "vertical")
-        out = torch.empty(N, C, Hout, Wout, device=dev, dtype=torch.uint8)
-        call("ppea_lanczos_v_u8", ptr(cur, torch.uint8), tp, kmax, ptr(out), N * C, Hin, Hout, Wout, stream_ptr())
-        cur = out
-    return cur
+    return _lanczos_resize(srcs, (n, C, Hin, Win), out_hw, taps_h, taps_v, flip, nonzero,
+                           lambda ptrs, tp, kmax, *rest: call("ppea_lanczos_h_view_u8", ptrs, len(srcs), n, C, pixel, row,
+                                                              channel, item, tp, kmax, *rest))
 
 
 @torch.no_grad()

@@ -85,6 +85,63 @@ def test_lanczos_resize_equals_pillow(device):
         assert np.array_equal(got[n].permute(1, 2, 0).numpy(), np.asarray(im)), n
 
 
+# ---- 1b. planar frames through the generic-stride horizontal kernel -------------------------------------------------
+def _carved(parts, device):
+    """The host tensors as contiguous views of ONE device buffer of 255s, at the byte offsets 1, 7 (mod 16), 1, 7, ..."""
+    starts, end = [], 0
+    for k, t in enumerate(parts):
+        start = -(-end // 16) * 16 + (1, 7)[k % 2]
+        starts.append(start)
+        end = start + t.numel()
+    buf = torch.full((end + 16,), 255, dtype=torch.uint8, device=device)
+    views = [buf[s:s + t.numel()].view(t.shape) for s, t in zip(starts, parts)]
+    for v, t in zip(views, parts):
+        v.copy_(t)
+    assert [(v.data_ptr() - buf.data_ptr()) % 16 for v in views[:2]] == [1, 7][:len(views)] and buf.data_ptr() % 16 == 0
+    return views
+
+
+# shape -> (H, Wout), the flips, the images set to zero, the number of sources:
+#   141 rows at 4 per workgroup: the last workgroup is partial; 101 is no multiple of the 16-byte pitch
+#   C = 1 (rows per image = H), 10 rows per workgroup across image borders, flips and one blank image
+#   an output wider than a workgroup: one row per workgroup
+#   two sources off every alignment
+PLANAR_CASES = {
+    "partial_last_workgroup": ((1, 3, 47, 101), (47, 64), [0], [], 1),
+    "one_channel_flips_blank": ((5, 1, 9, 40), (9, 24), [1, 0, 1, 1, 0], [3], 1),
+    "one_row_per_workgroup": ((2, 3, 3, 333), (3, 300), [0, 1], [], 1),
+    "two_unaligned_sources": ((4, 3, 5, 37), (5, 24), [0, 1, 1, 0], [2], 2),
+}
+
+
+@pytest.mark.parametrize("case", sorted(PLANAR_CASES))
+def test_planar_frames_through_the_strided_horizontal_kernel(device, case):
+    from PIL import Image
+    from ppeadepth import input_pipeline as ip
+    shape, out_hw, flips, blank, nsrc = PLANAR_CASES[case]
+    N, C, in_hw = shape[0], shape[1], shape[2:]
+    img = torch.randint(0, 256, shape, generator=torch.Generator().manual_seed(N * in_hw[1]), dtype=torch.uint8)
+    img[:, :, 0, 0] = 255                                         # no image is blank by chance
+    for n in blank:
+        img[n] = 0
+    flip = torch.tensor(flips, dtype=torch.bool)
+    flipped = torch.where(flip.reshape(-1, 1, 1, 1), img.flip(-1), img)
+    want = ip.LanczosResize(in_hw, out_hw, "cpu")(flipped)
+    srcs = _carved(list(img.chunk(nsrc)), device)
+    nonzero = torch.full((N,), 7, device=device, dtype=torch.int32)
+    first = ip.LanczosResize(in_hw, out_hw, device, "hip", first=True)
+    assert first.taps_v is None                                   # the horizontal pass alone
+    got = first(srcs if nsrc > 1 else srcs[0], flip.to(device, torch.int32), nonzero)
+    assert got.dtype == torch.uint8 and tuple(got.shape) == (N, C) + out_hw and torch.equal(got.cpu(), want)
+    assert nonzero.tolist() == [int(n not in blank) for n in range(N)]
+    if not any(flips):                                            # and without the optional arguments
+        assert torch.equal(first(srcs if nsrc > 1 else srcs[0]).cpu(), want)
+    if C == 3:
+        for n in range(N):
+            im = Image.fromarray(flipped[n].permute(1, 2, 0).numpy()).resize((out_hw[1], out_hw[0]), Image.LANCZOS)
+            assert np.array_equal(got[n].cpu().permute(1, 2, 0).numpy(), np.asarray(im)), n
+
+
 # ---- 2. jitter, all orders ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("ends", [False, True])
 def test_color_jitter_every_operation_order(device, ends):
@@ -223,3 +280,69 @@ def test_pipeline_at_the_workload_ratio(device):
     raw, aug, flip, jit = _pipeline_case(raw_hw, H, W, B, 61)
     want = ip.DeviceInputPipeline(raw_hw, H, W, "cpu")(raw, aug, flip, jit)
     _assert_same(ip.DeviceInputPipeline(raw_hw, H, W, device)(raw, aug, flip, jit), want)
+
+
+# ---- 6. launches of the other three pipelines -----------------------------------------------------------------------
+CONV_OR_GEMM = re.compile(r"Cijk_|igemm|ck::|ck_tile|miopen|MIOpen|gemm|Gemm|GEMM|rocblas|hipblaslt|conv|Conv")
+
+
+def _cameras(B):
+    cam = torch.zeros(B, 3, 3, dtype=torch.float64)
+    cam[:, 0, 0], cam[:, 1, 1], cam[:, 2, 2] = 1131.0 + torch.arange(B), 1130.0 - torch.arange(B), 1
+    cam[:, 0, 2], cam[:, 1, 2] = 523.0, 191.0 + torch.arange(B)
+    return cam
+
+
+def _ddad_call(device, B):
+    from ppeadepth import input_pipeline as ip
+    g = torch.Generator().manual_seed(71)
+    raw = {f: torch.randint(0, 256, (B, 3, 50, 77), generator=g, dtype=torch.uint8).to(device) for f in (0, -1)}
+    pipe, cams = ip.DDADInputPipeline(device, 16, 24, (50, 77)), _cameras(B)
+    return lambda: pipe(raw, cams)
+
+
+def _cityscapes_training_call(device, B):
+    from ppeadepth import input_pipeline as ip
+    g = torch.Generator().manual_seed(72)
+    trip = torch.randint(0, 256, (B, 40, 3 * 52, 3), generator=g, dtype=torch.uint8)
+    trip[B - 1, :, 2 * 52:] = 0                                   # a missing neighbour frame
+    trip = trip.to(device)
+    jit = {(f, s): ip.draw_jitter_params(B, g) for f in (0, -1, 1) for s in range(4)}
+    pipe, cams = ip.CityscapesInputPipeline(device, 16, 24, (40, 52)), _cameras(B)
+    aug, flip = torch.ones(B, dtype=torch.bool), torch.arange(B) % 2 == 0
+    return lambda: pipe(trip, cams, aug, flip, jit)
+
+
+def _cityscapes_eval_call(device, B):
+    from ppeadepth import input_pipeline as ip
+    g = torch.Generator().manual_seed(73)
+    raw = {f: torch.randint(0, 256, (B, 42, 64, 3), generator=g, dtype=torch.uint8).to(device) for f in (0, -1)}
+    pipe, cams = ip.CityscapesEvalPipeline(device, 16, 24, (42, 64)), _cameras(B)
+    return lambda: pipe(raw, cams)
+
+
+# (the pipeline's kernels, memsets, fills, copies) of one call, as measured on the commit before the four pipelines got
+# one core, which this one may not exceed: 4 levels x (2 resize passes + 2 jitter launches), + `repeat_rows` for DDAD; the
+# memset of the blank-frame marks, or where nothing is jittered the fill of the all-zero parameter table (torch.zeros: an
+# ATen fill kernel); the one host-to-device copy
+PIPELINE_LAUNCHES = {
+    "ddad": (_ddad_call, (17, 0, 1, 1)),
+    "cityscapes_training": (_cityscapes_training_call, (16, 1, 0, 1)),
+    "cityscapes_eval": (_cityscapes_eval_call, (16, 0, 1, 1)),
+}
+
+
+def _launch_counts(names):
+    """(pipeline kernels, memsets, fills, copies, anything else)"""
+    found = [len([n for n in names if re.search(p, n)])
+             for p in (r"lanczos_[hv]|jitter_(sum|out)|repeat_rows", "Memset", "FillFunctor", "Memcpy")]
+    return tuple(found) + (len(names) - sum(found),)
+
+
+@pytest.mark.parametrize("which", sorted(PIPELINE_LAUNCHES))
+def test_launches_do_not_depend_on_the_batch_size(device, which):
+    make, expected = PIPELINE_LAUNCHES[which]
+    n2, n1 = _device_events(make(device, 2)), _device_events(make(device, 1))
+    print(f"{which}: {len(n2)} device events at B=2, {len(n1)} at B=1: {_launch_counts(n2)} {sorted(set(n2))}")
+    assert _launch_counts(n2) == _launch_counts(n1) == expected + (0,) and len(n1) == len(n2)
+    assert not [n for n in n2 if CONV_OR_GEMM.search(n)]
