@@ -380,7 +380,8 @@ int ppea_reflect_pad1_bwd_bf16(const void* dout, void* din, long planes, int H, 
  *     grid [B,H,W,2] normalised to [-1,1] (x then y); eps added to z (1e-7).
  *     bwd: d_depth [B,1,H,W] and dP [B,3,4] overwritten; dP is summed from per-block partials in a caller-owned
  *     workspace of ppea_backproject_project_bwd_workspace_bytes(B, H, W) bytes in a FIXED order (no float atomics:
- *     the pose gradient is bitwise reproducible).
+ *     the pose gradient is bitwise reproducible).  B is the grid's y extent and a pixel index an int: B > 65535 or
+ *     H * W > 0x7fffff00 is PPEA_ERR_UNSUPPORTED, here and for the split entry points below.
  * ---------------------------------------------------------------------------------------- */
 int ppea_backproject_project_fwd_f32(const float* depth, const float* inv_K, const float* P,
                                      float* grid, int B, int H, int W, float eps, void* stream);
@@ -401,8 +402,7 @@ int ppea_backproject_project_bwd_f32(const float* depth, const float* inv_K, con
  *     dP [B,4,4] (12 sums, row 3 zeros) are overwritten, either may be NULL (not wanted), not both.
  *   Both backward passes sum per-block partials from a caller-owned workspace of *_bwd_workspace_bytes(B, H, W) bytes in a
  *   fixed order.  Where row 3 of `points` is 1, project3d(backproject(.)) and its gradients carry the fused kernels' bits.
- *   B is the grid's y extent: B > 65535 is PPEA_ERR_UNSUPPORTED.  Note that `P` / `dP` here are [B,4,4], unlike the
- *   [B,3,4] `P` / `dP` of ppea_backproject_project_* above.
+ *   Note that `P` / `dP` here are [B,4,4], unlike the [B,3,4] `P` / `dP` of ppea_backproject_project_* above.
  * ---------------------------------------------------------------------------------------- */
 int ppea_backproject_fwd_f32(const float* depth, const float* inv_K, float* points, int B, int H, int W, void* stream);
 long ppea_backproject_bwd_workspace_bytes(int B, int H, int W);
@@ -479,32 +479,28 @@ int ppea_smooth_bwd_f32(const float* disp, const float* img, float gx, float gy,
                         int B, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * A24/A25  per-pixel loss selection (trainer.py:1069-1114): min over the two source frames,
+ * A24/A25  per-pixel loss selection (trainer.py:1069-1114): min over the S source frames, S in {1, 2},
  *      selec_reproj overwrite, identity min + tie-break noise, automask argmin.
- *      reproj, identity [B,2,H,W]; warped_m1/p1 [B,3,H,W]; noise [B,1,H,W] (already * 1e-5) or
- *      NULL.  Outputs: sel [B,1,H,W] selected reprojection loss; src_idx uint8 [B,1,H,W]
- *      (0/1 = which of reproj's two channels feeds `sel`, 2 = forced zero);
- *      frame_idx int64 [B,1,H,W] (argmin over the two frames, first minimum);
+ *      reproj, identity [B,S,H,W]; warped_0 / warped_1 [B,C,H,W], read for selec_reproj only and NULL
+ *      otherwise; noise [B,1,H,W] (already * 1e-5) or NULL.  Outputs: sel [B,1,H,W] selected
+ *      reprojection loss; src_idx uint8 [B,1,H,W] (0/1 = which of reproj's channels feeds `sel`,
+ *      2 = forced zero); frame_idx int64 [B,1,H,W] (argmin over the frames, first minimum);
  *      auto_idx int64 [B,1,H,W] (argmin over [sel, identity_min+noise], first minimum).
+ *      S = 1 (frame_ids [0, -1], the two-frame items of DDAD): sel is the only channel, src_idx = 0 and
+ *      frame_idx = 0 everywhere, the identity minimum is the only identity channel (+ noise), auto_idx by
+ *      the same first-minimum / NaN rule; no warped frame is read, and selec_reproj != 0 is
+ *      PPEA_ERR_UNSUPPORTED (the reference reads the warped frame +1 there, trainer.py:1077-1083).
  * ---------------------------------------------------------------------------------------- */
-int ppea_loss_select_f32(const float* reproj, const float* identity, const float* warped_m1,
-                         const float* warped_p1, const float* noise, float* sel,
+int ppea_loss_select_f32(const float* reproj, const float* identity, const float* warped_0,
+                         const float* warped_1, const float* noise, float* sel,
                          uint8_t* src_idx, int64_t* frame_idx, int64_t* auto_idx,
-                         int B, int C, int H, int W, int selec_reproj, void* stream);
-/* The same for S source frames, S in {1, 2}: reproj, identity [B,S,H,W].  S = 2 is ppea_loss_select_f32 bit for bit
- * (warped_0 / warped_1 = warped_m1 / warped_p1, read for selec_reproj only and NULL otherwise).  S = 1 (frame_ids [0, -1],
- * the two-frame items of DDAD): sel is the only channel, src_idx = 0 and frame_idx = 0 everywhere, the identity minimum is
- * the only identity channel (+ noise), auto_idx by the same first-minimum / NaN rule; no warped frame is read, and
- * selec_reproj != 0 is PPEA_ERR_UNSUPPORTED (the reference reads the warped frame +1 there, trainer.py:1077-1083). */
-int ppea_loss_select_n_f32(const float* reproj, const float* identity, const float* warped_0,
-                           const float* warped_1, const float* noise, float* sel,
-                           uint8_t* src_idx, int64_t* frame_idx, int64_t* auto_idx,
-                           int B, int S, int C, int H, int W, int selec_reproj, void* stream);
+                         int B, int S, int C, int H, int W, int selec_reproj, void* stream);
 
 /* Tail of compute_losses (trainer.py:1092-1139) after the per-pixel selection: mask (automask argmin == 0, or for the
  * multi-frame pass consistency_mask * (1 - augmentation_mask)), rl = sum(sel * mask) / (sum(mask) + 1e-7), and for the
  * multi-frame pass the consistency loss mean(|multi - mono| * (1 - mask)) and its target.  One pass + finalize forward, one
- * pass backward (d reproj [B][2][H][W] routed by the selection's source index, d multi_depth); fixed summation order.
+ * pass backward (d reproj [B][S][H][W], S in {1, 2}, routed by the selection's source index, d multi_depth; the forward
+ * does not see the frames: it reads the selected loss); fixed summation order.
  *   sel, mask, target, multi, mono [B][1][H][W] fp32; auto_idx int64 or NULL; cons [B][H][W] or NULL; aug [B] or NULL;
  *   partial: ppea_loss_tail_blocks(B*H*W) * 3 floats; out[0] = rl, out[1] = consistency loss, out[2] = 1/(sum(mask)+1e-7);
  *   g_rl / g_con: device scalars (gradients of out[0] / out[1]) or NULL. */
@@ -513,13 +509,8 @@ int ppea_loss_tail_fwd_f32(const float* sel, const int64_t* auto_idx, const floa
                            const float* mono, float* mask, float* target, float* partial, float* out, int B, int H, int W,
                            int is_multi, void* stream);
 int ppea_loss_tail_bwd_f32(const float* mask, const uint8_t* src, const float* out, const float* g_rl, const float* g_con,
-                           const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int H, int W,
-                           void* stream);
-/* The backward for S source frames, S in {1, 2}: d_reproj [B][S][H][W]; S = 2 is ppea_loss_tail_bwd_f32 (the forward does
- * not see the frames: it reads the selected loss). */
-int ppea_loss_tail_bwd_n_f32(const float* mask, const uint8_t* src, const float* out, const float* g_rl, const float* g_con,
-                             const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int S, int H,
-                             int W, void* stream);
+                           const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int S, int H,
+                           int W, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A12 / A14  Dense convolutions as implicit GEMMs on the matrix cores (csrc/conv_nhwc.hip, conv_wgrad.hip):

@@ -2,150 +2,93 @@
 //   A18+A19  BackprojectDepth -> Project3D fused        (layers.py:138-199)
 //   A18, A19 the same two modules as one launch each, for callers that keep them apart or need the points
 //   A20      F.grid_sample bilinear, align_corners=True  (trainer.py:911-914, rkm.py:299)
+//   A15      axis-angle + translation -> 4x4, and the relative-pose chains built from it
 // All HBM-bound streaming kernels: one thread per output pixel, coalesced NCHW rows,
 // no intermediate [B,4,HW] point cloud (the reference writes ~5 MB/img for 1.5 MB
 // of algorithmic traffic; here depth is read once and the grid written once).
+//
+// The projection arithmetic is written ONCE, in four device functions (load_rows, backproject_pixel, project_point,
+// project_point_bwd); the six kernels of the fused and the split form are loads, one or two calls and stores.  The fused
+// kernels pass the literal Xh[3] = 1.f: p * 1.f and dc * 1.f are exact and fold away, so where row 3 of the points is 1
+// the split form carries the fused form's bits.  That, and the recorded bits of tests/golden/geometry_bits.npz, hold only
+// while the expression trees below stay as written: the parentheses, the order of the k sums, division in the forward
+// and reciprocal-multiply in the backward, -ffp-contract=off.  One silent change of association moves the pose gradient
+// and, a few optimizer steps later, the whole pose branch.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
 
-struct Cam {            // per-batch matrices broadcast through SGPRs
-    float ik[9];        // inv_K[:3,:3]
-    float p[12];        // P = (K @ T)[:3,:4]
-};
-
-__device__ __forceinline__ Cam load_cam(const float* __restrict__ inv_K, const float* __restrict__ P, int b) {
-    Cam c;
+// Rows 0-2, columns 0 .. COLS-1 of item b of a batch of row-major matrices with 4 columns, `stride` floats per item: 16 for
+// [B,4,4] (inv_K; K @ T, whose `[:, :3, :]` is read in place without a copy), 12 for P [B,3,4].  Broadcast through SGPRs.
+template <int COLS>
+__device__ __forceinline__ void load_rows(const float* __restrict__ m, int stride, int b, float (&o)[3 * COLS]) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) c.ik[i * 3 + j] = inv_K[b * 16 + i * 4 + j];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) c.p[i] = P[b * 12 + i];
-    return c;
+        for (int j = 0; j < COLS; ++j) o[i * COLS + j] = m[b * stride + i * 4 + j];
 }
 
 // ray = inv_K[:3,:3] @ (x, y, 1) with the reference's matmul association (k = 0,1,2).
-__device__ __forceinline__ void pixel_ray(const Cam& c, float x, float y, float (&r)[3]) {
+__device__ __forceinline__ void pixel_ray(const float (&ik)[9], float x, float y, float (&r)[3]) {
 #pragma unroll
-    for (int i = 0; i < 3; ++i) r[i] = (c.ik[i * 3] * x + c.ik[i * 3 + 1] * y) + c.ik[i * 3 + 2];
+    for (int i = 0; i < 3; ++i) r[i] = (ik[i * 3] * x + ik[i * 3 + 1] * y) + ik[i * 3 + 2];
 }
 
-__global__ __launch_bounds__(256) void backproject_project_fwd(const float* __restrict__ depth,
-                                                               const float* __restrict__ inv_K,
-                                                               const float* __restrict__ P,
-                                                               float* __restrict__ grid, int H, int W,
-                                                               float eps) {
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= H * W) return;
-    const Cam c = load_cam(inv_K, P, b);
-    const int py = i / W, px = i - py * W;
-    float r[3];
-    pixel_ray(c, (float)px, (float)py, r);
-    const float d = depth[(long)b * H * W + i];
-    const float X = d * r[0], Y = d * r[1], Z = d * r[2];
-    float cam[3];
+// BackprojectDepth at pixel (px, py): its ray r and the homogeneous point Xh = (depth * r, 1)
+__device__ __forceinline__ void backproject_pixel(const float (&ik)[9], int px, int py, float d, float (&r)[3], float (&Xh)[4]) {
+    pixel_ray(ik, (float)px, (float)py, r);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) Xh[k] = d * r[k];
+    Xh[3] = 1.f;
+}
+
+__device__ __forceinline__ float dot3(const float* a, const float (&r)[3]) { return a[0] * r[0] + a[1] * r[1] + a[2] * r[2]; }
+
+// cam = P @ Xh in the reference's matmul association (k = 0,1,2,3)
+__device__ __forceinline__ void camera_point(const float (&p)[12], const float (&Xh)[4], float (&cam)[3]) {
 #pragma unroll
     for (int k = 0; k < 3; ++k)
-        cam[k] = ((c.p[k * 4] * X + c.p[k * 4 + 1] * Y) + c.p[k * 4 + 2] * Z) + c.p[k * 4 + 3];
+        cam[k] = ((p[k * 4] * Xh[0] + p[k * 4 + 1] * Xh[1]) + p[k * 4 + 2] * Xh[2]) + p[k * 4 + 3] * Xh[3];
+}
+
+// Project3D at one point -> (grid.x, grid.y, cam z); the pixel by DIVISION, as the reference forms it
+__device__ __forceinline__ float3 project_point(const float (&p)[12], const float (&Xh)[4], int H, int W, float eps) {
+    float cam[3];
+    camera_point(p, Xh, cam);
     const float iz = cam[2] + eps;
     float u = cam[0] / iz, v = cam[1] / iz;
     u = u / (float)(W - 1);
     v = v / (float)(H - 1);
-    float2 o;
-    o.x = (u - 0.5f) * 2.f;
-    o.y = (v - 0.5f) * 2.f;
-    reinterpret_cast<float2*>(grid)[(long)b * H * W + i] = o;
+    return make_float3((u - 0.5f) * 2.f, (v - 0.5f) * 2.f, cam[2]);
 }
 
-// d_depth (per pixel) and dP (12 sums per batch item: wave shuffle reduce -> LDS -> one partial per block and entry in
-// `partial` [B][blocks][12]; bp_reduce_dP adds them in a fixed order.  Round 1 added the block sums with float atomics:
-// the pose gradient -- and, after a few optimizer steps, the whole pose branch -- then depended on the order in which
-// the 480 blocks of an image happened to finish).
-__global__ __launch_bounds__(256) void backproject_project_bwd(const float* __restrict__ depth,
-                                                               const float* __restrict__ inv_K,
-                                                               const float* __restrict__ P,
-                                                               const float* __restrict__ d_grid,
-                                                               float* __restrict__ d_depth,
-                                                               float* __restrict__ partial, int H, int W,
-                                                               float eps) {
-    __shared__ float red[4][12];
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const Cam c = load_cam(inv_K, P, b);
-    float g[12];
+// The gradient of project_point at one point, from d grid `dg` and d cam z `*dz` (NULL: none): dc = d cam, dX = P^T dc and
+// the 12 terms g[k * 4 + j] = dc[k] * Xh[j] of dP.  The pixel by RECIPROCAL-MULTIPLY here.
+__device__ __forceinline__ void project_point_bwd(const float (&p)[12], const float (&Xh)[4], float2 dg, const float* __restrict__ dz,
+                                                  int H, int W, float eps, float (&dc)[3], float (&dX)[4], float (&g)[12]) {
+    float cam[3];
+    camera_point(p, Xh, cam);
+    const float iz = 1.f / (cam[2] + eps);
+    const float u = cam[0] * iz, v = cam[1] * iz;
+    const float du = dg.x * 2.f / (float)(W - 1), dv = dg.y * 2.f / (float)(H - 1);
+    dc[0] = du * iz;
+    dc[1] = dv * iz;
+    dc[2] = -(du * u + dv * v) * iz;
+    if (dz != nullptr) dc[2] = dc[2] + *dz;
 #pragma unroll
-    for (int k = 0; k < 12; ++k) g[k] = 0.f;
-    if (i < H * W) {
-        const int py = i / W, px = i - py * W;
-        float r[3];
-        pixel_ray(c, (float)px, (float)py, r);
-        const float d = depth[(long)b * H * W + i];
-        const float Xh[4] = {d * r[0], d * r[1], d * r[2], 1.f};
-        float cam[3];
+    for (int j = 0; j < 4; ++j) dX[j] = p[j] * dc[0] + p[4 + j] * dc[1] + p[8 + j] * dc[2];
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-            cam[k] = ((c.p[k * 4] * Xh[0] + c.p[k * 4 + 1] * Xh[1]) + c.p[k * 4 + 2] * Xh[2]) + c.p[k * 4 + 3];
-        const float iz = 1.f / (cam[2] + eps);
-        const float u = cam[0] * iz, v = cam[1] * iz;
-        const float2 dg = reinterpret_cast<const float2*>(d_grid)[(long)b * H * W + i];
-        const float du = dg.x * 2.f / (float)(W - 1), dv = dg.y * 2.f / (float)(H - 1);
-        const float dc[3] = {du * iz, dv * iz, -(du * u + dv * v) * iz};
-        float dX[3];
+    for (int k = 0; k < 3; ++k)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) dX[j] = c.p[j] * dc[0] + c.p[4 + j] * dc[1] + c.p[8 + j] * dc[2];
-        d_depth[(long)b * H * W + i] = dX[0] * r[0] + dX[1] * r[1] + dX[2] * r[2];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) g[k * 4 + j] = dc[k] * Xh[j];
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        const float s = wave_sum(g[k]);
-        if (lane == 0) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < 12) {
-        const float s = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-        partial[((long)b * gridDim.x + blockIdx.x) * 12 + threadIdx.x] = s;
-    }
+        for (int j = 0; j < 4; ++j) g[k * 4 + j] = dc[k] * Xh[j];
 }
 
-// dP[b][k] = sum over the image's blocks, always in the same order (one wave per batch item, fixed tree)
-__global__ __launch_bounds__(64) void bp_reduce_dP(const float* __restrict__ partial, float* __restrict__ dP, int blocks) {
-    const int b = blockIdx.x, lane = threadIdx.x;
-    float acc[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) acc[k] = 0.f;
-    for (int i = lane; i < blocks; i += 64) {
-        const float* p = partial + ((long)b * blocks + i) * 12;
-#pragma unroll
-        for (int k = 0; k < 12; ++k) acc[k] += p[k];
-    }
-#pragma unroll
-    for (int k = 0; k < 12; ++k) {
-        const float s = wave_sum(acc[k]);
-        if (lane == 0) dP[b * 12 + k] = s;
-    }
-}
-
-// ---- the same geometry split at the point cloud (layers.py:138-199 as two modules) ---------------------------------------
-// BackprojectDepth and Project3D for callers that keep the reference's two-module form or need the [B,4,HW] points / the
-// projected depth themselves.  Same expression shapes as the fused kernels above: where row 3 of the points is 1 the grid,
-// d_depth and dP carry the fused kernels' bits (p * 1.f and dc * 1.f are exact).
-__device__ __forceinline__ Cam load_ik(const float* __restrict__ inv_K, int b) {
-    Cam c;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) c.ik[i * 3 + j] = inv_K[b * 16 + i * 4 + j];
-    return c;
-}
-
-// N per-thread terms -> one partial per block and entry in partial [B][blocks][N] (wave shuffle -> LDS -> fixed tree)
+// N per-thread terms -> one partial per block and entry in partial [B][blocks][N] (wave shuffle -> LDS -> fixed tree);
+// bp_reduce_4x4 adds them in a fixed order.  Round 1 added the block sums with float atomics: the pose gradient -- and, after a
+// few optimizer steps, the whole pose branch -- then depended on the order in which the 480 blocks of an image happened to
+// finish.
 template <int N>
 __device__ __forceinline__ void block_partials(const float (&g)[N], float (&red)[4][N], float* __restrict__ partial, int b) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -161,57 +104,10 @@ __device__ __forceinline__ void block_partials(const float (&g)[N], float (&red)
     }
 }
 
-__global__ __launch_bounds__(256) void backproject_fwd(const float* __restrict__ depth, const float* __restrict__ inv_K,
-                                                       float* __restrict__ points, int H, int W) {
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const long HW = (long)H * W;
-    if (i >= HW) return;
-    const Cam c = load_ik(inv_K, b);
-    const int py = i / W, px = i - py * W;
-    float r[3];
-    pixel_ray(c, (float)px, (float)py, r);
-    const float d = depth[b * HW + i];
-    float* o = points + (long)b * 4 * HW + i;
-    o[0] = d * r[0];
-    o[HW] = d * r[1];
-    o[2 * HW] = d * r[2];
-    o[3 * HW] = 1.f;
-}
-
-// d_depth (NULL: not wanted) = d_points[:3] . ray; partial != NULL: the 9 sums of d inv_K[:3,:3], entry (i, j) = d_points[i] * depth * (x, y, 1)[j]
-__global__ __launch_bounds__(256) void backproject_bwd(const float* __restrict__ depth, const float* __restrict__ inv_K,
-                                                       const float* __restrict__ d_points, float* __restrict__ d_depth,
-                                                       float* __restrict__ partial, int H, int W) {
-    __shared__ float red[4][9];
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    const long HW = (long)H * W;
-    const Cam c = load_ik(inv_K, b);
-    float g[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) g[k] = 0.f;
-    if (i < HW) {
-        const int py = i / W, px = i - py * W;
-        const float xy[3] = {(float)px, (float)py, 1.f};
-        float r[3];
-        pixel_ray(c, xy[0], xy[1], r);
-        const float* dp = d_points + (long)b * 4 * HW + i;
-        const float dX[3] = {dp[0], dp[HW], dp[2 * HW]};
-        if (d_depth != nullptr) d_depth[b * HW + i] = dX[0] * r[0] + dX[1] * r[1] + dX[2] * r[2];
-        if (partial != nullptr) {
-            const float d = depth[b * HW + i];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int j = 0; j < 3; ++j) g[k * 3 + j] = (dX[k] * d) * xy[j];
-        }
-    }
-    if (partial != nullptr) block_partials<9>(g, red, partial, b);      // uniform over the launch
-}
-
-// out [B][4][4]: the R x C sums in the upper-left corner, added in bp_reduce_dP's fixed order, zeros elsewhere
-template <int R, int C>
+// out [B][ROWS][4] (ROWS = 4: a 4x4; 3: the fused form's [B,3,4]): the R x C sums over the image's blocks in the upper-left
+// corner, zeros elsewhere; always in the same order (one wave per batch item: lane-strided over the blocks, then wave_sum,
+// entry by entry).  <3,4,3>: dP [B,3,4]; <3,4,4>: dP [B,4,4]; <3,3,4>: d_inv_K [B,4,4].
+template <int R, int C, int ROWS>
 __global__ __launch_bounds__(64) void bp_reduce_4x4(const float* __restrict__ partial, float* __restrict__ out, int blocks) {
     const int b = blockIdx.x, lane = threadIdx.x;
     float acc[R * C];
@@ -228,7 +124,106 @@ __global__ __launch_bounds__(64) void bp_reduce_4x4(const float* __restrict__ pa
         const float s = wave_sum(acc[k]);
         if (lane == (k / C) * 4 + k % C) v = s;
     }
-    if (lane < 16) out[b * 16 + lane] = v;
+    if (lane < ROWS * 4) out[b * (ROWS * 4) + lane] = v;
+}
+
+// ---- A18+A19 fused: depth -> grid, P [B,3,4] ------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void backproject_project_fwd(const float* __restrict__ depth,
+                                                               const float* __restrict__ inv_K,
+                                                               const float* __restrict__ P,
+                                                               float* __restrict__ grid, int H, int W,
+                                                               float eps) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const long HW = (long)H * W;
+    if (i >= HW) return;
+    float ik[9], p[12];
+    load_rows<3>(inv_K, 16, b, ik);
+    load_rows<4>(P, 12, b, p);
+    const int py = i / W, px = i - py * W;
+    float r[3], Xh[4];
+    backproject_pixel(ik, px, py, depth[b * HW + i], r, Xh);
+    const float3 o = project_point(p, Xh, H, W, eps);
+    reinterpret_cast<float2*>(grid)[b * HW + i] = make_float2(o.x, o.y);
+}
+
+// d_depth (per pixel) and the 12 per-block sums of dP in `partial` [B][blocks][12]
+__global__ __launch_bounds__(256) void backproject_project_bwd(const float* __restrict__ depth,
+                                                               const float* __restrict__ inv_K,
+                                                               const float* __restrict__ P,
+                                                               const float* __restrict__ d_grid,
+                                                               float* __restrict__ d_depth,
+                                                               float* __restrict__ partial, int H, int W,
+                                                               float eps) {
+    __shared__ float red[4][12];
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const long HW = (long)H * W;
+    float ik[9], p[12];
+    load_rows<3>(inv_K, 16, b, ik);
+    load_rows<4>(P, 12, b, p);
+    float g[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) g[k] = 0.f;
+    if (i < HW) {
+        const int py = i / W, px = i - py * W;
+        float r[3], Xh[4], dc[3], dX[4];
+        backproject_pixel(ik, px, py, depth[b * HW + i], r, Xh);
+        project_point_bwd(p, Xh, reinterpret_cast<const float2*>(d_grid)[b * HW + i], nullptr, H, W, eps, dc, dX, g);
+        d_depth[b * HW + i] = dot3(dX, r);
+    }
+    block_partials<12>(g, red, partial, b);
+}
+
+// ---- the same geometry split at the point cloud (layers.py:138-199 as two modules) ---------------------------------------
+// BackprojectDepth and Project3D for callers that keep the reference's two-module form or need the [B,4,HW] points / the
+// projected depth themselves.  P is the [B,4,4] product K @ T.
+__global__ __launch_bounds__(256) void backproject_fwd(const float* __restrict__ depth, const float* __restrict__ inv_K,
+                                                       float* __restrict__ points, int H, int W) {
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const long HW = (long)H * W;
+    if (i >= HW) return;
+    float ik[9];
+    load_rows<3>(inv_K, 16, b, ik);
+    const int py = i / W, px = i - py * W;
+    float r[3], Xh[4];
+    backproject_pixel(ik, px, py, depth[b * HW + i], r, Xh);
+    float* o = points + (long)b * 4 * HW + i;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j * HW] = Xh[j];
+}
+
+// d_depth (NULL: not wanted) = d_points[:3] . ray; partial != NULL: the 9 sums of d inv_K[:3,:3], entry (i, j) = d_points[i] * depth * (x, y, 1)[j]
+__global__ __launch_bounds__(256) void backproject_bwd(const float* __restrict__ depth, const float* __restrict__ inv_K,
+                                                       const float* __restrict__ d_points, float* __restrict__ d_depth,
+                                                       float* __restrict__ partial, int H, int W) {
+    __shared__ float red[4][9];
+    const int b = blockIdx.y;
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const long HW = (long)H * W;
+    float ik[9];
+    load_rows<3>(inv_K, 16, b, ik);
+    float g[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) g[k] = 0.f;
+    if (i < HW) {
+        const int py = i / W, px = i - py * W;
+        const float xy[3] = {(float)px, (float)py, 1.f};
+        float r[3];
+        pixel_ray(ik, xy[0], xy[1], r);
+        const float* dp = d_points + (long)b * 4 * HW + i;
+        const float dX[3] = {dp[0], dp[HW], dp[2 * HW]};
+        if (d_depth != nullptr) d_depth[b * HW + i] = dot3(dX, r);
+        if (partial != nullptr) {
+            const float d = depth[b * HW + i];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int j = 0; j < 3; ++j) g[k * 3 + j] = (dX[k] * d) * xy[j];
+        }
+    }
+    if (partial != nullptr) block_partials<9>(g, red, partial, b);      // uniform over the launch
 }
 
 __global__ __launch_bounds__(256) void project3d_fwd(const float* __restrict__ points, const float* __restrict__ P,
@@ -238,26 +233,14 @@ __global__ __launch_bounds__(256) void project3d_fwd(const float* __restrict__ p
     const long HW = (long)H * W;
     if (i >= HW) return;
     float p[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) p[k] = P[b * 16 + k];
+    load_rows<4>(P, 16, b, p);
     const float* x = points + (long)b * 4 * HW + i;
     const float Xh[4] = {x[0], x[HW], x[2 * HW], x[3 * HW]};
-    float cam[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        cam[k] = ((p[k * 4] * Xh[0] + p[k * 4 + 1] * Xh[1]) + p[k * 4 + 2] * Xh[2]) + p[k * 4 + 3] * Xh[3];
-    const float iz = cam[2] + eps;
-    float u = cam[0] / iz, v = cam[1] / iz;
-    u = u / (float)(W - 1);
-    v = v / (float)(H - 1);
-    float2 o;
-    o.x = (u - 0.5f) * 2.f;
-    o.y = (v - 0.5f) * 2.f;
-    reinterpret_cast<float2*>(grid)[b * HW + i] = o;
-    if (z != nullptr) z[b * HW + i] = cam[2];
+    const float3 o = project_point(p, Xh, H, W, eps);
+    reinterpret_cast<float2*>(grid)[b * HW + i] = make_float2(o.x, o.y);
+    if (z != nullptr) z[b * HW + i] = o.z;
 }
 
-// P: the [B,4,4] product K @ T, rows 0-2 read in place (the reference's `[:, :3, :]` without a copy).
 // d_points [B,4,HW] (NULL: not wanted) and, with partial != NULL, the 12 per-block sums of dP; d_z (NULL: none) is the
 // gradient of the projected depth cam[2]
 __global__ __launch_bounds__(256) void project3d_bwd(const float* __restrict__ points, const float* __restrict__ P,
@@ -269,33 +252,21 @@ __global__ __launch_bounds__(256) void project3d_bwd(const float* __restrict__ p
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     const long HW = (long)H * W;
     float p[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) p[k] = P[b * 16 + k];
+    load_rows<4>(P, 16, b, p);
     float g[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) g[k] = 0.f;
     if (i < HW) {
         const float* x = points + (long)b * 4 * HW + i;
         const float Xh[4] = {x[0], x[HW], x[2 * HW], x[3 * HW]};
-        float cam[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-            cam[k] = ((p[k * 4] * Xh[0] + p[k * 4 + 1] * Xh[1]) + p[k * 4 + 2] * Xh[2]) + p[k * 4 + 3] * Xh[3];
-        const float iz = 1.f / (cam[2] + eps);
-        const float u = cam[0] * iz, v = cam[1] * iz;
-        const float2 dg = reinterpret_cast<const float2*>(d_grid)[b * HW + i];
-        const float du = dg.x * 2.f / (float)(W - 1), dv = dg.y * 2.f / (float)(H - 1);
-        float dc[3] = {du * iz, dv * iz, -(du * u + dv * v) * iz};
-        if (d_z != nullptr) dc[2] = dc[2] + d_z[b * HW + i];
+        float dc[3], dX[4];
+        project_point_bwd(p, Xh, reinterpret_cast<const float2*>(d_grid)[b * HW + i], d_z != nullptr ? d_z + b * HW + i : nullptr,
+                          H, W, eps, dc, dX, g);
         if (d_points != nullptr) {
             float* o = d_points + (long)b * 4 * HW + i;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) o[j * HW] = p[j] * dc[0] + p[4 + j] * dc[1] + p[8 + j] * dc[2];
+            for (int j = 0; j < 4; ++j) o[j * HW] = dX[j];
         }
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) g[k * 4 + j] = dc[k] * Xh[j];
     }
     if (partial != nullptr) block_partials<12>(g, red, partial, b);     // uniform over the launch
 }
@@ -332,7 +303,6 @@ __device__ __forceinline__ float fetch(const float* __restrict__ plane, int x, i
     return (x >= 0 && x < Wi && y >= 0 && y < Hi) ? plane[(long)y * Wi + x] : 0.f;
 }
 
-template <int CMAX>
 __global__ __launch_bounds__(256) void grid_sample_fwd(const float* __restrict__ src,
                                                        const float* __restrict__ grid,
                                                        float* __restrict__ out, int C, int Hi, int Wi,
@@ -459,6 +429,19 @@ struct PoseChain {
     int pair[POSE_CHAIN_MAX], invert[POSE_CHAIN_MAX], pred[POSE_CHAIN_MAX];
 };
 
+// A <- A @ R (A multiplied from the left onto R), 4x4 row-major, each entry summed as in the formula above; both chain
+// kernels multiply through this function
+__device__ __forceinline__ void left_multiply(float (&A)[16], const float (&R)[16]) {
+    float P[16];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            P[4 * i + j] = ((A[4 * i] * R[j] + A[4 * i + 1] * R[4 + j]) + A[4 * i + 2] * R[8 + j]) + A[4 * i + 3] * R[12 + j];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) A[i] = P[i];
+}
+
 template <int F>
 __global__ void pose_chain_fwd(PoseChain c, const float* __restrict__ keep, float* __restrict__ T, int B, int stride) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -471,16 +454,7 @@ __global__ void pose_chain_fwd(PoseChain c, const float* __restrict__ keep, floa
         const bool on = keep == nullptr || keep[b * F + f] != 0.f;
 #pragma unroll
         for (int g = 0; g < F; ++g) {
-            if (g < f && c.pred[f] == g) {
-                float P[16];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int j = 0; j < 4; ++j)
-                        P[4 * i + j] = ((A[4 * i] * R[g][j] + A[4 * i + 1] * R[g][4 + j]) + A[4 * i + 2] * R[g][8 + j]) + A[4 * i + 3] * R[g][12 + j];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) A[i] = P[i];
-            }
+            if (g < f && c.pred[f] == g) left_multiply(A, R[g]);
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -495,7 +469,7 @@ __global__ void pose_chain_fwd(PoseChain c, const float* __restrict__ keep, floa
 // head = state[0] (brought into 0 .. F - 1) the pair (t - j - 1, t - j) is slot (head - j) mod F; `aa_new` / `tr_new`
 // (sample b at + b * stride; NULL: the ring already holds it) is the newest pair (t - 1, t) and is written into slot head
 // first.  T(0 -> -1) = inv(pair 0), T(0 -> -(j + 1)) = inv(pair j) @ T(0 -> -j), each built by pose_matrix_f32 and
-// multiplied in pose_chain_fwd's order.  seen = state[1 + b] frames came before this one: frame j of item b is present iff
+// multiplied by left_multiply.  seen = state[1 + b] frames came before this one: frame j of item b is present iff
 // seen > j; an absent frame is exact zeros (so is everything behind it: seen <= j implies seen <= j + 1) and its slot is
 // never read.  present [B][F] bytes.  One thread per item; a thread touches only its own item's words of the ring.
 template <int F>
@@ -533,16 +507,7 @@ __global__ void pose_chain_ring_fwd(const float* __restrict__ aa_new, const floa
                 for (int k = 0; k < 6; ++k) v[k] = pr[k];
             }
             pose_matrix_f32(v, v + 3, 1, A);
-            if (j > 0) {
-                float P[16];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        P[4 * i + q] = ((A[4 * i] * R[q] + A[4 * i + 1] * R[4 + q]) + A[4 * i + 2] * R[8 + q]) + A[4 * i + 3] * R[12 + q];
-#pragma unroll
-                for (int i = 0; i < 16; ++i) A[i] = P[i];
-            }
+            if (j > 0) left_multiply(A, R);
         }
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -568,93 +533,106 @@ __global__ void pose_matrix_bwd(const float* __restrict__ aa, const float* __res
     for (int k = 0; k < 3; ++k) { daa[3 * b + k] = g[k]; dtr[3 * b + k] = g[3 + k]; }
 }
 
+
+// kernel<F> for F = 1 .. POSE_CHAIN_MAX (checked by the callers): fn receives std::integral_constant<int, F>
+template <typename Fn>
+void with_frames(int F, Fn fn) {
+    switch (F) {
+        case 1: fn(std::integral_constant<int, 1>()); break;
+        case 2: fn(std::integral_constant<int, 2>()); break;
+        case 3: fn(std::integral_constant<int, 3>()); break;
+        default: fn(std::integral_constant<int, 4>()); break;
+    }
+}
+
+// The six projection entry points: B is gridDim.y and a pixel index an int.  min_hw = 2 where the grid is normalised by
+// W - 1 and H - 1, 1 for backproject_*.
+bool dims_ok(int B, int H, int W, int min_hw) {
+    return B >= 0 && B <= 65535 && H >= min_hw && W >= min_hw && (long)H * W <= 0x7fffff00L;
+}
+dim3 pixel_grid(int B, int H, int W) { return dim3((H * W + 255) / 256, B); }
+
+// bytes of the [B][blocks][n] per-block sums of a backward launch
+long partial_bytes(int B, int H, int W, int min_hw, int n) {
+    if (B <= 0 || H < min_hw || W < min_hw) return 0;
+    return (long)B * (((long)H * W + 255) / 256) * n * (long)sizeof(float);
+}
+
 }  // namespace
 
 extern "C" {
 
 int ppea_backproject_project_fwd_f32(const float* depth, const float* inv_K, const float* P, float* grid,
                                      int B, int H, int W, float eps, void* stream) {
-    if (B < 0 || H < 2 || W < 2) return PPEA_ERR_UNSUPPORTED;
+    if (!dims_ok(B, H, W, 2)) return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
-    dim3 g((H * W + 255) / 256, B);
-    hipLaunchKernelGGL(backproject_project_fwd, g, dim3(256), 0, (hipStream_t)stream, depth, inv_K, P, grid,
+    hipLaunchKernelGGL(backproject_project_fwd, pixel_grid(B, H, W), dim3(256), 0, (hipStream_t)stream, depth, inv_K, P, grid,
                        H, W, eps);
     return launch_status();
 }
 
-long ppea_backproject_project_bwd_workspace_bytes(int B, int H, int W) {
-    if (B <= 0 || H < 2 || W < 2) return 0;
-    return (long)B * ((H * W + 255) / 256) * 12 * (long)sizeof(float);
-}
+long ppea_backproject_project_bwd_workspace_bytes(int B, int H, int W) { return partial_bytes(B, H, W, 2, 12); }
 
 int ppea_backproject_project_bwd_f32(const float* depth, const float* inv_K, const float* P,
                                      const float* d_grid, float* d_depth, float* dP, void* workspace, int B, int H,
                                      int W, float eps, void* stream) {
-    if (B < 0 || H < 2 || W < 2) return PPEA_ERR_UNSUPPORTED;
+    if (!dims_ok(B, H, W, 2)) return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
     if (workspace == nullptr) return PPEA_ERR_ARG;
-    dim3 g((H * W + 255) / 256, B);
+    const dim3 g = pixel_grid(B, H, W);
     hipLaunchKernelGGL(backproject_project_bwd, g, dim3(256), 0, (hipStream_t)stream, depth, inv_K, P,
                        d_grid, d_depth, (float*)workspace, H, W, eps);
-    hipLaunchKernelGGL(bp_reduce_dP, dim3(B), dim3(64), 0, (hipStream_t)stream, (const float*)workspace, dP, (int)g.x);
+    hipLaunchKernelGGL((bp_reduce_4x4<3, 4, 3>), dim3(B), dim3(64), 0, (hipStream_t)stream, (const float*)workspace, dP, (int)g.x);
     return launch_status();
 }
 
 // BackprojectDepth / Project3D as separate launches (see backproject_fwd ... project3d_bwd above)
 int ppea_backproject_fwd_f32(const float* depth, const float* inv_K, float* points, int B, int H, int W, void* stream) {
-    if (B < 0 || H < 1 || W < 1 || (long)H * W > 0x7fffff00L || B > 65535) return PPEA_ERR_UNSUPPORTED;   // B is gridDim.y
+    if (!dims_ok(B, H, W, 1)) return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
     if (!depth || !inv_K || !points) return PPEA_ERR_ARG;
-    dim3 g((H * W + 255) / 256, B);
-    hipLaunchKernelGGL(backproject_fwd, g, dim3(256), 0, (hipStream_t)stream, depth, inv_K, points, H, W);
+    hipLaunchKernelGGL(backproject_fwd, pixel_grid(B, H, W), dim3(256), 0, (hipStream_t)stream, depth, inv_K, points, H, W);
     return launch_status();
 }
 
-long ppea_backproject_bwd_workspace_bytes(int B, int H, int W) {
-    if (B <= 0 || H < 1 || W < 1) return 0;
-    return (long)B * (((long)H * W + 255) / 256) * 9 * (long)sizeof(float);
-}
+long ppea_backproject_bwd_workspace_bytes(int B, int H, int W) { return partial_bytes(B, H, W, 1, 9); }
 
 int ppea_backproject_bwd_f32(const float* depth, const float* inv_K, const float* d_points, float* d_depth, float* d_inv_K,
                              void* workspace, int B, int H, int W, void* stream) {
-    if (B < 0 || H < 1 || W < 1 || (long)H * W > 0x7fffff00L || B > 65535) return PPEA_ERR_UNSUPPORTED;   // B is gridDim.y
+    if (!dims_ok(B, H, W, 1)) return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
     if (!depth || !inv_K || !d_points || (d_depth == nullptr && d_inv_K == nullptr) || (d_inv_K != nullptr && workspace == nullptr))
         return PPEA_ERR_ARG;
-    dim3 g((H * W + 255) / 256, B);
+    const dim3 g = pixel_grid(B, H, W);
     float* partial = d_inv_K != nullptr ? (float*)workspace : nullptr;
     hipLaunchKernelGGL(backproject_bwd, g, dim3(256), 0, (hipStream_t)stream, depth, inv_K, d_points, d_depth, partial, H, W);
     if (d_inv_K != nullptr)
-        hipLaunchKernelGGL((bp_reduce_4x4<3, 3>), dim3(B), dim3(64), 0, (hipStream_t)stream, (const float*)partial, d_inv_K, (int)g.x);
+        hipLaunchKernelGGL((bp_reduce_4x4<3, 3, 4>), dim3(B), dim3(64), 0, (hipStream_t)stream, (const float*)partial, d_inv_K, (int)g.x);
     return launch_status();
 }
 
 int ppea_project3d_fwd_f32(const float* points, const float* P, float* grid, float* z, int B, int H, int W, float eps,
                            void* stream) {
-    if (B < 0 || H < 2 || W < 2 || (long)H * W > 0x7fffff00L || B > 65535) return PPEA_ERR_UNSUPPORTED;   // B is gridDim.y
+    if (!dims_ok(B, H, W, 2)) return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
     if (!points || !P || !grid) return PPEA_ERR_ARG;
-    dim3 g((H * W + 255) / 256, B);
-    hipLaunchKernelGGL(project3d_fwd, g, dim3(256), 0, (hipStream_t)stream, points, P, grid, z, H, W, eps);
+    hipLaunchKernelGGL(project3d_fwd, pixel_grid(B, H, W), dim3(256), 0, (hipStream_t)stream, points, P, grid, z, H, W, eps);
     return launch_status();
 }
 
-long ppea_project3d_bwd_workspace_bytes(int B, int H, int W) {
-    if (B <= 0 || H < 2 || W < 2) return 0;
-    return (long)B * (((long)H * W + 255) / 256) * 12 * (long)sizeof(float);
-}
+long ppea_project3d_bwd_workspace_bytes(int B, int H, int W) { return partial_bytes(B, H, W, 2, 12); }
 
 int ppea_project3d_bwd_f32(const float* points, const float* P, const float* d_grid, const float* d_z, float* d_points,
                            float* dP, void* workspace, int B, int H, int W, float eps, void* stream) {
-    if (B < 0 || H < 2 || W < 2 || (long)H * W > 0x7fffff00L || B > 65535) return PPEA_ERR_UNSUPPORTED;   // B is gridDim.y
+    if (!dims_ok(B, H, W, 2)) return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
     if (!points || !P || !d_grid || (d_points == nullptr && dP == nullptr) || (dP != nullptr && workspace == nullptr))
         return PPEA_ERR_ARG;
-    dim3 g((H * W + 255) / 256, B);
+    const dim3 g = pixel_grid(B, H, W);
     float* partial = dP != nullptr ? (float*)workspace : nullptr;
     hipLaunchKernelGGL(project3d_bwd, g, dim3(256), 0, (hipStream_t)stream, points, P, d_grid, d_z, d_points, partial, H, W, eps);
     if (dP != nullptr)
-        hipLaunchKernelGGL((bp_reduce_4x4<3, 4>), dim3(B), dim3(64), 0, (hipStream_t)stream, (const float*)partial, dP, (int)g.x);
+        hipLaunchKernelGGL((bp_reduce_4x4<3, 4, 4>), dim3(B), dim3(64), 0, (hipStream_t)stream, (const float*)partial, dP, (int)g.x);
     return launch_status();
 }
 
@@ -664,7 +642,7 @@ int ppea_grid_sample_fwd_f32(const float* src, const float* grid, float* out, in
         return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
     dim3 g((Ho * Wo + 255) / 256, B);
-    hipLaunchKernelGGL(grid_sample_fwd<0>, g, dim3(256), 0, (hipStream_t)stream, src, grid, out, C, Hi, Wi,
+    hipLaunchKernelGGL(grid_sample_fwd, g, dim3(256), 0, (hipStream_t)stream, src, grid, out, C, Hi, Wi,
                        Ho, Wo, padding);
     return launch_status();
 }
@@ -710,14 +688,10 @@ int ppea_pose_chain_fwd_f32(const float* const* aa, const float* const* tr, int 
     }
     if (B == 0) return 0;
     if (!T) return PPEA_ERR_ARG;
-    const dim3 g((B + 63) / 64), blk(64);
-    hipStream_t s = (hipStream_t)stream;
-    switch (F) {
-        case 1: hipLaunchKernelGGL(pose_chain_fwd<1>, g, blk, 0, s, c, keep, T, B, stride); break;
-        case 2: hipLaunchKernelGGL(pose_chain_fwd<2>, g, blk, 0, s, c, keep, T, B, stride); break;
-        case 3: hipLaunchKernelGGL(pose_chain_fwd<3>, g, blk, 0, s, c, keep, T, B, stride); break;
-        default: hipLaunchKernelGGL(pose_chain_fwd<4>, g, blk, 0, s, c, keep, T, B, stride); break;
-    }
+    with_frames(F, [&](auto f) {
+        hipLaunchKernelGGL(pose_chain_fwd<decltype(f)::value>, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, c, keep, T,
+                           B, stride);
+    });
     return launch_status();
 }
 // The chain of a video stream (see pose_chain_ring_fwd): ring [F][B][2][3] fp32 and state [1 + B] int32 on the device;
@@ -729,14 +703,10 @@ int ppea_pose_chain_ring_fwd_f32(const float* aa_new, const float* tr_new, int s
     if ((aa_new == nullptr) != (tr_new == nullptr) || (aa_new != nullptr && stride < 3)) return PPEA_ERR_ARG;
     if (B == 0) return 0;
     if (!ring || !state || !T || !present) return PPEA_ERR_ARG;
-    const dim3 g((B + 63) / 64), blk(64);
-    hipStream_t s = (hipStream_t)stream;
-    switch (F) {
-        case 1: hipLaunchKernelGGL(pose_chain_ring_fwd<1>, g, blk, 0, s, aa_new, tr_new, stride, ring, state, T, present, B); break;
-        case 2: hipLaunchKernelGGL(pose_chain_ring_fwd<2>, g, blk, 0, s, aa_new, tr_new, stride, ring, state, T, present, B); break;
-        case 3: hipLaunchKernelGGL(pose_chain_ring_fwd<3>, g, blk, 0, s, aa_new, tr_new, stride, ring, state, T, present, B); break;
-        default: hipLaunchKernelGGL(pose_chain_ring_fwd<4>, g, blk, 0, s, aa_new, tr_new, stride, ring, state, T, present, B); break;
-    }
+    with_frames(F, [&](auto f) {
+        hipLaunchKernelGGL(pose_chain_ring_fwd<decltype(f)::value>, dim3((B + 63) / 64), dim3(64), 0, (hipStream_t)stream, aa_new,
+                           tr_new, stride, ring, state, T, present, B);
+    });
     return launch_status();
 }
 int ppea_pose_matrix_bwd_f32(const float* aa, const float* tr, const float* dT, float* daa, float* dtr, int B, int invert,

@@ -444,10 +444,11 @@ int ppea_smooth_bwd_f32(const float* disp, const float* img, float gx, float gy,
     return launch_status();
 }
 
-// S source frames: reproj / identity [B][S][H][W]; warped_0 / warped_1 [B][C][H][W] are read for selec_reproj only (S = 2).
-int ppea_loss_select_n_f32(const float* reproj, const float* identity, const float* warped_0, const float* warped_1,
-                           const float* noise, float* sel, uint8_t* src_idx, int64_t* frame_idx, int64_t* auto_idx,
-                           int B, int S, int C, int H, int W, int selec_reproj, void* stream) {
+// S source frames, S in {1, 2}: reproj / identity [B][S][H][W]; warped_0 / warped_1 [B][C][H][W] are read for selec_reproj
+// only (S = 2).
+int ppea_loss_select_f32(const float* reproj, const float* identity, const float* warped_0, const float* warped_1,
+                         const float* noise, float* sel, uint8_t* src_idx, int64_t* frame_idx, int64_t* auto_idx,
+                         int B, int S, int C, int H, int W, int selec_reproj, void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || (S != 1 && S != 2)) return PPEA_ERR_UNSUPPORTED;
     if (selec_reproj && S == 1) return PPEA_ERR_UNSUPPORTED;        // one frame has no other frame to fall back on
     if (selec_reproj && (C <= 0 || warped_0 == nullptr || warped_1 == nullptr)) return PPEA_ERR_ARG;
@@ -459,18 +460,6 @@ int ppea_loss_select_n_f32(const float* reproj, const float* identity, const flo
     else
         hipLaunchKernelGGL(loss_select<1>, grid, dim3(256), 0, (hipStream_t)stream, reproj, identity, warped_0, warped_1,
                            noise, sel, src_idx, frame_idx, auto_idx, B, C, H, W, 0);
-    return launch_status();
-}
-
-int ppea_loss_select_f32(const float* reproj, const float* identity, const float* warped_m1,
-                         const float* warped_p1, const float* noise, float* sel, uint8_t* src_idx,
-                         int64_t* frame_idx, int64_t* auto_idx, int B, int C, int H, int W, int selec_reproj,
-                         void* stream) {
-    if (B <= 0 || C <= 0 || H <= 0 || W <= 0) return PPEA_ERR_UNSUPPORTED;
-    const long total = (long)B * H * W;
-    hipLaunchKernelGGL(loss_select<2>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       reproj, identity, warped_m1, warped_p1, noise, sel, src_idx, frame_idx, auto_idx, B, C,
-                       H, W, selec_reproj);
     return launch_status();
 }
 
@@ -491,9 +480,9 @@ int ppea_loss_tail_fwd_f32(const float* sel, const int64_t* auto_idx, const floa
     hipLaunchKernelGGL(loss_tail_finalize, dim3(1), dim3(256), 0, (hipStream_t)stream, partial, nblk, total, out);
     return launch_status();
 }
-int ppea_loss_tail_bwd_n_f32(const float* mask, const uint8_t* src, const float* out, const float* g_rl, const float* g_con,
-                             const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int S, int H,
-                             int W, void* stream) {
+int ppea_loss_tail_bwd_f32(const float* mask, const uint8_t* src, const float* out, const float* g_rl, const float* g_con,
+                           const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int S, int H,
+                           int W, void* stream) {
     if (B <= 0 || H <= 0 || W <= 0 || (S != 1 && S != 2)) return PPEA_ERR_UNSUPPORTED;
     const long hw = (long)H * W, total = (long)B * hw;
     const dim3 grid((unsigned)((total + 255) / 256));
@@ -505,10 +494,4 @@ int ppea_loss_tail_bwd_n_f32(const float* mask, const uint8_t* src, const float*
                            mono, d_reproj, d_multi, hw, total);
     return launch_status();
 }
-int ppea_loss_tail_bwd_f32(const float* mask, const uint8_t* src, const float* out, const float* g_rl, const float* g_con,
-                           const float* multi, const float* mono, float* d_reproj, float* d_multi, int B, int H, int W,
-                           void* stream) {
-    return ppea_loss_tail_bwd_n_f32(mask, src, out, g_rl, g_con, multi, mono, d_reproj, d_multi, B, 2, H, W, stream);
-}
-
 }  // extern "C"

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 25
+ABI_VERSION = 26
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -131,8 +131,7 @@ SIGNATURES = {
     "ppea_smooth_num_partials": [],
     "ppea_smooth_fwd_f32": [_vp] * 3 + [_i] * 4 + [_vp],
     "ppea_smooth_bwd_f32": [_vp, _vp, _f, _f, _vp] + [_i] * 4 + [_vp],
-    "ppea_loss_select_f32": [_vp] * 9 + [_i] * 5 + [_vp],
-    "ppea_loss_select_n_f32": [_vp] * 9 + [_i] * 6 + [_vp],
+    "ppea_loss_select_f32": [_vp] * 9 + [_i] * 6 + [_vp],
     "ppea_bn_fwd_channel_f32": [_vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
     "ppea_bn_fwd_channel_bf16": [_vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
     "ppea_bn_fwd_channel_sums_f32": [_vp, _vp, _i, _vp, _vp, _f, _f, _vp, _vp, _vp, _f, _vp, _i, _i, _i, _i, _vp],
@@ -188,8 +187,7 @@ SIGNATURES = {
     "ppea_nhwc_maxpool3x3s2_bwd_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "ppea_loss_tail_blocks": [_l],
     "ppea_loss_tail_fwd_f32": [_vp] * 10 + [_i] * 4 + [_vp],
-    "ppea_loss_tail_bwd_f32": [_vp] * 9 + [_i] * 3 + [_vp],
-    "ppea_loss_tail_bwd_n_f32": [_vp] * 9 + [_i] * 4 + [_vp],
+    "ppea_loss_tail_bwd_f32": [_vp] * 9 + [_i] * 4 + [_vp],
     "ppea_cost_volume_reduce_f32": [_vp] * 6 + [_i] * 4 + [_vp],
     "ppea_cost_volume_multi_fwd_f32": [_vp] * 7 + [_i] * 6 + [_f, _vp],
     "ppea_cost_volume_multi_fwd_bf16": [_vp] * 8 + [_i] * 6 + [_f, _vp],

@@ -297,12 +297,24 @@ def dwconv_lk(x, w_big, w_small=None, want_sums=False):
 # ---------------------------------------------------------------------------------------------
 # A18+A19  BackprojectDepth -> Project3D                         layers.py:138-199
 # ---------------------------------------------------------------------------------------------
+def _device_f32(name, *ts):
+    """fp32 contiguous views of device tensors; a host tensor is refused (no CPU path behind an op)."""
+    for t in ts:
+        if not t.is_cuda:
+            raise PpeaKernelError(f"{name}: PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback)")
+    return [t.contiguous().float() for t in ts]
+
+
+def _bwd_workspace(op, like, H, W):
+    """The per-block partial sums of `ppea_<op>_bwd_f32` for like.shape[0] images of H x W, sized by the library."""
+    nbytes = getattr(_abi.lib, f"ppea_{op}_bwd_workspace_bytes")(like.shape[0], H, W)
+    return torch.empty(nbytes // 4, device=like.device, dtype=_F32)
+
+
 class _BackprojectProject(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth, inv_K, P, eps):
-        depth = depth.contiguous().float()
-        inv_K = inv_K.contiguous().float()
-        P = P.contiguous().float()
+        depth, inv_K, P = _device_f32("backproject_project", depth, inv_K, P)
         B, _, H, W = depth.shape
         grid = torch.empty(B, H, W, 2, device=depth.device, dtype=_F32)
         call("ppea_backproject_project_fwd_f32", ptr(depth), ptr(inv_K), ptr(P), ptr(grid), B, H, W,
@@ -317,7 +329,7 @@ class _BackprojectProject(torch.autograd.Function):
         B, _, H, W = depth.shape
         d_depth = torch.empty_like(depth)
         dP = torch.empty_like(P)
-        ws = torch.empty(_abi.lib.ppea_backproject_project_bwd_workspace_bytes(B, H, W) // 4, device=depth.device, dtype=_F32)
+        ws = _bwd_workspace("backproject_project", depth, H, W)
         call("ppea_backproject_project_bwd_f32", ptr(depth), ptr(inv_K), ptr(P),
              ptr(d_grid.contiguous().float()), ptr(d_depth), ptr(dP), ptr(ws), B, H, W, ctx.eps, stream_ptr())
         return d_depth, None, dP, None
@@ -330,14 +342,6 @@ def backproject_project(depth, inv_K, K, T, eps=1e-7):
 
 
 # The two halves on their own (layers.BackprojectDepth / layers.Project3D): the same arithmetic split at the point cloud.
-def _device_f32(name, *ts):
-    """fp32 contiguous views of device tensors; a host tensor is refused (no CPU path behind an op)."""
-    for t in ts:
-        if not t.is_cuda:
-            raise PpeaKernelError(f"{name}: PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback)")
-    return [t.contiguous().float() for t in ts]
-
-
 def _per_item(m, B):
     """[1,4,4] -> [B,4,4] as the kernels index it (one small copy; autograd sums the gradient back); [B,4,4] as it is."""
     return m if m.shape[0] == B else m.expand(B, 4, 4).contiguous()
@@ -360,7 +364,7 @@ class _Backproject(torch.autograd.Function):
         d_inv_K = ws = None
         if ctx.needs_input_grad[1]:
             d_inv_K = torch.empty_like(inv_K)
-            ws = torch.empty(_abi.lib.ppea_backproject_bwd_workspace_bytes(B, H, W) // 4, device=depth.device, dtype=_F32)
+            ws = _bwd_workspace("backproject", depth, H, W)
         call("ppea_backproject_bwd_f32", ptr(depth), ptr(inv_K), ptr(d_points.contiguous().float()), ptr(d_depth),
              ptr(d_inv_K), ptr(ws), B, H, W, stream_ptr())
         return d_depth, d_inv_K
@@ -406,7 +410,7 @@ class _Project3D(torch.autograd.Function):
         dP = ws = None
         if want_P:
             dP = torch.empty_like(P)
-            ws = torch.empty(_abi.lib.ppea_project3d_bwd_workspace_bytes(B, H, W) // 4, device=points.device, dtype=_F32)
+            ws = _bwd_workspace("project3d", points, H, W)
         call("ppea_project3d_bwd_f32", ptr(points), ptr(P), ptr(d_grid.contiguous().float()), ptr(d_z), ptr(d_points),
              ptr(dP), ptr(ws), B, H, W, eps, stream_ptr())
         return d_points, dP, None, None, None, None
@@ -531,41 +535,7 @@ def smooth_loss(disp, img):
 # A24/A25  per-pixel selection                                     trainer.py:1069-1091
 # ---------------------------------------------------------------------------------------------
 class _LossSelect(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, reproj, identity, warped_m1, warped_p1, noise, selec):
-        reproj = reproj.contiguous().float()
-        B, _, H, W = reproj.shape
-        C = warped_m1.shape[1]
-        dev = reproj.device
-        sel = torch.empty(B, 1, H, W, device=dev, dtype=_F32)
-        src = torch.empty(B, 1, H, W, device=dev, dtype=torch.uint8)
-        fidx = torch.empty(B, 1, H, W, device=dev, dtype=torch.int64)
-        aidx = torch.empty(B, 1, H, W, device=dev, dtype=torch.int64)
-        call("ppea_loss_select_f32", ptr(reproj), ptr(identity.contiguous().float()),
-             ptr(warped_m1.contiguous().float()), ptr(warped_p1.contiguous().float()),
-             ptr(None if noise is None else noise.contiguous().float()), ptr(sel), ptr(src), ptr(fidx),
-             ptr(aidx), B, C, H, W, int(bool(selec)), stream_ptr())
-        ctx.save_for_backward(src)
-        ctx.mark_non_differentiable(src, fidx, aidx)
-        ctx.set_materialize_grads(False)
-        return sel, src, fidx, aidx
-
-    @staticmethod
-    def backward(ctx, d_sel, _a, _b, _c):
-        (src,) = ctx.saved_tensors
-        if d_sel is None:
-            return None, None, None, None, None, None
-        d = torch.cat([d_sel * (src == 0), d_sel * (src == 1)], 1)
-        return d, None, None, None, None, None
-
-
-def loss_select(reproj, identity, warped_m1, warped_p1, noise, selec_reproj=True):
-    """-> (selected reprojection loss [B,1,H,W], source idx u8, frame argmin i64, automask argmin i64)."""
-    return _LossSelect.apply(reproj, identity, warped_m1, warped_p1, noise, selec_reproj)
-
-
-class _LossSelectN(torch.autograd.Function):
-    """`_LossSelect` for S = reproj.shape[1] source frames, S in {1, 2} (ppea_loss_select_n_f32)."""
+    """S = reproj.shape[1] source frames, S in {1, 2} (ppea_loss_select_f32)."""
 
     @staticmethod
     def forward(ctx, reproj, identity, noise, selec, *warped):
@@ -577,7 +547,7 @@ class _LossSelectN(torch.autograd.Function):
         src = torch.empty(B, 1, H, W, device=dev, dtype=torch.uint8)
         fidx = torch.empty(B, 1, H, W, device=dev, dtype=torch.int64)
         aidx = torch.empty(B, 1, H, W, device=dev, dtype=torch.int64)
-        call("ppea_loss_select_n_f32", ptr(reproj), ptr(identity.contiguous().float()),
+        call("ppea_loss_select_f32", ptr(reproj), ptr(identity.contiguous().float()),
              ptr(warped[0] if warped else None), ptr(warped[1] if warped else None),
              ptr(None if noise is None else noise.contiguous().float()), ptr(sel), ptr(src), ptr(fidx),
              ptr(aidx), B, S, warped[0].shape[1] if warped else 0, H, W, int(bool(selec)), stream_ptr())
@@ -596,20 +566,21 @@ class _LossSelectN(torch.autograd.Function):
         return (d,) + (None,) * (len(ctx.needs_input_grad) - 1)
 
 
-def loss_select_n(reproj, identity, warped, noise, selec_reproj=False):
-    """`loss_select` for S = reproj.shape[1] source frames, S in {1, 2}; `identity` [B,S,H,W]; `warped`: the S warped
-    frames, read for `selec_reproj` only, or None.  One frame (frame_ids [0, -1]): the selected loss is that frame's, the
-    source and frame indices are 0, and `selec_reproj` -- which falls back on the OTHER frame -- is refused."""
+def loss_select(reproj, identity, warped, noise, selec_reproj):
+    """-> (selected reprojection loss [B,1,H,W], source idx u8, frame argmin i64, automask argmin i64) for S =
+    reproj.shape[1] source frames, S in {1, 2}; `identity` [B,S,H,W]; `warped`: the S warped frames, read for
+    `selec_reproj` only, or None.  One frame (frame_ids [0, -1]): the selected loss is that frame's, the source and frame
+    indices are 0, and `selec_reproj` -- which falls back on the OTHER frame -- is refused."""
     S = reproj.shape[1]
     if S not in (1, 2) or identity.shape[1] != S:
-        raise ValueError(f"loss_select_n: reproj {tuple(reproj.shape)}, identity {tuple(identity.shape)}: one or two source "
+        raise ValueError(f"loss_select: reproj {tuple(reproj.shape)}, identity {tuple(identity.shape)}: one or two source "
                          "frames, the same in both")
     if selec_reproj and S == 1:
-        raise ValueError("loss_select_n: selec_reproj needs two source frames (train frame_ids [0, -1] with --selec_reproj, "
+        raise ValueError("loss_select: selec_reproj needs two source frames (train frame_ids [0, -1] with --selec_reproj, "
                          "which switches it off)")
     if selec_reproj and (warped is None or len(warped) != S):
-        raise ValueError("loss_select_n: selec_reproj reads the warped frame of every source frame")
-    return _LossSelectN.apply(reproj, identity, noise, selec_reproj, *(warped if selec_reproj else ()))
+        raise ValueError("loss_select: selec_reproj reads the warped frame of every source frame")
+    return _LossSelect.apply(reproj, identity, noise, selec_reproj, *(warped if selec_reproj else ()))
 
 
 class _LossTail(torch.autograd.Function):
@@ -650,7 +621,7 @@ class _LossTail(torch.autograd.Function):
         dev = mask.device
         d_reproj = torch.empty(B, ctx.n_src, H, W, device=dev, dtype=_F32) if ctx.needs_input_grad[0] else None
         d_multi = torch.empty(B, 1, H, W, device=dev, dtype=_F32) if (is_multi and multi_grad and g_cl is not None) else None
-        call("ppea_loss_tail_bwd_n_f32", ptr(mask), ptr(src), ptr(out), ptr(None if g_rl is None else g_rl.contiguous().float()),
+        call("ppea_loss_tail_bwd_f32", ptr(mask), ptr(src), ptr(out), ptr(None if g_rl is None else g_rl.contiguous().float()),
              ptr(None if g_cl is None else g_cl.contiguous().float()), ptr(multi), ptr(mono), ptr(d_reproj), ptr(d_multi),
              B, ctx.n_src, H, W, stream_ptr())
         return d_reproj, None, None, None, None, None, d_multi, None, None
@@ -1972,6 +1943,18 @@ def pose_matrix(axisangle, translation, invert=False):
 POSE_CHAIN_MAX = 4        # csrc/geometry.hip POSE_CHAIN_MAX: lookup frames and pose-network outputs per launch
 
 
+def _pose_rows(ts, B):
+    """Pose-decoder outputs [B,1,3] or [B,3] as the chain kernels read them -> ([B,3] tensors, floats from one item to the
+    next).  Views that are fp32 on the device, dense in their last axis and share one batch stride (slices of the decoder's
+    output) are read in place; anything else is copied to contiguous fp32 [B,3]."""
+    rows = [t.reshape(B, 3) for t in ts]                          # views: [B,1,3] -> [B,3] keeps the batch stride
+    stride = rows[0].stride(0) if B > 1 else 3
+    if all(t.is_cuda and t.dtype == _F32 and t.stride(1) == 1 and (B <= 1 or t.stride(0) == stride) and stride >= 3
+           for t in rows):
+        return rows, stride
+    return [t.float().contiguous() for t in rows], 3
+
+
 @torch.no_grad()
 def pose_chain(pairs, chain, keep=None):
     """Relative poses of the F lookup frames in one launch (repdepth.py:465-507; no gradient, as in the reference).
@@ -1986,14 +1969,8 @@ def pose_chain(pairs, chain, keep=None):
         if not (0 <= p < P and -1 <= pred < f):
             raise PpeaKernelError(f"pose_chain: frame {f} names pair {p} / predecessor {pred}")
     B = pairs[0][0].shape[0]
-    flat = [t.reshape(B, 3) for pr in pairs for t in pr]          # views: [B,1,3] -> [B,3] keeps the batch stride
+    flat, stride = _pose_rows([t for pr in pairs for t in pr], B)
     dev = flat[0].device
-    stride = flat[0].stride(0) if B > 1 else 3
-    in_place = all(t.is_cuda and t.dtype == _F32 and t.stride(1) == 1 and (B <= 1 or t.stride(0) == stride) and stride >= 3
-                   for t in flat)
-    if not in_place:
-        flat = [t.float().contiguous() for t in flat]
-        stride = 3
     for t in flat:
         if not t.is_cuda or t.device != dev:
             raise PpeaKernelError("PPEA-Depth HIP kernels need tensors on a HIP device (no CPU fallback)")
@@ -2024,11 +2001,7 @@ def pose_chain_ring(ring, state, new=None):
     aa = tr = None
     stride = 3
     if new is not None:
-        aa, tr = (t.reshape(B, 3) for t in new)
-        stride = aa.stride(0) if B > 1 else 3
-        if not all(t.is_cuda and t.dtype == _F32 and t.stride(1) == 1 and (B <= 1 or t.stride(0) == stride) and stride >= 3
-                   for t in (aa, tr)):
-            aa, tr, stride = aa.float().contiguous(), tr.float().contiguous(), 3
+        (aa, tr), stride = _pose_rows(new, B)
         if aa.device != ring.device or tr.device != ring.device:
             raise PpeaKernelError("pose_chain_ring: the new pair is on another device")
     T = torch.empty(B, Fr, 4, 4, device=ring.device, dtype=_F32)

@@ -482,13 +482,10 @@ class Trainer:
             noise = None
             if not opt.disable_automasking:
                 noise = rng.randn_like_cpu_order((B, 1, H, W), self.device) * 0.00001
-            if n_src == 2:
-                reprojection_loss, _src, frame_idxs, auto_idx = ops.loss_select(
-                    reprojection_losses, identity_losses, outputs[("color", fids[0], scale)].detach(),
-                    outputs[("color", fids[1], scale)].detach(), noise, opt.selec_reproj)
-            else:           # one source frame: the minimum over the frames is that frame, no warped frame is read
-                reprojection_loss, _src, frame_idxs, auto_idx = ops.loss_select_n(
-                    reprojection_losses, identity_losses, None, noise, False)
+            # the warped frames are read for selec_reproj only; with one source frame the minimum over the frames is that frame
+            warped = [outputs[("color", f, scale)].detach() for f in fids] if opt.selec_reproj else None
+            reprojection_loss, _src, frame_idxs, auto_idx = ops.loss_select(
+                reprojection_losses, identity_losses, warped, noise, opt.selec_reproj)
             outputs[("frame_idxs", scale)] = frame_idxs
             if not opt.disable_automasking:
                 outputs[("automask_idxs", scale)] = auto_idx

@@ -90,7 +90,7 @@ def test_loss_select_one_frame_against_the_torch_composite(device, shape, with_n
     idm = identity.min(1, keepdim=True)[0]
     ref_aidx = torch.argmin(torch.cat([ref_sel, idm if noise is None else idm + noise], 1), dim=1, keepdim=True)
     rd = reproj.clone().to(device).requires_grad_(True)
-    sel, src, fidx, aidx = ops.loss_select_n(rd, identity.to(device), None, None if noise is None else noise.to(device), False)
+    sel, src, fidx, aidx = ops.loss_select(rd, identity.to(device), None, None if noise is None else noise.to(device), False)
     go = torch.randn(b, 1, h, w, generator=_g(11))
     sel.backward(go.to(device))
     assert sel.shape == (b, 1, h, w) and torch.equal(sel.detach().cpu().nan_to_num(nan=-1.0), ref_sel.nan_to_num(nan=-1.0))
@@ -109,12 +109,12 @@ def test_loss_select_one_frame_refuses_selec_reproj(device):
     from ppeadepth import _abi, ops
     r = torch.rand(1, 1, 2, 2, device=device)
     with pytest.raises(ValueError, match="selec_reproj"):
-        ops.loss_select_n(r, r, [r.expand(1, 3, 2, 2)], None, True)
+        ops.loss_select(r, r, [r.expand(1, 3, 2, 2)], None, True)
     out = [torch.zeros(1, 1, 2, 2, device=device, dtype=dt) for dt in (torch.float32, torch.uint8, torch.int64, torch.int64)]
-    rc = _abi.lib.ppea_loss_select_n_f32(_abi.ptr(r), _abi.ptr(r), None, None, None, *[_abi.ptr(t) for t in out],
+    rc = _abi.lib.ppea_loss_select_f32(_abi.ptr(r), _abi.ptr(r), None, None, None, *[_abi.ptr(t) for t in out],
                                          1, 1, 0, 2, 2, 1, _abi.stream_ptr())
     assert rc == -1                                               # PPEA_ERR_UNSUPPORTED, nothing launched
-    assert _abi.lib.ppea_loss_select_n_f32(_abi.ptr(r), _abi.ptr(r), None, None, None, *[_abi.ptr(t) for t in out],
+    assert _abi.lib.ppea_loss_select_f32(_abi.ptr(r), _abi.ptr(r), None, None, None, *[_abi.ptr(t) for t in out],
                                            1, 3, 0, 2, 2, 0, _abi.stream_ptr()) == -1
     torch.cuda.synchronize()
     assert not any(bool(t.any()) for t in out)
@@ -122,36 +122,34 @@ def test_loss_select_one_frame_refuses_selec_reproj(device):
 
 @pytest.mark.parametrize("selec", [True, False], ids=["selec", "plain_min"])
 @pytest.mark.parametrize("nan_layer", [False, True], ids=["finite", "nan"])
-def test_two_frame_call_of_the_new_entry_points_is_the_existing_one_bit_for_bit(device, selec, nan_layer):
-    """ppea_loss_select_n_f32 / ppea_loss_tail_bwd_n_f32 with S = 2 against ppea_loss_select_f32 / ppea_loss_tail_bwd_f32 on
-    the edge cases of test_loss_select_edges (ties, black warps, NaN layer), with and without noise, forward and backward."""
+def test_loss_tail_bwd_routes_the_gradient_by_source_index(device, selec, nan_layer):
+    """ppea_loss_tail_bwd_f32 for S = 1 and S = 2 on the source indices that `ops.loss_select` produces from the edge cases
+    of test_loss_select_edges (ties, black warps, NaN layer; the forward of that selection is asserted there):
+    d_reproj[b, c, p] == (g_rl * mask) * out[2] where src == c, exact zero elsewhere -- pixels with the forced-zero code 2
+    get zero in every channel.  fp32 with the kernel's association, bit for bit."""
     from ppeadepth import _abi, ops
     shape = E.SELECT_SHAPES[-1]
     c = E.select_cases(*shape, E.SELECT_SEEDS[shape], nan_layer=nan_layer)
     b, _, h, w = shape
-    go = torch.randn(b, 1, h, w, generator=_g(11)).to(device)
-    warped = [c["warped_m1"].to(device), c["warped_p1"].to(device)]
-    for noise in (None, c["noise"].to(device)):
-        old_in = c["reproj"].clone().to(device).requires_grad_(True)
-        new_in = c["reproj"].clone().to(device).requires_grad_(True)
-        old = ops.loss_select(old_in, c["identity"].to(device), warped[0], warped[1], noise, selec)
-        new = ops.loss_select_n(new_in, c["identity"].to(device), warped if selec else None, noise, selec)
-        old[0].backward(go)
-        new[0].backward(go)
-        for a, e in zip(new, old):
-            assert a.dtype == e.dtype and torch.equal(a.detach().view(torch.uint8), e.detach().view(torch.uint8))
-        assert torch.equal(new_in.grad, old_in.grad)
-    # the tail's backward: the existing symbol and the S = 2 call of the new one
-    src = old[1]
-    mask = (torch.rand(b, 1, h, w, generator=_g(12)) > 0.3).float().to(device)
-    out = torch.tensor([0.3, 0.1, 1.0 / 37.0], device=device)
-    g_rl = torch.tensor([0.7], device=device)
-    d_old, d_new = torch.full((b, 2, h, w), -1.0, device=device), torch.full((b, 2, h, w), -2.0, device=device)
-    _abi.call("ppea_loss_tail_bwd_f32", _abi.ptr(mask), _abi.ptr(src), _abi.ptr(out), _abi.ptr(g_rl), None, None, None,
-              _abi.ptr(d_old), None, b, h, w, _abi.stream_ptr())
-    _abi.call("ppea_loss_tail_bwd_n_f32", _abi.ptr(mask), _abi.ptr(src), _abi.ptr(out), _abi.ptr(g_rl), None, None, None,
-              _abi.ptr(d_new), None, b, 2, h, w, _abi.stream_ptr())
-    assert torch.equal(d_old, d_new) and bool((d_old != 0).any())
+    warped = [c["warped_m1"].to(device), c["warped_p1"].to(device)] if selec else None
+    src2 = ops.loss_select(c["reproj"].to(device), c["identity"].to(device), warped, c["noise"].to(device), selec)[1].clone()
+    assert bool((src2 == 2).any()) == selec                       # black in both warps: only selec_reproj forces zero
+    src2.view(-1)[5] = 2                                          # planted, so that every case has one
+    assert all(bool((src2 == v).any()) for v in (0, 1, 2))
+    src1 = torch.where(src2 == 1, torch.zeros_like(src2), src2)   # one frame: source 0, or the forced-zero code
+    mask = (torch.rand(b, 1, h, w, generator=_g(12)) > 0.3).float()
+    out = torch.tensor([0.3, 0.1, 1.0 / 37.0])
+    g_rl = torch.tensor([0.7])
+    g = (g_rl * mask) * out[2]
+    assert g.dtype == torch.float32
+    mask_d, out_d, g_rl_d = mask.to(device), out.to(device), g_rl.to(device)
+    for S, src in ((1, src1), (2, src2)):
+        want = torch.cat([torch.where(src.cpu() == ch, g, torch.zeros_like(g)) for ch in range(S)], 1)
+        d = torch.full((b, S, h, w), -1.0, device=device)
+        _abi.call("ppea_loss_tail_bwd_f32", _abi.ptr(mask_d), _abi.ptr(src), _abi.ptr(out_d), _abi.ptr(g_rl_d), None, None, None,
+                  _abi.ptr(d), None, b, S, h, w, _abi.stream_ptr())
+        assert torch.equal(d.cpu(), want) and bool((d != 0).any())
+        assert not d.cpu()[(src.cpu() == 2).expand(b, S, h, w)].any()
 
 
 # ---- 2. loss_tail, one frame ----------------------------------------------------------------------------------------------

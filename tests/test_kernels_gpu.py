@@ -319,8 +319,8 @@ def test_loss_select_indices_bit_exact(device, golden):
     rp = torch.cat([R.reprojection_loss(g["pred_m1"], tgt), R.reprojection_loss(g["pred_p1"], tgt)], 1)
     idl = torch.cat([R.reprojection_loss(g["src_m1"], tgt), R.reprojection_loss(g["src_p1"], tgt)], 1)
     noise = g["mono:noise"] * 0.00001
-    sel, src, fidx, aidx = ops.loss_select(rp.to(device), idl.to(device), g["pred_m1"].to(device),
-                                           g["pred_p1"].to(device), noise.to(device), True)
+    sel, src, fidx, aidx = ops.loss_select(rp.to(device), idl.to(device), [g["pred_m1"].to(device), g["pred_p1"].to(device)],
+                                           noise.to(device), True)
     ref_sel, ref_fidx = R.select_reprojection(rp, g["pred_m1"], g["pred_p1"])
     assert torch.equal(sel.cpu(), ref_sel)
     assert fidx.dtype == torch.int64 and torch.equal(fidx.cpu(), ref_fidx)
@@ -330,7 +330,7 @@ def test_loss_select_indices_bit_exact(device, golden):
     a, b = g["tie_a"], g["tie_b"]
     zeros = torch.ones_like(g["pred_m1"])
     _, _, _, tie = ops.loss_select(torch.cat([a, a], 1).to(device), torch.cat([b, b], 1).to(device),
-                                   zeros.to(device), zeros.to(device), None, True)
+                                   [zeros.to(device), zeros.to(device)], None, True)
     assert torch.equal((tie == 0).float().cpu(), g["tie_mask"])
 
 

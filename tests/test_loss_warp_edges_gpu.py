@@ -131,8 +131,8 @@ def _select_reference(c, selec, noise):
 
 def _run_select(ops, device, c, selec, noise, grad_out=None):
     rd = c["reproj"].clone().to(device).requires_grad_(grad_out is not None)
-    sel, src, fidx, aidx = ops.loss_select(rd, c["identity"].to(device), c["warped_m1"].to(device),
-                                           c["warped_p1"].to(device), None if noise is None else noise.to(device), selec)
+    sel, src, fidx, aidx = ops.loss_select(rd, c["identity"].to(device), [c["warped_m1"].to(device), c["warped_p1"].to(device)],
+                                           None if noise is None else noise.to(device), selec)
     if grad_out is not None:
         sel.backward(grad_out.to(device))
     return sel.detach().cpu(), src.cpu(), fidx.cpu(), aidx.cpu(), (rd.grad.cpu() if grad_out is not None else None)
