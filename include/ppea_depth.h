@@ -200,6 +200,27 @@ int ppea_pwgrad_ex_pair_bf16(const void* const* P, const void* const* Q, void* w
 int ppea_tapsum_fwd_bf16(const void* T, const void* bias, int bias_bf16, void* pre, void* h, int B, int Ch, int H,
                          int W, void* stream);
 int ppea_tapsum_bwd_bf16(const void* g, void* dT, int B, int Ch, int H, int W, void* stream);
+/* Plans of the pointwise GEMM kernels (ABI 27).  Host only, no device call, no stream; each is answered by the function the
+ * launch itself goes by, under the PPEA_PW_TILE / PPEA_PW_V2 / PPEA_PWGRAD_V2 hooks as the launch reads them (per call).
+ *   ppea_pwconv_plan   what ppea_pwconv_bf16, _stats_bf16, _ex_bf16 (a_transposed as given) and _infer_bf16 (which serves
+ *        version 2 only) launch for B, M, K, HW.  plan[8]:
+ *          [0] version  1 pwconv_kernel<BM, ., WN, EPI, a_transposed, BK>, 2 pwconv2_kernel<BM, BK, EPI, a_transposed>
+ *          [1] BM  [2] BK  [3] WN (pixel-waves per workgroup)  [4] [5] [6] grid x, y, z
+ *          [7] P   statistics partials per channel (= ppea_pwconv_stats_partials for a_transposed == 0)
+ *        PPEA_ERR_UNSUPPORTED exactly where those entry points return it for their shape arguments.
+ *   ppea_pwgrad_plan   the split of ppea_pwgrad_bf16 / ppea_pwgrad_ex_bf16.  plan[9]:
+ *          [0] pixel step of pwgrad2_kernel<step> (0: pwgrad_kernel, 64 pixels per step)  [1] steps per image
+ *          [2] total steps  [3] steps per split  [4] S (splits = grid x)  [5] tiles along M  [6] tiles along N
+ *          [7] [8] workspace bytes (= ppea_pwgrad_workspace_bytes): the low 31 bits, the bits above them
+ *   ppea_pwgrad_pair_plan   the same for ppea_pwgrad_ex_pair_bf16 (pwgrad2_pair_kernel<32>): [5] [6] = tiles of problem 0,
+ *        of problem 1;  [7] [8] = ppea_pwgrad_pair_workspace_bytes.  PPEA_ERR_UNSUPPORTED where the pair form is not served. */
+int ppea_pwconv_plan(int B, int M, int K, int HW, int a_transposed, int* plan);
+/* Test support, host only: ppea_pwconv_plan for one B and A mode over M = Mstep * (1..nM) x K = 32 * (1..nK) x
+ * HW = 8 * (1..nHW); out[nM][nK][nHW], one byte per shape: bit 0 version 2, bits 1-2 BM (0: 32, 1: 64, 2: 128), bit 3
+ * BK = 64; 0xff: not served.  summary[2] = shapes served, row-major shapes whose ppea_pwconv_stats_partials is not plan[7]. */
+int ppea_pwconv_plan_sweep(int B, int a_transposed, int Mstep, int nM, int nK, int nHW, unsigned char* out, long* summary);
+int ppea_pwgrad_plan(int B, int M, int N, int HW, int* plan);
+int ppea_pwgrad_pair_plan(int B, const int* M, const int* N, int HW, int* plan);
 
 /* ------------------------------------------------------------------------------------------
  * A2 (+A5/A6 glue)  Training-mode BatchNorm fused with its neighbours (csrc/bn_fused.hip):

@@ -500,16 +500,15 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
 // ppea_pwconv_stats_partials must size that buffer for the kernel that will run.
 struct PwCfg { int v2, bm, bk, wn; };
 
-PwCfg pw_choose(int B, int M, int K, int HW, bool ta) {
+// `force` / `v2env`: the values of PPEA_PW_TILE / PPEA_PW_V2 (pw_choose reads them per call; the plan sweep reads them once).
+PwCfg pw_choose_env(int B, int M, int K, int HW, bool ta, const char* force, const char* v2env) {
     const int nb = (HW + BN - 1) / BN;
     const long blocks128 = (long)nb * ((M + 127) / 128) * B, blocks64 = (long)nb * ((M + 63) / 64) * B;
     PwCfg c;
-    // tuning / test hooks, read per call so that a test can walk the tiles in one process
-    const char* force = getenv("PPEA_PW_TILE");                 // v1 tile: "128", "64", "32" [+ "d" = 64-channel steps]
-    const char* v2env = getenv("PPEA_PW_V2");                   // "0": v1 everywhere; "bm,bk": force a v2 tile
+    const bool v2off = v2env != nullptr && v2env[0] == '0' && v2env[1] == 0;
     if (force != nullptr) {
         c.bm = atoi(force) == 128 ? 128 : (atoi(force) == 64 ? 64 : 32);
-        c.bk = strchr(force, 'd') != nullptr ? 64 : 32;
+        c.bk = (c.bm != 128 && strchr(force, 'd') != nullptr) ? 64 : 32;      // v1 has no 128-row tile with 64-channel steps
     } else {
         c.bm = (M >= 128 && blocks128 >= 512) ? 128 : ((M > 32 && blocks64 >= 256) ? 64 : 32);
         // 64 channels per step only where it pays (measured on v1): long contraction AND too few tiles to hide the
@@ -517,7 +516,7 @@ PwCfg pw_choose(int B, int M, int K, int HW, bool ta) {
         c.bk = (c.bm != 128 && K >= 512) ? 64 : 32;
     }
     c.v2 = 0;
-    if (!ta && !(v2env != nullptr && v2env[0] == '0' && v2env[1] == 0)) {
+    if (!ta && !v2off) {
         // measured per trunk shape (tools/bench_pw4.py, profiles/r03_pwconv_shapes.txt): enough 128-row tiles to fill the
         // chip once -> 128 x 128 tiles with 32-channel steps (48 KB of LDS: three workgroups per CU hide each other's
         // barriers); else 64-row tiles (64-channel steps for long contractions); else 32-row tiles with 64-channel steps
@@ -530,8 +529,36 @@ PwCfg pw_choose(int B, int M, int K, int HW, bool ta) {
         if (bm == 32 && bk == 32) bk = 64;                       // a 32 x 32 A tile is half a piece per wave
         if ((bm == 128 || bm == 64 || bm == 32) && (bk == 64 || bk == 32) && K % bk == 0) { c.v2 = 1; c.bm = bm; c.bk = bk; }
     }
+    if (ta) {
+        // transposed matrix on the LDS-DMA ring: 128-row tiles only (see pwconv2_kernel); PPEA_PW_V2=0 keeps v1
+        static const bool ta_v2 = !(getenv("PPEA_PW_TA_V2") != nullptr && getenv("PPEA_PW_TA_V2")[0] == '0');
+        // ... where they give at least ~128 workgroups: a 128-channel result on 12 x 40 maps is 48 tiles with a long
+        // contraction each, and v1's 32-row tiles (192 workgroups) are faster there (10 against 18 us, tools/bench_pw_ta.py)
+        if (ta_v2 && !v2off && M >= 128 && blocks128 >= 128 && (M % 8) == 0 && (K % 32) == 0) { c.v2 = 1; c.bm = 128; c.bk = 32; }
+    }
     c.wn = c.bm == 32 ? 4 : 2;
     return c;
+}
+
+PwCfg pw_choose(int B, int M, int K, int HW, bool ta) {
+    // tuning / test hooks, read per call so that a test can walk the tiles in one process
+    return pw_choose_env(B, M, K, HW, ta, getenv("PPEA_PW_TILE"),  // v1 tile: "128", "64", "32" [+ "d" = 64-channel steps]
+                         getenv("PPEA_PW_V2"));                    // "0": v1 everywhere; "bm,bk": force a v2 tile
+}
+
+// the shape checks of every entry point of this file (and of ppea_pwconv_plan)
+bool pw_served(int B, int M, int K, int HW, bool ta) {
+    if (B <= 0 || M <= 0 || K <= 0 || HW <= 0 || (K % 32) != 0 || (HW % 8) != 0 || B > 65535) return false;
+    return !(ta && (M % 8) != 0);
+}
+
+// plan[0..7] of ppea_pwconv_plan for a served shape
+void pw_plan_of(const PwCfg& c, int B, int M, int HW, int* plan) {
+    const int nb = (HW + BN - 1) / BN, mt = (M + c.bm - 1) / c.bm;
+    plan[0] = c.v2 ? 2 : 1; plan[1] = c.bm; plan[2] = c.bk; plan[3] = c.wn;
+    if (c.v2) { plan[4] = nb * mt * B; plan[5] = 1; plan[6] = 1; }
+    else { plan[4] = nb; plan[5] = mt; plan[6] = B; }
+    plan[7] = B * nb * c.wn;
 }
 
 template <int BM, int BK, int EPI, bool TA = false>
@@ -557,25 +584,16 @@ template <int EPI, bool TA>
 int launch_pw(const void* A, const void* X, const void* bias, int bias_bf16, const void* aux, void* Y, void* Y2, int B,
               int M, int K, int HW, hipStream_t st) {
     const PwCfg c = pw_choose(B, M, K, HW, TA);
-    if constexpr (!TA) {
-        if (c.v2) {
+    if (c.v2) {
+        if constexpr (TA) {
+            return launch_pw2_t<128, 32, EPI, true>(A, X, bias, bias_bf16, aux, Y, Y2, B, M, K, HW, st);
+        } else {
 #define PW2(BM_, BK_) return launch_pw2_t<BM_, BK_, EPI>(A, X, bias, bias_bf16, aux, Y, Y2, B, M, K, HW, st)
             if (c.bm == 128) { if (c.bk == 64) PW2(128, 64); else PW2(128, 32); }
             if (c.bm == 64) { if (c.bk == 64) PW2(64, 64); else PW2(64, 32); }
             PW2(32, 64);
 #undef PW2
         }
-    }
-    if constexpr (TA) {
-        // transposed matrix on the LDS-DMA ring: 128-row tiles only (see pwconv2_kernel); PPEA_PW_V2=0 keeps v1
-        const char* v2env = getenv("PPEA_PW_V2");
-        static const bool ta_v2 = !(getenv("PPEA_PW_TA_V2") != nullptr && getenv("PPEA_PW_TA_V2")[0] == '0');
-        // ... where they give at least ~128 workgroups: a 128-channel result on 12 x 40 maps is 48 tiles with a long
-        // contraction each, and v1's 32-row tiles (192 workgroups) are faster there (10 against 18 us, tools/bench_pw_ta.py)
-        const long tiles128 = (long)((HW + BN - 1) / BN) * ((M + 127) / 128) * B;
-        if (ta_v2 && !(v2env != nullptr && v2env[0] == '0' && v2env[1] == 0) && M >= 128 && tiles128 >= 128 && (M % 8) == 0 &&
-            (K % 32) == 0)
-            return launch_pw2_t<128, 32, EPI, true>(A, X, bias, bias_bf16, aux, Y, Y2, B, M, K, HW, st);
     }
     const int nb = (HW + BN - 1) / BN;
 #define PW_LAUNCH(BM_, WM_, WN_, BK_)                                                                                 \
@@ -597,24 +615,63 @@ extern "C" {
 // Requirements of the fast path: K % 32 == 0, HW % 8 == 0 (else PPEA_ERR_UNSUPPORTED).
 int ppea_pwconv_bf16(const void* A, const void* X, const float* bias, void* Y, int B, int M, int K, int HW,
                      void* stream) {
-    if (B <= 0 || M <= 0 || K <= 0 || HW <= 0 || (K % 32) != 0 || (HW % 8) != 0 || B > 65535)
-        return PPEA_ERR_UNSUPPORTED;
+    if (!pw_served(B, M, K, HW, false)) return PPEA_ERR_UNSUPPORTED;
     return launch_pw<0, false>(A, X, bias, 0, nullptr, Y, nullptr, B, M, K, HW, (hipStream_t)stream);
 }
 
 // ppea_pwconv_bf16 plus the statistics of the BatchNorm that follows (conv_bn / conv_bn_relu, rka.py:182-197): per output
 // channel the sum and the sum of squares of the stored bf16 values, as P = ppea_pwconv_stats_partials(B, M, K, HW) partial
 // pairs, stats [M][P][2] fp32 (every entry written; reduce with ppea_bn_finalize_sums_f32).
-int ppea_pwconv_stats_partials(int B, int M, int K, int HW) {
+static int stats_partials_env(int B, int M, int K, int HW, const char* force, const char* v2env) {
     if (B <= 0 || M <= 0 || K <= 0 || HW <= 0) return 0;
-    return B * ((HW + BN - 1) / BN) * pw_choose(B, M, K, HW, false).wn;
+    return B * ((HW + BN - 1) / BN) * pw_choose_env(B, M, K, HW, false, force, v2env).wn;
+}
+int ppea_pwconv_stats_partials(int B, int M, int K, int HW) {
+    return stats_partials_env(B, M, K, HW, getenv("PPEA_PW_TILE"), getenv("PPEA_PW_V2"));
 }
 int ppea_pwconv_stats_bf16(const void* A, const void* X, const float* bias, void* Y, float* stats, int B, int M, int K,
                            int HW, void* stream) {
-    if (B <= 0 || M <= 0 || K <= 0 || HW <= 0 || (K % 32) != 0 || (HW % 8) != 0 || B > 65535)
-        return PPEA_ERR_UNSUPPORTED;
+    if (!pw_served(B, M, K, HW, false)) return PPEA_ERR_UNSUPPORTED;
     if (stats == nullptr) return PPEA_ERR_ARG;
     return launch_pw<4, false>(A, X, bias, 0, nullptr, Y, stats, B, M, K, HW, (hipStream_t)stream);
+}
+
+// Host only: what ppea_pwconv_bf16 / _stats_bf16 / _ex_bf16 / _infer_bf16 launch for these arguments, answered by pw_choose
+// (the function launch_pw goes by).  plan[0..7] = version (1: pwconv_kernel, 2: pwconv2_kernel), BM, BK, WN, grid x, y, z,
+// statistics partials P.  PPEA_ERR_UNSUPPORTED exactly where the entry points return it for their shape arguments.
+int ppea_pwconv_plan(int B, int M, int K, int HW, int a_transposed, int* plan) {
+    if (plan == nullptr) return PPEA_ERR_ARG;
+    if (!pw_served(B, M, K, HW, a_transposed != 0)) return PPEA_ERR_UNSUPPORTED;
+    const PwCfg c = pw_choose(B, M, K, HW, a_transposed != 0);
+    if (c.v2 && (long)((HW + BN - 1) / BN) * ((M + c.bm - 1) / c.bm) * B > 0x7fffffffL) return PPEA_ERR_UNSUPPORTED;
+    pw_plan_of(c, B, M, HW, plan);
+    return 0;
+}
+
+// Test support, host only: ppea_pwconv_plan for one B and A mode over M = Mstep * (1..nM) x K = 32 * (1..nK) x
+// HW = 8 * (1..nHW), one byte per shape in out[nM][nK][nHW]: bit 0 v2, bits 1-2 BM (0: 32, 1: 64, 2: 128), bit 3 BK = 64;
+// 0xff: not served.  summary[0] = shapes served, [1] = row-major shapes whose ppea_pwconv_stats_partials differs from
+// plan[7].  The hooks are read once for the whole sweep.
+int ppea_pwconv_plan_sweep(int B, int a_transposed, int Mstep, int nM, int nK, int nHW, unsigned char* out, long* summary) {
+    if (out == nullptr || summary == nullptr || Mstep <= 0) return PPEA_ERR_ARG;
+    const char* force = getenv("PPEA_PW_TILE");
+    const char* v2env = getenv("PPEA_PW_V2");
+    const bool ta = a_transposed != 0;
+    summary[0] = summary[1] = 0;
+    long i = 0;
+    for (int im = 1; im <= nM; ++im)
+        for (int ik = 1; ik <= nK; ++ik)
+            for (int ip = 1; ip <= nHW; ++ip, ++i) {
+                const int M = im * Mstep, K = 32 * ik, HW = 8 * ip;
+                if (!pw_served(B, M, K, HW, ta)) { out[i] = 0xff; continue; }
+                const PwCfg c = pw_choose_env(B, M, K, HW, ta, force, v2env);
+                int plan[8];
+                pw_plan_of(c, B, M, HW, plan);
+                out[i] = (unsigned char)(c.v2 | ((c.bm == 128 ? 2 : (c.bm == 64 ? 1 : 0)) << 1) | ((c.bk == 64) << 3));
+                summary[0]++;
+                if (!ta && stats_partials_env(B, M, K, HW, force, v2env) != plan[7]) summary[1]++;
+            }
+    return 0;
 }
 
 // Same GEMM with an epilogue (adapters, replknet_adapter.py:20-109): epi 0 plain; epi 1 writes the
@@ -622,9 +679,7 @@ int ppea_pwconv_stats_bf16(const void* A, const void* X, const float* bias, void
 // `bias` is fp32 or, with bias_bf16 != 0, bf16.  a_transposed != 0: A is given as At [K][M] (M % 8 == 0).
 int ppea_pwconv_ex_bf16(const void* A, const void* X, const void* bias, int bias_bf16, int epi, const void* aux,
                         void* Y, void* Y2, int B, int M, int K, int HW, int a_transposed, void* stream) {
-    if (B <= 0 || M <= 0 || K <= 0 || HW <= 0 || (K % 32) != 0 || (HW % 8) != 0 || B > 65535)
-        return PPEA_ERR_UNSUPPORTED;
-    if (a_transposed && (M % 8) != 0) return PPEA_ERR_UNSUPPORTED;
+    if (!pw_served(B, M, K, HW, a_transposed != 0)) return PPEA_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     if (epi == 1 && !Y2) return PPEA_ERR_ARG;
     if (epi == 2 && !aux) return PPEA_ERR_ARG;
@@ -654,8 +709,7 @@ int ppea_pwconv_ex_bf16(const void* A, const void* X, const void* bias, int bias
 int ppea_pwconv_infer_bf16(const void* A, const void* X, const float* s, const float* o, int act, const void* r1,
                            const void* r2, float r2_scale, const float* s2, const float* o2, void* Y, void* Y2, int B, int M,
                            int K, int HW, void* stream) {
-    if (B <= 0 || M <= 0 || K <= 0 || HW <= 0 || (K % 32) != 0 || (HW % 8) != 0 || B > 65535)
-        return PPEA_ERR_UNSUPPORTED;
+    if (!pw_served(B, M, K, HW, false)) return PPEA_ERR_UNSUPPORTED;
     if (A == nullptr || X == nullptr || Y == nullptr || act < 0 || act > 2) return PPEA_ERR_ARG;
     if (Y2 != nullptr && (s2 == nullptr || o2 == nullptr)) return PPEA_ERR_ARG;
     const PwCfg c = pw_choose(B, M, K, HW, false);

@@ -500,4 +500,35 @@ int ppea_pwgrad_ex_pair_bf16(const void* const* P, const void* const* Q, void* w
     return launch_status();
 }
 
+// Host only: the split ppea_pwgrad_bf16 / ppea_pwgrad_ex_bf16 launch by, answered by plan() and pwgrad_bk().
+// out[0..8] = pixel step of pwgrad2_kernel (0: pwgrad_kernel), steps per image, total steps, steps per split, S, tiles along
+// M, tiles along N, workspace bytes (low 31 bits, the bits above).  PPEA_ERR_UNSUPPORTED where the entry points return it
+// for their shape arguments.
+int ppea_pwgrad_plan(int B, int M, int N, int HW, int* out) {
+    if (out == nullptr) return PPEA_ERR_ARG;
+    if (B <= 0 || M <= 0 || N <= 0 || HW <= 0 || (HW % 8) != 0) return PPEA_ERR_UNSUPPORTED;
+    int spi, total, sps, S;
+    plan(B, M, N, HW, spi, total, sps, S);
+    const int mt = (M + TM - 1) / TM, nt = (N + TN - 1) / TN;
+    if (mt > 65535 || nt > 65535) return PPEA_ERR_UNSUPPORTED;
+    const long bytes = ppea_pwgrad_workspace_bytes(B, M, N, HW);
+    out[0] = pwgrad_bk(HW); out[1] = spi; out[2] = total; out[3] = sps; out[4] = S; out[5] = mt; out[6] = nt;
+    out[7] = (int)(bytes & 0x7fffffffL); out[8] = (int)(bytes >> 31);
+    return 0;
+}
+
+// The same for ppea_pwgrad_ex_pair_bf16 (pair_plan()): out[5], out[6] = tiles of problem 0 and of problem 1.
+int ppea_pwgrad_pair_plan(int B, const int* M, const int* N, int HW, int* out) {
+    if (out == nullptr || M == nullptr || N == nullptr) return PPEA_ERR_ARG;
+    if (B <= 0 || HW <= 0 || pwgrad_bk(HW) != 32 || M[0] <= 0 || M[1] <= 0 || N[0] <= 0 || N[1] <= 0) return PPEA_ERR_UNSUPPORTED;
+    int tiles, spi, total, sps, S;
+    pair_plan(B, M, N, HW, tiles, spi, total, sps, S);
+    if (tiles > 65535) return PPEA_ERR_UNSUPPORTED;
+    const long bytes = ppea_pwgrad_pair_workspace_bytes(B, M, N, HW);
+    out[0] = 32; out[1] = spi; out[2] = total; out[3] = sps; out[4] = S;
+    out[5] = ((M[0] + TM - 1) / TM) * ((N[0] + TN - 1) / TN); out[6] = tiles - out[5];
+    out[7] = (int)(bytes & 0x7fffffffL); out[8] = (int)(bytes >> 31);
+    return 0;
+}
+
 }  // extern "C"

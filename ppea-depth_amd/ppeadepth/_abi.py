@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 26
+ABI_VERSION = 27
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -173,6 +173,10 @@ SIGNATURES = {
     "ppea_dwconv_lk_fwd_stats_bf16p": [_vp] * 6 + [_i] * 6 + [_vp],
     "ppea_pwconv_stats_partials": [_i] * 4,
     "ppea_pwconv_stats_bf16": [_vp] * 5 + [_i] * 4 + [_vp],
+    "ppea_pwconv_plan": [_i] * 5 + [_vp],
+    "ppea_pwconv_plan_sweep": [_i] * 6 + [_vp, _vp],
+    "ppea_pwgrad_plan": [_i] * 4 + [_vp],
+    "ppea_pwgrad_pair_plan": [_i, _vp, _vp, _i, _vp],
     "ppea_bn_finalize_sums_f32": [_vp, _i, _i, ctypes.c_long, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp],
     "ppea_conv2d_f32_fwd": [_vp] * 6 + [_i] * 9 + [_vp],
     "ppea_conv2d_f32_dgrad": [_vp] * 5 + [_i] * 11 + [_vp],

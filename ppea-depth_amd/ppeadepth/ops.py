@@ -2526,6 +2526,52 @@ def conv_wgrad_plan(N, Cin, Cout, K, stride, Ho, Wo):
     return p
 
 
+PWCONV_PLAN_FIELDS = ("version", "BM", "BK", "WN", "grid_x", "grid_y", "grid_z", "partials")
+PWGRAD_PLAN_FIELDS = ("step", "steps_per_image", "total_steps", "steps_per_split", "S", "tiles_m", "tiles_n")
+
+
+def pwconv_plan(B, M, K, HW, transposed=False):
+    """The kernel ppea_pwconv_bf16 / _stats_bf16 / _ex_bf16 / _infer_bf16 launch for these arguments under the hooks set right
+    now (host only, works without a device): dict of PWCONV_PLAN_FIELDS, or None where the entry points do not serve the shape."""
+    out = (_ct.c_int * 8)()
+    if not try_call("ppea_pwconv_plan", B, M, K, HW, int(transposed), out):
+        return None
+    return dict(zip(PWCONV_PLAN_FIELDS, out))
+
+
+def pwconv_plan_sweep(B, transposed, Mstep, nM, nK, nHW):
+    """pwconv_plan for one B and A mode over M = Mstep * (1..nM) x K = 32 * (1..nK) x HW = 8 * (1..nHW) (host only) ->
+    (uint8 tensor [nM, nK, nHW] of packed plans: bit 0 version 2, bits 1-2 BM (32, 64, 128), bit 3 BK = 64, 255 not served;
+    dict(served, partials_mismatch))."""
+    out = torch.empty(nM, nK, nHW, dtype=torch.uint8)
+    summary = (_ct.c_long * 2)()
+    call("ppea_pwconv_plan_sweep", B, int(transposed), Mstep, nM, nK, nHW, _ct.c_void_p(out.data_ptr()), summary)
+    return out, dict(served=summary[0], partials_mismatch=summary[1])
+
+
+def _pwgrad_plan_dict(out):
+    p = dict(zip(PWGRAD_PLAN_FIELDS, out))
+    p["workspace_bytes"] = out[7] + (out[8] << 31)
+    return p
+
+
+def pwgrad_plan(B, M, N, HW):
+    """The split ppea_pwgrad_bf16 / ppea_pwgrad_ex_bf16 launch by (host only): dict of PWGRAD_PLAN_FIELDS + workspace_bytes;
+    step 0: pwgrad_kernel (64 pixels per step), 32: pwgrad2_kernel<32>.  None where they do not serve the shape."""
+    out = (_ct.c_int * 9)()
+    if not try_call("ppea_pwgrad_plan", B, M, N, HW, out):
+        return None
+    return _pwgrad_plan_dict(out)
+
+
+def pwgrad_pair_plan(B, Ms, Ns, HW):
+    """The same for ppea_pwgrad_ex_pair_bf16 (tiles_m / tiles_n: the tiles of problem 0 / of problem 1); None: not served."""
+    out = (_ct.c_int * 9)()
+    if not try_call("ppea_pwgrad_pair_plan", B, (_ct.c_int * 2)(*Ms), (_ct.c_int * 2)(*Ns), HW, out):
+        return None
+    return _pwgrad_plan_dict(out)
+
+
 DWCONV_LK_PLAN_FIELDS = ("family", "partials", "lds_bytes", "NSEG", "WS", "BN", "BA", "band", "G", "bands", "segs",
                          "items_per_channel", "wpc", "ipw", "fast", "H", "NY", "NTX", "RS", "VEC", "gi", "ngroups", "wgpc", "cpw")
 DWCONV_LK_VARIANTS = ("plain", "stats", "bn", "bias_act")

@@ -10,6 +10,7 @@ import torch
 
 from conftest import rel_err
 
+from oracle import pw_inputs as PW
 from oracle import synth
 
 pytestmark = pytest.mark.gpu
@@ -19,7 +20,7 @@ TOL = 1e-3
 # k x k + 5 x 5 sum re-associate (the bound the issue sets for this comparison; it cannot run on the CPU, where the module
 # path's depthwise and cost-volume operators do not exist, so it is asserted here)
 FOLD_TOL = 1e-4
-PW_TOL = 2 ** -7          # bound of test_pwconv_mfma / test_pwconv_v2_lds_dma_ring_every_tile for the same main loop
+PW_TOL = PW.INFER_TOL     # 2^-7: bound of test_pwconv_mfma / test_pwconv_v2_lds_dma_ring_every_tile for the same main loop
 
 
 def _g(seed):
@@ -59,14 +60,12 @@ def test_pwconv_inference_epilogue_against_fp64(device, B, M, K, H, W):
     for act, use1, use2, want2 in COMBOS:
         ok, y, y2 = _infer(a, x, s, o, act, r1 if use1 else None, r2 if use2 else None, 0.75, s2, o2, want2)
         assert ok and (y2 is not None) == want2, (act, use1, use2, want2)
-        t = v(s) * acc + v(o)
-        t = torch.relu(t) if act == 1 else (torch.nn.functional.gelu(t) if act == 2 else t)
-        ref = t + (r1.double() if use1 else 0) + (0.75 * r2.double() if use2 else 0)
+        # the float64 reference shared with tests/test_pw_arms_gpu.py
+        ref, ref2 = PW.infer_reference(acc, s, o, act, r1 if use1 else None, r2 if use2 else None, 0.75, s2, o2)
         e = float((y.double() - ref).abs().max() / ref.abs().max())
         print(f"[{B},{M},{K},{H}x{W}] act {act} r1 {use1} r2 {use2}: Y {e:.3e}", end="")
         assert e <= PW_TOL, (act, use1, use2, want2, e)
         if want2:
-            ref2 = v(s2) * ref + v(o2)
             e2 = float((y2.double() - ref2).abs().max() / ref2.abs().max())
             print(f" Y2 {e2:.3e}", end="")
             assert e2 <= PW_TOL, (act, use1, use2, e2)
