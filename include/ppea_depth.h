@@ -676,9 +676,12 @@ int ppea_conv_image_wgrad_bf16(const void* dz, const void* x, void* dw, int dw_b
  *      bf16 features (the bf16 step): the kernel is bound by the bytes crossing the L1, so the (1 + F) maps are packed into
  *      channel-PAIR dwords first (`pairs`: caller-owned workspace of (1 + F) * B * C/2 * h * w uint32) and a corner load
  *      serves two channels.  Bit-identical to the fp32 form on the features widened to fp32.  C even.
+ *      Refused before anything is launched or read: F outside 1 .. 4, C <= 0 (bf16: odd C), h or w < 5, D outside
+ *      1 .. 65535, B > 65535 (B is a grid dimension) -> PPEA_ERR_UNSUPPORTED; then B == 0 -> 0; then a NULL cur / lookup /
+ *      pairs / P / inv_K / bins / skip / cost -> PPEA_ERR_ARG (as the ring entries below, where only `skip` may be NULL).
  * A10 cost_volume_reduce (:446-456, :372-387): missing -> per-pixel max; confidence mask;
  *      argmin over bins after 0 -> 100 (int64, first minimum); lowest = 1/bins[argmin];
- *      cost_out = filled cost * confidence.
+ *      cost_out = filled cost * confidence.  B > 65535 (a grid dimension): PPEA_ERR_UNSUPPORTED.
  * ---------------------------------------------------------------------------------------- */
 int ppea_cost_volume_multi_fwd_f32(const float* cur, const float* lookup, const float* P, const float* inv_K,
                                    const float* bins, const int32_t* skip, float* cost, int B, int F, int C, int h, int w,
@@ -695,7 +698,8 @@ int ppea_cost_volume_multi_fwd_bf16(const void* cur, const void* lookup, void* p
  *      channel-pair dwords already (ppea_cv_ring_store_bf16 writes both).
  *      ppea_cv_ring_store_*: src [B,C,h,w] -> slot head of dst [F,B,..] (bf16: packed to channel pairs, C even); state NULL:
  *      dst is a plain [B,..] buffer.
- *      ppea_cv_ring_advance: head <- (head + 1) mod F, seen[b] <- min(seen[b] + 1, F); enqueue after the sweep and the store. */
+ *      ppea_cv_ring_advance: head <- (head + 1) mod F, seen[b] <- min(max(seen[b], 0) + 1, F) for any word (INT_MAX gives F);
+ *      enqueue after the sweep and the store. */
 int ppea_cost_volume_ring_fwd_f32(const float* cur, const float* ring, const int32_t* state, const float* P,
                                   const float* inv_K, const float* bins, const int32_t* skip, float* cost, int B, int F,
                                   int C, int h, int w, int D, float eps, void* stream);

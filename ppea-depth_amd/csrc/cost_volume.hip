@@ -137,7 +137,10 @@ __global__ __launch_bounds__(256) void cost_volume_fwd(const typename CvFeat<PK>
             w00[f][k] = (1.f - tx) * (1.f - ty); w01[f][k] = tx * (1.f - ty); w10[f][k] = (1.f - tx) * ty; w11[f][k] = tx * ty;
             off[f][k] = y0 * w + x0;
             if (!(x0 + 1 < w && y0 + 1 < h)) {
-                // rare: the footprint touches the last column / row.  Corner by corner with zero fill, as grid_sample does
+                // The footprint touches the last column / row: corner by corner with zero fill, as grid_sample does.  Not
+                // reached by finite inputs: xv <= w - 2 and ix >= w - 1 are two roundings of (gx + 1) / 2 * (w - 1) that
+                // differ by a few ulps of w, never by 1 (tests/test_cv_arms_cpu.py counts it over every row and a pose sweep:
+                // 0; DESIGN.md, "Several lookup frames").  Kept: it is what makes the 8-byte loads below safe by construction.
                 const T* lk = fb[f] + off[f][k];
                 double acc = 0.0;
                 for (int c = 0; c < CE; ++c) {
@@ -215,11 +218,12 @@ __global__ __launch_bounds__(256) void cv_ring_store(const void* __restrict__ sr
     }
 }
 
-// thread 0: the head; thread 1 + b: item b's count of frames seen.  Every thread owns its word.
+// thread 0: the head; thread 1 + b: item b's count of frames seen.  Every thread owns its word.  The count is clamped
+// before the increment: a word of INT_MAX must come out as F, not overflow.
 __global__ void cv_ring_advance(int32_t* __restrict__ state, int B, int F) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i > B) return;
-    state[i] = i == 0 ? (ring_head(state, F) + 1) % F : min(max(state[i], 0) + 1, F);
+    state[i] = i == 0 ? (ring_head(state, F) + 1) % F : min(max(state[i], 0), F - 1) + 1;
 }
 
 // Bins per thread for F lookup frames: the F * DB samples of a thread each hold a double sum, an offset and four weights.
@@ -279,9 +283,9 @@ extern "C" {
 int ppea_cost_volume_multi_fwd_f32(const float* cur, const float* lookup, const float* P, const float* inv_K,
                                    const float* bins, const int32_t* skip, float* cost, int B, int F, int C, int h, int w,
                                    int D, float eps, void* stream) {
-    if (B < 0 || F < 1 || F > 4 || C <= 0 || h < 5 || w < 5 || D <= 0 || D > 65535) return PPEA_ERR_UNSUPPORTED;
+    if (B < 0 || B > 65535 || F < 1 || F > 4 || C <= 0 || h < 5 || w < 5 || D <= 0 || D > 65535) return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
-    if (skip == nullptr) return PPEA_ERR_ARG;
+    if (!cur || !lookup || !P || !inv_K || !bins || !skip || !cost) return PPEA_ERR_ARG;
     return cost_volume_launch<false, false>(cur, lookup, P, inv_K, bins, skip, nullptr, cost, B, F, C, h, w, D, eps,
                                             (hipStream_t)stream);
 }
@@ -291,9 +295,10 @@ int ppea_cost_volume_multi_fwd_f32(const float* cur, const float* lookup, const 
 int ppea_cost_volume_multi_fwd_bf16(const void* cur, const void* lookup, void* pairs, const float* P, const float* inv_K,
                                     const float* bins, const int32_t* skip, float* cost, int B, int F, int C, int h, int w,
                                     int D, float eps, void* stream) {
-    if (B < 0 || F < 1 || F > 4 || C <= 0 || (C & 1) || h < 5 || w < 5 || D <= 0 || D > 65535) return PPEA_ERR_UNSUPPORTED;
+    if (B < 0 || B > 65535 || F < 1 || F > 4 || C <= 0 || (C & 1) || h < 5 || w < 5 || D <= 0 || D > 65535)
+        return PPEA_ERR_UNSUPPORTED;
     if (B == 0) return 0;
-    if (pairs == nullptr || skip == nullptr) return PPEA_ERR_ARG;
+    if (!cur || !lookup || !pairs || !P || !inv_K || !bins || !skip || !cost) return PPEA_ERR_ARG;
     const long n = (long)B * (C / 2) * h * w;
     uint32_t* pc = (uint32_t*)pairs;
     hipLaunchKernelGGL(cv_pack_pairs, dim3((unsigned)((n * (1 + F) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
@@ -362,7 +367,7 @@ int ppea_cv_ring_advance(int32_t* state, int B, int F, void* stream) {
 
 int ppea_cost_volume_reduce_f32(const float* cost, const float* bins, float* cost_out, float* confidence,
                                 int64_t* argmin, float* lowest, int B, int D, int h, int w, void* stream) {
-    if (B < 0 || D <= 0 || h <= 0 || w <= 0) return PPEA_ERR_UNSUPPORTED;
+    if (B < 0 || B > 65535 || D <= 0 || h <= 0 || w <= 0) return PPEA_ERR_UNSUPPORTED;      // B is gridDim.y
     if (B == 0) return 0;
     dim3 g((h * w + 255) / 256, B);
     hipLaunchKernelGGL(cost_volume_reduce, g, dim3(256), 0, (hipStream_t)stream, cost, bins, cost_out,
