@@ -785,6 +785,17 @@ int ppea_velodyne_depth_f32(const float* points, const int64_t* point_offsets, i
  *   window once, in 16-byte loads wherever its address allows and byte by byte at the ends, and writes the three channel
  *   rows.  No byte outside the windows is read.
  * ppea_lanczos_v_u8: columns of src [planes][Hin][W] -> dst [planes][Hout][W], planes <= 65535.  One launch.
+ * ppea_lanczos_h_ragged_u8 / ppea_lanczos_v_ragged_u8 (ABI 28): the two passes over N interleaved-RGB (HWC) frames of
+ *   DIFFERENT sizes (KITTI raw has one size per recording day and a training batch mixes them), packed back to back in one
+ *   device buffer of buf_bytes < 2^31 bytes.  desc int32 [N][4] = (byte offset, H, W, size class), H = W = 0 an absent
+ *   frame (a missing neighbour); it is given twice, on the host (desc_host: checked before anything is launched -- an
+ *   extent outside the buffer, H > Hcap, a class >= K, only one of H and W zero: PPEA_ERR_ARG; a row that cannot be staged
+ *   in 60 KiB less 1280 bytes of bookkeeping: PPEA_ERR_UNSUPPORTED) and on the device (desc: what the kernels read; they
+ *   clamp it the same way, so a device copy that differs cannot make them read outside the buffer).  prefix: device int32
+ *   [N + 1], prefix[n] = the rows of the images before n.  taps: device int32 [K][out][2 + kmax], the tables of the K size
+ *   classes, rows zero-padded to the longest.  The horizontal pass writes rows [0, H_n) of dst [N][3][Hcap][Wout] (the
+ *   rest is left as it was); flip / nonzero [N] as above.  The vertical pass reads only those rows and writes the dense
+ *   [N][3][Hout][W]; an absent frame is written as zeros.  One launch each (and the memset of nonzero), N * 3 <= 65535.
  * ppea_color_jitter_u8: img [N][3][H][W] uint8 -> color = img / 255 and color_aug = jitter(img) / 255, both [N][3][H][W]
  *   fp32 (one correctly rounded division, as ToTensor).  params [N][10] int32: the order of the four operations
  *   (0 brightness, 1 contrast, 2 saturation, 3 hue), the brightness / contrast / saturation factors as fp32 bit patterns,
@@ -802,6 +813,11 @@ int ppea_lanczos_h_view_u8(const void* const* srcs, int nsrc, int items_per_src,
                            int32_t* nonzero, uint8_t* dst, int H, int Win, int Wout, void* stream);
 int ppea_lanczos_v_u8(const uint8_t* src, const int32_t* taps, int kmax, uint8_t* dst, long planes, int Hin, int Hout,
                       int W, void* stream);
+int ppea_lanczos_h_ragged_u8(const uint8_t* buf, long buf_bytes, const int32_t* desc_host, const int32_t* desc,
+                             const int32_t* prefix, int N, const int32_t* taps, int K, int kmax, const int32_t* flip,
+                             int32_t* nonzero, uint8_t* dst, int Hcap, int Wout, void* stream);
+int ppea_lanczos_v_ragged_u8(const uint8_t* src, const int32_t* desc_host, const int32_t* desc, int N, const int32_t* taps,
+                             int K, int kmax, uint8_t* dst, int Hcap, int Hout, int W, void* stream);
 long ppea_color_jitter_workspace_bytes(int N, int H, int W);
 int ppea_color_jitter_u8(const uint8_t* img, const int32_t* params, const int32_t* nonzero, void* workspace, float* color,
                          float* color_aug, int N, int H, int W, void* stream);

@@ -10,8 +10,10 @@
 //               images that hold a non-zero byte (a missing neighbour frame is all zeros).  Planar output.
 //   lanczos_h_view3   its specialisation for interleaved RGB (a JPEG decoder's HWC): a row's window staged once in 16-byte
 //               chunks and written as three channel rows.  One host function launches either for both entry points.
+//   lanczos_h_ragged3   the same staging and accumulation (one copy of each: stage_chunk3, resample_pixel3) for frames of
+//               DIFFERENT sizes packed into one buffer: what is uniform there (width, tap table, output row) is per row here.
 //   lanczos_v   the same arithmetic down the columns of the 8-bit intermediate, 4 columns per thread through 32-bit words
-//               when the row length allows.
+//               when the row length allows.  lanczos_v_ragged: per image its own height and its class's table.
 //   jitter_sum  the item's pointwise operations that precede contrast, then Pillow's RGB -> L; an exact integer sum per
 //               2048- or 4096-pixel chunk (no atomics: the partial sums are added again, in order, by every workgroup of
 //               the second launch).
@@ -79,10 +81,47 @@ __device__ __forceinline__ const uint8_t* view_base(const Srcs& srcs, int s) {
     return base;
 }
 
-// Interleaved pixels (pixel stride 3, channel stride 1): rows g = image * H + y.  The row's window, Win * 3 bytes, is
-// staged ONCE, as it lies in memory: 16-byte chunks at the alignment the source has (a window that starts at x0 * 3 is in
-// general not aligned), the partial chunk at either end byte by byte, so no byte outside the window is read.  One thread
-// per output pixel then writes the three channel rows; a flipped image is read mirrored.
+// Interleaved pixels (pixel stride 3, channel stride 1).  A row's window, L = Win * 3 bytes at p, is staged ONCE, as it
+// lies in memory: 16-byte chunks at the alignment the source has (a window that starts at x0 * 3 is in general not
+// aligned), the partial chunk at either end byte by byte, so no byte outside the window is read.  stage_chunk3 is chunk j
+// of that: -> whether it held a non-zero byte.
+__device__ __forceinline__ bool stage_chunk3(const uint8_t* p, int L, int j, uint8_t* row) {
+    const int b0 = j * VIEW_CHUNK - (int)((uintptr_t)p % VIEW_CHUNK);      // the chunk's first byte, window-relative
+    uint8_t* out = row + j * VIEW_CHUNK;
+    bool nz = false;
+    if (b0 >= 0 && b0 + VIEW_CHUNK <= L) {
+        const uint4 v = *(const uint4*)(p + b0);
+        *(uint4*)out = v;
+        nz = (v.x | v.y | v.z | v.w) != 0;
+    } else {
+        for (int q = 0; q < VIEW_CHUNK; ++q) {
+            const int b = b0 + q;
+            if (b >= 0 && b < L) {
+                const uint8_t v = p[b];
+                out[q] = v;
+                nz |= v != 0;
+            }
+        }
+    }
+    return nz;
+}
+
+// One output pixel of a staged row (`row`: where stage_chunk3 put the bytes of p): the three channels written `plane`
+// apart; a flipped image is read mirrored.
+__device__ __forceinline__ void resample_pixel3(const uint8_t* row, const uint8_t* p, const Taps t, int Win, bool flip,
+                                                uint8_t* o, long plane) {
+    const uint8_t* in = row + (int)((uintptr_t)p % VIEW_CHUNK);
+    const int first = flip ? Win - 1 - t.lo : t.lo, step = flip ? -3 : 3;
+    in += first * 3;
+    int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
+    for (int k = 0; k < t.n; ++k, in += step) {
+        const int c = t.c[k];
+        a0 += (int)in[0] * c, a1 += (int)in[1] * c, a2 += (int)in[2] * c;
+    }
+    o[0] = (uint8_t)clip8(a0), o[plane] = (uint8_t)clip8(a1), o[2 * plane] = (uint8_t)clip8(a2);
+}
+
+// Frames of one size: rows g = image * H + y.  One thread per chunk stages, then one thread per output pixel.
 __global__ __launch_bounds__(THREADS) void lanczos_h_view3(Srcs srcs, int items_per_src, long row_stride, long item_stride,
                                                            const int* __restrict__ table, int kmax,
                                                            const int* __restrict__ flip, int* __restrict__ nonzero,
@@ -104,25 +143,7 @@ __global__ __launch_bounds__(THREADS) void lanczos_h_view3(Srcs srcs, int items_
     const int L = Win * 3, chunks = pitch / VIEW_CHUNK;
     for (int i = threadIdx.x; i < nr * chunks; i += THREADS) {
         const int r = i / chunks, j = i - r * chunks;
-        const uint8_t* p = vr.src[r];
-        const int b0 = j * VIEW_CHUNK - (int)((uintptr_t)p % VIEW_CHUNK);      // the chunk's first byte, window-relative
-        uint8_t* out = smem + (size_t)r * pitch + j * VIEW_CHUNK;
-        bool nz = false;
-        if (b0 >= 0 && b0 + VIEW_CHUNK <= L) {
-            const uint4 v = *(const uint4*)(p + b0);
-            *(uint4*)out = v;
-            nz = (v.x | v.y | v.z | v.w) != 0;
-        } else {
-            for (int q = 0; q < VIEW_CHUNK; ++q) {
-                const int b = b0 + q;
-                if (b >= 0 && b < L) {
-                    const uint8_t v = p[b];
-                    out[q] = v;
-                    nz |= v != 0;
-                }
-            }
-        }
-        if (nz) vr.nz[r] = 1;                   // every writer stores the same value
+        if (stage_chunk3(vr.src[r], L, j, smem + (size_t)r * pitch)) vr.nz[r] = 1;      // every writer stores the same value
     }
     __syncthreads();
     if (nonzero && threadIdx.x < nr && vr.nz[threadIdx.x]) {
@@ -132,18 +153,94 @@ __global__ __launch_bounds__(THREADS) void lanczos_h_view3(Srcs srcs, int items_
     const long plane = (long)H * Wout;
     for (int i = threadIdx.x; i < nr * Wout; i += THREADS) {
         const int r = i / Wout, x = i - r * Wout;
-        const Taps t = taps_of(table, kmax, x, Win);
-        const uint8_t* in = smem + (size_t)r * pitch + (int)((uintptr_t)vr.src[r] % VIEW_CHUNK);
-        const int first = vr.flip[r] ? Win - 1 - t.lo : t.lo, step = vr.flip[r] ? -3 : 3;
-        in += first * 3;
-        int a0 = 1 << (PRECISION_BITS - 1), a1 = a0, a2 = a0;
-        for (int k = 0; k < t.n; ++k, in += step) {
-            const int c = t.c[k];
-            a0 += (int)in[0] * c, a1 += (int)in[1] * c, a2 += (int)in[2] * c;
-        }
         const long g = row0 + r, n = g / H;
-        uint8_t* o = dst + (n * 3 * H + (g - n * H)) * Wout + x;
-        o[0] = (uint8_t)clip8(a0), o[plane] = (uint8_t)clip8(a1), o[2 * plane] = (uint8_t)clip8(a2);
+        resample_pixel3(smem + (size_t)r * pitch, vr.src[r], taps_of(table, kmax, x, Win), Win, vr.flip[r] != 0,
+                        dst + (n * 3 * H + (g - n * H)) * Wout + x, plane);
+    }
+}
+
+// Frames of different sizes, packed back to back in ONE buffer (a real KITTI batch mixes the recording days' sizes):
+// desc [N] = (byte offset, H, W, size class), H = W = 0 an absent frame; prefix [N + 1] numbers the rows of all images
+// through, so a workgroup's `rpb` rows may belong to images of different widths and classes.  A row's bookkeeping thread
+// finds its image by binary search in `prefix` (N is a few dozen) and notes, per row, what lanczos_h_view3 has uniform:
+// the width, the offset of the class's table in tables [K][Wout][2 + kmax] and the output row in dst [N][3][Hcap][Wout]
+// (rows >= H are not written).  A row whose descriptor does not lie inside the buffer, the staged pitch or Hcap gets
+// width 0: nothing of it is read or written (the entry point refuses such descriptors before the launch).
+constexpr int RAGGED_META = MAX_RPB * (int)(2 * sizeof(void*) + 6 * sizeof(int));
+
+// desc [n] = (byte offset, H, W, size class); the table need not be 16-byte aligned
+__device__ __forceinline__ int4 desc_of(const int* __restrict__ desc, int n) {
+    const int* d = desc + 4L * n;
+    return make_int4(d[0], d[1], d[2], d[3]);
+}
+
+struct RaggedRows {
+    ViewRows v;
+    long* out;
+    int *win, *tab, *img;
+};
+__device__ __forceinline__ RaggedRows ragged_rows(uint8_t* smem, size_t line_bytes) {
+    RaggedRows r;
+    r.v.src = (const uint8_t**)(smem + line_bytes);         // line_bytes % 16 == 0
+    r.out = (long*)(r.v.src + MAX_RPB);
+    r.v.flip = (int*)(r.out + MAX_RPB);
+    r.v.nz = r.v.flip + MAX_RPB;
+    r.win = r.v.nz + MAX_RPB;
+    r.tab = r.win + MAX_RPB;
+    r.img = r.tab + MAX_RPB;
+    return r;
+}
+
+__global__ __launch_bounds__(THREADS) void lanczos_h_ragged3(const uint8_t* __restrict__ buf, long buf_bytes,
+                                                             const int* __restrict__ desc, const int* __restrict__ prefix,
+                                                             int N, const int* __restrict__ tables, int K, int kmax,
+                                                             const int* __restrict__ flip, int* __restrict__ nonzero,
+                                                             uint8_t* __restrict__ dst, int rows, int Hcap, int Wout,
+                                                             int rpb, int pitch) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];      // [rpb][pitch], then the rows' bookkeeping
+    const RaggedRows rr = ragged_rows(smem, (size_t)rpb * pitch);
+    const int row0 = blockIdx.x * rpb;
+    const int nr = min(rpb, rows - row0);
+    if (threadIdx.x < nr) {
+        const int g = row0 + threadIdx.x;
+        int n = 0, hi = N - 1;                  // the last image that starts at or before row g: an absent one has no rows
+        while (n < hi) {
+            const int mid = (n + hi + 1) >> 1;
+            if (prefix[mid] <= g) n = mid;
+            else hi = mid - 1;
+        }
+        const int4 d = desc_of(desc, n);
+        const int y = g - prefix[n], W = d.z;
+        const bool ok = d.x >= 0 && y >= 0 && y < d.y && d.y <= Hcap && W > 0 && (long)W * 3 + (VIEW_CHUNK - 1) <= pitch &&
+                        d.x + (long)d.y * W * 3 <= buf_bytes;
+        rr.v.src[threadIdx.x] = ok ? buf + d.x + (long)y * W * 3 : buf;
+        rr.out[threadIdx.x] = ((long)n * 3 * Hcap + y) * Wout;
+        rr.v.flip[threadIdx.x] = flip && flip[n] != 0;
+        rr.v.nz[threadIdx.x] = 0;
+        rr.win[threadIdx.x] = ok ? W : 0;
+        rr.tab[threadIdx.x] = min(max(d.w, 0), K - 1) * Wout * (2 + kmax);
+        rr.img[threadIdx.x] = n;
+    }
+    __syncthreads();
+    const int chunks = pitch / VIEW_CHUNK;
+    for (int i = threadIdx.x; i < nr * chunks; i += THREADS) {
+        const int r = i / chunks, j = i - r * chunks;
+        const int L = rr.win[r] * 3;
+        if (j * VIEW_CHUNK >= L + VIEW_CHUNK - 1) continue;             // behind a row narrower than the widest class
+        if (stage_chunk3(rr.v.src[r], L, j, smem + (size_t)r * pitch)) rr.v.nz[r] = 1;
+    }
+    __syncthreads();
+    if (nonzero && threadIdx.x < nr && rr.v.nz[threadIdx.x]) {
+        int* flag = nonzero + rr.img[threadIdx.x];
+        if (__atomic_load_n(flag, __ATOMIC_RELAXED) == 0) atomicOr(flag, 1);
+    }
+    const long plane = (long)Hcap * Wout;
+    for (int i = threadIdx.x; i < nr * Wout; i += THREADS) {
+        const int r = i / Wout, x = i - r * Wout;
+        const int Win = rr.win[r];
+        if (Win == 0) continue;
+        resample_pixel3(smem + (size_t)r * pitch, rr.v.src[r], taps_of(tables + rr.tab[r], kmax, x, Win), Win,
+                        rr.v.flip[r] != 0, dst + rr.out[r] + x, plane);
     }
 }
 
@@ -192,16 +289,9 @@ __global__ __launch_bounds__(THREADS) void lanczos_h_view(Srcs srcs, int items_p
     }
 }
 
-// grid (ceil(Hout * W / VEC / THREADS), planes); VEC = 4 needs W % 4 == 0 (then every row starts on a 32-bit word)
+// VEC output bytes of one row: `in` is the first tap's row at the thread's column, rows W apart
 template <int VEC>
-__global__ __launch_bounds__(THREADS) void lanczos_v(const uint8_t* __restrict__ src, const int* __restrict__ table, int kmax,
-                                                     uint8_t* __restrict__ dst, int Hin, int Hout, int W) {
-    const int Wv = W / VEC;
-    const int i = blockIdx.x * THREADS + threadIdx.x;
-    if (i >= Hout * Wv) return;
-    const int y = i / Wv, x = (i - y * Wv) * VEC;
-    const Taps t = taps_of(table, kmax, y, Hin);
-    const uint8_t* in = src + ((long)blockIdx.y * Hin + t.lo) * W + x;
+__device__ __forceinline__ void resample_column(const uint8_t* in, const Taps t, int W, uint8_t* out) {
     int acc[VEC];
 #pragma unroll
     for (int v = 0; v < VEC; ++v) acc[v] = 1 << (PRECISION_BITS - 1);
@@ -215,7 +305,6 @@ __global__ __launch_bounds__(THREADS) void lanczos_v(const uint8_t* __restrict__
             acc[0] += (int)in[(long)k * W] * c;
         }
     }
-    uint8_t* out = dst + ((long)blockIdx.y * Hout + y) * W + x;
     if (VEC == 4) {
         uint32_t w = 0;
 #pragma unroll
@@ -224,6 +313,35 @@ __global__ __launch_bounds__(THREADS) void lanczos_v(const uint8_t* __restrict__
     } else {
         out[0] = (uint8_t)clip8(acc[0]);
     }
+}
+
+// grid (ceil(Hout * W / VEC / THREADS), planes); VEC = 4 needs W % 4 == 0 (then every row starts on a 32-bit word)
+template <int VEC>
+__global__ __launch_bounds__(THREADS) void lanczos_v(const uint8_t* __restrict__ src, const int* __restrict__ table, int kmax,
+                                                     uint8_t* __restrict__ dst, int Hin, int Hout, int W) {
+    const int Wv = W / VEC;
+    const int i = blockIdx.x * THREADS + threadIdx.x;
+    if (i >= Hout * Wv) return;
+    const int y = i / Wv, x = (i - y * Wv) * VEC;
+    const Taps t = taps_of(table, kmax, y, Hin);
+    resample_column<VEC>(src + ((long)blockIdx.y * Hin + t.lo) * W + x, t, W, dst + ((long)blockIdx.y * Hout + y) * W + x);
+}
+
+// The ragged intermediate [N][3][Hcap][W] -> the dense [N][3][Hout][W]; grid (.., N * 3).  Image n has Hin = H_n rows
+// (the clamp of taps_of keeps every read below H_n: rows at or beyond it were never written) and the vertical table of its
+// class out of tables [K][Hout][2 + kmax]; both are uniform over the workgroup.  An absent image (H_n = 0) has no taps:
+// the accumulator's 1 << 21 clips to the zeros it is written as.
+template <int VEC>
+__global__ __launch_bounds__(THREADS) void lanczos_v_ragged(const uint8_t* __restrict__ src, const int* __restrict__ desc,
+                                                            const int* __restrict__ tables, int K, int kmax,
+                                                            uint8_t* __restrict__ dst, int Hcap, int Hout, int W) {
+    const int Wv = W / VEC;
+    const int i = blockIdx.x * THREADS + threadIdx.x;
+    if (i >= Hout * Wv) return;
+    const int y = i / Wv, x = (i - y * Wv) * VEC;
+    const int4 d = desc_of(desc, blockIdx.y / 3);
+    const Taps t = taps_of(tables + (long)min(max(d.w, 0), K - 1) * Hout * (2 + kmax), kmax, y, min(max(d.y, 0), Hcap));
+    resample_column<VEC>(src + ((long)blockIdx.y * Hcap + t.lo) * W + x, t, W, dst + ((long)blockIdx.y * Hout + y) * W + x);
 }
 
 // ---- ColorJitter ---------------------------------------------------------------------------------------------------
@@ -521,6 +639,79 @@ extern "C" int ppea_lanczos_v_u8(const uint8_t* src, const int32_t* taps, int km
     const dim3 grid((unsigned)((work + THREADS - 1) / THREADS), (unsigned)planes);
     if (vec) lanczos_v<4><<<grid, THREADS, 0, st>>>(src, taps, kmax, dst, Hin, Hout, W);
     else lanczos_v<1><<<grid, THREADS, 0, st>>>(src, taps, kmax, dst, Hin, Hout, W);
+    return launch_status();
+}
+
+// ---- frames of different sizes (KITTI's recording days) through one launch pair --------------------------------------
+// The descriptor as the host holds it, checked before anything is launched: every extent inside the buffer, every class
+// below K, H and W both zero (absent) or both positive.  -> 0, with the row count and the widest image.
+static int check_ragged(const int32_t* desc_host, int N, long buf_bytes, int K, int Hcap, long* rows, int* Wmax) {
+    *rows = 0, *Wmax = 0;
+    for (int n = 0; n < N; ++n) {
+        const int32_t *d = desc_host + 4L * n, off = d[0], H = d[1], W = d[2], k = d[3];
+        if (off < 0 || H < 0 || W < 0 || (H == 0) != (W == 0) || H > Hcap || k < 0 || k >= K) return PPEA_ERR_ARG;
+        if ((long)off + (long)H * W * 3 > buf_bytes) return PPEA_ERR_ARG;
+        *rows += H;
+        *Wmax = W > *Wmax ? W : *Wmax;
+    }
+    return *rows > 0x7fffffffL ? PPEA_ERR_UNSUPPORTED : 0;
+}
+
+// buf: interleaved-RGB (HWC) frames back to back, buf_bytes < 2^31 long; desc_host / desc: the same int32 [N][4] = (byte
+// offset, H, W, size class) on the host (checked here) and on the device (read by the kernel); prefix: device int32
+// [N + 1], prefix[n] = rows of the images before n; taps: device int32 [K][Wout][2 + kmax]; dst [N][3][Hcap][Wout], rows
+// at or beyond H_n not written.  flip / nonzero [N] as ppea_lanczos_h_view_u8's.  One memset and one launch.
+extern "C" int ppea_lanczos_h_ragged_u8(const uint8_t* buf, long buf_bytes, const int32_t* desc_host, const int32_t* desc,
+                                        const int32_t* prefix, int N, const int32_t* taps, int K, int kmax,
+                                        const int32_t* flip, int32_t* nonzero, uint8_t* dst, int Hcap, int Wout,
+                                        void* stream) {
+    if (!buf || !desc_host || !desc || !prefix || !taps || !dst) return PPEA_ERR_ARG;
+    if (buf_bytes <= 0 || N <= 0 || K <= 0 || kmax <= 0 || Hcap <= 0 || Wout <= 0) return PPEA_ERR_ARG;
+    if (buf_bytes > 0x7fffffffL || (long)K * Wout * (2 + kmax) > 0x7fffffffL || (long)N * 3 * Hcap > 0x7fffffffL)
+        return PPEA_ERR_UNSUPPORTED;
+    long rows;
+    int Wmax;
+    const int err = check_ragged(desc_host, N, buf_bytes, K, Hcap, &rows, &Wmax);
+    if (err != 0) return err;
+    // a staged row, as launch_lanczos_h's, sized by the widest image
+    const long pitch = ((long)Wmax * 3 + 2 * (VIEW_CHUNK - 1)) / VIEW_CHUNK * VIEW_CHUNK;
+    if (pitch > LDS_LIMIT - RAGGED_META) return PPEA_ERR_UNSUPPORTED;       // not even one row can be staged
+    hipStream_t st = (hipStream_t)stream;
+    if (nonzero) {
+        hipError_t e = hipMemsetAsync(nonzero, 0, (size_t)N * sizeof(int32_t), st);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (rows == 0) return 0;                    // every frame absent: the vertical pass writes the zeros
+    int rpb = THREADS / Wout;
+    rpb = rpb < 1 ? 1 : (rpb > MAX_RPB ? MAX_RPB : rpb);
+    if (rpb > (LDS_LIMIT - RAGGED_META) / pitch) rpb = (int)((LDS_LIMIT - RAGGED_META) / pitch);
+    const long blocks = (rows + rpb - 1) / rpb;
+    const size_t lds = (size_t)rpb * pitch + RAGGED_META;
+    lanczos_h_ragged3<<<(unsigned)blocks, THREADS, lds, st>>>(buf, buf_bytes, desc, prefix, N, taps, K, kmax, flip,
+                                                             nonzero, dst, (int)rows, Hcap, Wout, rpb, (int)pitch);
+    return launch_status();
+}
+
+// src: the intermediate [N][3][Hcap][W] of ppea_lanczos_h_ragged_u8; taps: device int32 [K][Hout][2 + kmax]; dst: the
+// dense [N][3][Hout][W], an absent image written as zeros.  One launch.
+extern "C" int ppea_lanczos_v_ragged_u8(const uint8_t* src, const int32_t* desc_host, const int32_t* desc, int N,
+                                        const int32_t* taps, int K, int kmax, uint8_t* dst, int Hcap, int Hout, int W,
+                                        void* stream) {
+    if (!src || !desc_host || !desc || !taps || !dst) return PPEA_ERR_ARG;
+    if (N <= 0 || K <= 0 || kmax <= 0 || Hcap <= 0 || Hout <= 0 || W <= 0) return PPEA_ERR_ARG;
+    if ((long)N * 3 > 65535 || (long)Hout * W > 0x7fffffffL || (long)Hcap * W > 0x7fffffffL ||
+        (long)K * Hout * (2 + kmax) > 0x7fffffffL)
+        return PPEA_ERR_UNSUPPORTED;
+    for (int n = 0; n < N; ++n) {
+        const int32_t* d = desc_host + 4L * n;
+        if (d[1] < 0 || d[1] > Hcap || d[3] < 0 || d[3] >= K) return PPEA_ERR_ARG;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    const bool vec = W % 4 == 0 && ((uintptr_t)src | (uintptr_t)dst) % 4 == 0;
+    const long work = (long)Hout * (vec ? W / 4 : W);
+    const dim3 grid((unsigned)((work + THREADS - 1) / THREADS), (unsigned)(N * 3));
+    if (vec) lanczos_v_ragged<4><<<grid, THREADS, 0, st>>>(src, desc, taps, K, kmax, dst, Hcap, Hout, W);
+    else lanczos_v_ragged<1><<<grid, THREADS, 0, st>>>(src, desc, taps, K, kmax, dst, Hcap, Hout, W);
     return launch_status();
 }
 

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 27
+ABI_VERSION = 28
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -208,6 +208,8 @@ SIGNATURES = {
     "ppea_lanczos_h_u8": [_vp, _i, _l, _vp, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp],
     "ppea_lanczos_h_view_u8": [_vp, _i, _i, _i, _l, _l, _l, _l, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _vp],
     "ppea_lanczos_v_u8": [_vp, _vp, _i, _vp, _l, _i, _i, _i, _vp],
+    "ppea_lanczos_h_ragged_u8": [_vp, _l, _vp, _vp, _vp, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp],
+    "ppea_lanczos_v_ragged_u8": [_vp, _vp, _vp, _i, _vp, _i, _i, _vp, _i, _i, _i, _vp],
     "ppea_color_jitter_workspace_bytes": [_i, _i, _i],
     "ppea_color_jitter_u8": [_vp] * 6 + [_i] * 3 + [_vp],
     "ppea_repeat_rows_f32": [_vp, _vp, _i, _i, _i, _vp],

@@ -20,6 +20,8 @@ draw per item shared by all its frames, `ToTensor`, and the per-scale intrinsics
   the level-0 sources of every frame to the colour entries, with or without augmentation.  `DeviceInputPipeline` (KITTI),
   `DDADInputPipeline`, `CityscapesInputPipeline` and `CityscapesEvalPipeline` supply their level-0 sources, whether they
   augment and their intrinsics; the Cityscapes ones read the decoder's HWC frames in place (ops.lanczos_resize_view_u8).
+* `DeviceInputPipeline(None, ...)` takes the frames of a batch at their own sizes (`RaggedFrames`, `pack_frames`,
+  `RaggedLevel0`; ops.lanczos_resize_ragged_u8): what ppeadepth/datasets.py reads from a KITTI folder.
 """
 import math
 
@@ -151,6 +153,148 @@ class LanczosResize:
         if self.in_hw[0] != self.out_hw[0]:
             x = self._clip8(self.mv @ x)
         return x.to(torch.uint8)
+
+
+# ---- frames of different sizes: KITTI raw has one frame size per recording day, and a training batch mixes the days ----
+MAX_RAGGED_BYTES = (1 << 31) - 1                # the descriptor's byte offsets are int32
+
+
+def ragged_layout(hws):
+    """[(H, W) or None per image] -> (desc int32 [N,4] = (byte offset, H, W, size class), sizes, total bytes): the images'
+    HWC bytes back to back; None is an absent image, H = W = 0 (the reference's 100x100 zero dummy for a missing neighbour,
+    mono_dataset.py:161-166); the size class is the index into `sizes`, the distinct (H, W) in order of first sight.
+    Nothing is allocated; a total of 2^31 bytes or more is refused."""
+    desc, sizes, total = np.zeros((len(hws), 4), np.int64), [], 0
+    for n, hw in enumerate(hws):
+        if hw is None:
+            desc[n, 0] = total
+            continue
+        h, w = int(hw[0]), int(hw[1])
+        if h <= 0 or w <= 0:
+            raise ValueError(f"image {n}: size {(h, w)}")
+        if (h, w) not in sizes:
+            sizes.append((h, w))
+        desc[n] = (total, h, w, sizes.index((h, w)))
+        total += h * w * 3
+        if total > MAX_RAGGED_BYTES:
+            raise ValueError(f"the frames of one batch hold 2^31 bytes or more (image {n} ends at byte {total})")
+    return torch.from_numpy(desc.astype(np.int32)), sizes, total
+
+
+class RaggedFrames:
+    """The raw frames of one batch, of any sizes, as the ragged level-0 pass reads them: `buf` ONE host byte buffer with
+    the images' HWC bytes back to back, `desc` int32 [N,4] (`ragged_layout`; the size classes index `sizes`), image
+    n = fi * batch + b (frame-major).  What a DataLoader's collate step hands over (`pack_frames`)."""
+
+    def __init__(self, buf, desc, sizes, batch):
+        self.buf, self.desc, self.sizes, self.batch = buf, desc, list(sizes), batch
+        if desc.shape[0] % batch != 0:
+            raise ValueError(f"{desc.shape[0]} images are no whole number of frames for a batch of {batch}")
+
+    def __len__(self):
+        return self.desc.shape[0]
+
+    def pin_memory(self):                       # what DataLoader(pin_memory=True) calls on a custom batch
+        self.buf = self.buf.pin_memory()
+        return self
+
+    def image(self, n):
+        """Image n as a uint8 [H,W,3] view of the buffer, or None when it is absent."""
+        off, h, w, _ = self.desc[n].tolist()
+        return self.buf[off:off + h * w * 3].view(h, w, 3) if h else None
+
+
+def pack_frames(raw, frame_idxs, pin=None):
+    """raw = {frame id: list of B items}, an item a uint8 [H,W,3] array / tensor as an image decoder returns it, of any size,
+    or None for a missing neighbour -> `RaggedFrames` in the order of frame_idxs.  The collate step of a DataLoader: host
+    work only, so it can run in a worker (pin=False there; pin=None pins the buffer when a GPU is present, so that the one
+    copy of the frame bytes to the device can be asynchronous)."""
+    B = len(raw[frame_idxs[0]])
+    items = []
+    for f in frame_idxs:
+        if len(raw[f]) != B:
+            raise ValueError(f"frame {f}: {len(raw[f])} items in a batch of {B}")
+        items += list(raw[f])
+    for n, it in enumerate(items):
+        if it is not None and (len(it.shape) != 3 or it.shape[2] != 3 or str(it.dtype).split(".")[-1] != "uint8"):
+            raise ValueError(f"image {n}: expected uint8 [H,W,3], got {it.dtype} {tuple(it.shape)}")
+    desc, sizes, total = ragged_layout([None if it is None else it.shape[:2] for it in items])
+    pin = torch.cuda.is_available() if pin is None else pin
+    buf = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=bool(pin))
+    for it, (off, h, w, _) in zip(items, desc.tolist()):
+        if it is not None:
+            t = it if torch.is_tensor(it) else torch.from_numpy(np.ascontiguousarray(it))
+            buf[off:off + h * w * 3].view(h, w, 3).copy_(t)
+    return RaggedFrames(buf, desc, sizes, B)
+
+
+class RaggedLevel0:
+    """Level 0 of a pipeline whose frames differ in size.  Size classes are keyed by (H, W) and kept for the pipeline's
+    life: a class's tables are built on first sight (`resample_matrix` / `compact_taps`; `identity_taps` where a size stays:
+    both passes of the ragged level always run), and on the "hip" backend the device tables [K][out][2 + kmax] are rebuilt
+    and uploaded only then, so a steady-state call uploads no table (`table_uploads`, `table_builds` count them)."""
+
+    def __init__(self, out_hw, device, backend):
+        self.out_hw, self.device, self.backend = tuple(out_hw), device, backend
+        self.classes, self.host = {}, []        # (H, W) -> k; per class what its backend needs
+        self.taps_h = self.taps_v = None
+        self.table_builds = self.table_uploads = 0
+
+    def class_of(self, hw):
+        k = self.classes.get(hw)
+        if k is None:
+            k = self.classes[hw] = len(self.host)
+            (h, w), (ho, wo) = hw, self.out_hw
+            if self.backend == "hip":
+                self.host.append((compact_taps(resample_matrix(w, wo)) if w != wo else identity_taps(w),
+                                  compact_taps(resample_matrix(h, ho)) if h != ho else identity_taps(h)))
+                self.taps_h = None
+            else:
+                self.host.append(LanczosResize(hw, self.out_hw, self.device, "torch"))
+            self.table_builds += 1
+        return k
+
+    def describe(self, frames):
+        """-> the frames' descriptor with THIS pipeline's size classes (host int32 [N,4])."""
+        desc = frames.desc.clone()
+        if frames.sizes:
+            mine = torch.tensor([self.class_of(tuple(hw)) for hw in frames.sizes], dtype=torch.int32)
+            desc[:, 3] = torch.where(desc[:, 1] > 0, mine[desc[:, 3].long()], torch.zeros_like(desc[:, 3]))
+        return desc
+
+    def tables(self):
+        """The device tables of all classes seen so far; at least one class (an all-absent batch reads none of it)."""
+        if not self.host:
+            self.class_of(self.out_hw)
+        if self.taps_h is None:
+            both = []
+            for i in range(2):
+                kmax = max(t[i].shape[1] for t in self.host)
+                both.append(np.stack([np.pad(t[i], ((0, 0), (0, kmax - t[i].shape[1]))) for t in self.host]))
+            self.taps_h, self.taps_v = (torch.from_numpy(t).to(self.device) for t in both)
+            self.table_uploads += 1
+        return self.taps_h, self.taps_v
+
+    def run_hip(self, frames, desc, words, flip, nonzero):
+        from ppeadepth import ops
+        taps_h, taps_v = self.tables()
+        buf = frames.buf.to(self.device, non_blocking=True)         # the call's one copy of frame bytes
+        return ops.lanczos_resize_ragged_u8(buf, (desc, words), self.out_hw, taps_h, taps_v, flip, nonzero)
+
+    def run_torch(self, frames, fi, do_flip):
+        """Frame fi of every item -> (uint8 [B,3,Hout,Wout], blank [B]): per item the `LanczosResize` of its class on the
+        (flipped) frame; an absent frame is zeros; blank = absent, or no non-zero byte."""
+        B, out, blank = frames.batch, [], []
+        for b in range(B):
+            img = frames.image(fi * B + b)
+            blank.append(img is None or not bool(img.any()))
+            if img is None:
+                out.append(torch.zeros((3,) + self.out_hw, dtype=torch.uint8, device=self.device))
+                continue
+            img = img.to(self.device).permute(2, 0, 1)
+            img = img.flip(-1) if bool(do_flip[b]) else img
+            out.append(self.host[self.class_of(tuple(img.shape[1:]))]._torch(img))
+        return torch.stack(out), torch.tensor(blank, device=self.device)
 
 
 # ---- ColorJitter: torchvision's PIL path, bit for bit, on uint8 batches -------------------------------------------------
@@ -341,11 +485,13 @@ class _PyramidPipeline:
         self.device = torch.device(device)
         self.backend = _backend_of(self.device, backend)
         self.height, self.width, self.num_scales, self.frame_idxs, self.hwc = height, width, num_scales, tuple(frame_idxs), hwc
-        self.resize, prev = [], tuple(src_hw)
+        # src_hw None: the frames differ in size, level 0 is `RaggedLevel0` and the level-0 source a `RaggedFrames`
+        self.ragged = RaggedLevel0((height, width), self.device, self.backend) if src_hw is None else None
+        self.resize, prev = [], None if src_hw is None else tuple(src_hw)
         for s in range(num_scales):
             hw = (height // 2 ** s, width // 2 ** s)
-            self.resize.append(LanczosResize(prev, hw, self.device, self.backend, first=(s == 0),
-                                             filter=level0_filter if s == 0 else "lanczos"))
+            self.resize.append(None if prev is None else LanczosResize(prev, hw, self.device, self.backend, first=(s == 0),
+                                                                       filter=level0_filter if s == 0 else "lanczos"))
             prev = hw
         # ToTensor's divisor as a tensor: a true division on every device (the GPU folds a Python scalar into a multiplication
         # by its reciprocal, which is not the same fp32 value for 126 of the 256 levels)
@@ -366,15 +512,20 @@ class _PyramidPipeline:
 
     def _colors_torch(self, level0, B, aug, kk):
         inputs = {}
-        for f, img in zip(self.frame_idxs, level0):
-            img = img.to(self.device)
-            img = img.permute(0, 3, 1, 2) if self.hwc else img
-            if aug is not None:
+        for fi, f in enumerate(self.frame_idxs):
+            if self.ragged is not None:
                 do_color_aug, do_flip, jitter, generator = aug
-                img = torch.where(do_flip.to(self.device).reshape(-1, 1, 1, 1), img.flip(-1), img)
-                blank = (img.reshape(B, -1).sum(1) == 0)
+                img, blank = self.ragged.run_torch(level0, fi, do_flip)          # level 0, flipped, per item
+            else:
+                img = level0[fi].to(self.device)
+                img = img.permute(0, 3, 1, 2) if self.hwc else img
+                if aug is not None:
+                    do_color_aug, do_flip, jitter, generator = aug
+                    img = torch.where(do_flip.to(self.device).reshape(-1, 1, 1, 1), img.flip(-1), img)
+                    blank = (img.reshape(B, -1).sum(1) == 0)
             for s in range(self.num_scales):
-                img = self.resize[s](img)                               # uint8, chained from the previous scale
+                if s or self.ragged is None:
+                    img = self.resize[s](img)                           # uint8, chained from the previous scale
                 color = inputs[("color", f, s)] = img.to(torch.float32) / self.unit      # ToTensor
                 if aug is None:
                     inputs[("color_aug", f, s)] = color.clone()
@@ -399,9 +550,14 @@ class _PyramidPipeline:
                     raise ValueError("backend 'hip' takes do_color_aug, do_flip and the jitter parameters as host tensors")
             table = pack_jitter_params(by_scale, do_color_aug.repeat(S * F))                  # [S * N, 10]
             host, words = [do_flip.to(torch.int32).repeat(F), table.reshape(-1)], N + table.numel()
+        desc, ragged_words = None, 0
+        if self.ragged is not None:                                 # the frames' descriptor and row prefix ride along
+            desc = self.ragged.describe(level0)
+            host.append(torch.cat([desc.reshape(-1), ops.ragged_row_prefix(desc)]))
+            ragged_words = host[-1].numel()
         if kk is not None:
             host.append(torch.from_numpy(kk).view(torch.int32).reshape(-1))
-        dev = torch.cat(host).to(self.device)                       # the call's one host-to-device copy
+        dev = torch.cat(host).to(self.device)                       # the call's one host-to-device copy of parameters
         if aug is None:
             # no jitter: an all-zero parameter table (apply = 0, written on the device) turns the ColorJitter launch into the
             # uint8 -> fp32 conversion of both outputs
@@ -410,11 +566,14 @@ class _PyramidPipeline:
         else:
             flip, params = dev[:N], dev[N:words].view(S, N, -1)
             nonzero = torch.empty(N, device=self.device, dtype=torch.int32)      # 0: a blank (missing) frame, never jittered
-        level0 = [v.to(self.device) for v in level0]
+        if self.ragged is None:
+            level0 = [v.to(self.device) for v in level0]
         levels = []
         for s in range(S):
             if s > 0:
                 img = self.resize[s](img)
+            elif self.ragged is not None:
+                img = self.ragged.run_hip(level0, desc, dev[words:words + ragged_words], flip, nonzero)
             elif self.hwc:
                 img = self.resize[0].views(level0, flip, nonzero)
             else:
@@ -425,7 +584,7 @@ class _PyramidPipeline:
             for s, (color, jit) in enumerate(levels):
                 inputs[("color", f, s)] = color[fi * B:(fi + 1) * B]
                 inputs[("color_aug", f, s)] = jit[fi * B:(fi + 1) * B]
-        return inputs, None if kk is None else dev[words:].view(torch.float32).view(kk.shape)
+        return inputs, None if kk is None else dev[words + ragged_words:].view(torch.float32).view(kk.shape)
 
 
 class DeviceInputPipeline(_PyramidPipeline):
@@ -433,7 +592,13 @@ class DeviceInputPipeline(_PyramidPipeline):
     in HIP kernels, "torch" (the default on the CPU) in the torch formulation above; both return the same bytes.
 
     A "hip" call is the core's 16 kernels, memset and copy (flip flags and jitter parameters) plus one launch that repeats
-    K / inv_K over the batch: 17 kernels."""
+    K / inv_K over the batch: 17 kernels.
+
+    raw_hw: the one size of all raw frames, or None: every frame has its own size (KITTI raw has one per recording day, and
+    a shuffled batch mixes them) and comes as a decoder returns it (HWC), `None` for a missing neighbour.  Level 0 is then
+    the ragged launch pair (`RaggedLevel0`, ops.lanczos_resize_ragged_u8) on all frames at once, whatever the number of
+    sizes: still 17 kernels; the frames' descriptor rides in the parameter copy and the frame bytes are one more copy.
+    Everything after level 0 is the same code."""
 
     def __init__(self, raw_hw, height, width, device, num_scales=4, frame_idxs=(0, -1, 1), K=KITTI_K, is_train=True,
                  backend=None):
@@ -451,12 +616,20 @@ class DeviceInputPipeline(_PyramidPipeline):
     @torch.no_grad()
     def __call__(self, raw, do_color_aug=None, do_flip=None, jitter=None, generator=None):
         """raw: {frame id: uint8 [B,3,Hraw,Wraw]} (a missing neighbour = all zeros, mono_dataset.py:160-164).
+        With raw_hw=None: {frame id: list of B items}, an item a uint8 [H,W,3] array / tensor of any size or None for a
+        missing neighbour, or those already packed (`pack_frames`, datasets.collate_raw: a `RaggedFrames`).
         do_color_aug / do_flip: [B] bool (default: drawn with p = 0.5 each when is_train, mono_dataset.py:143-144).
         backend "hip": these flags and the jitter parameters are host tensors (as draw_jitter_params returns them); they go
         to the device in one table, and a device tensor is refused rather than copied back."""
-        B = raw[self.frame_idxs[0]].shape[0]
+        if self.ragged is not None:
+            frames = raw if isinstance(raw, RaggedFrames) else pack_frames(raw, self.frame_idxs, pin=self.backend == "hip")
+            if len(frames) != len(self.frame_idxs) * frames.batch:
+                raise ValueError(f"{len(frames)} images for {len(self.frame_idxs)} frames of {frames.batch} items")
+            B, level0 = frames.batch, frames
+        else:
+            B, level0 = raw[self.frame_idxs[0]].shape[0], [raw[f] for f in self.frame_idxs]
         do_color_aug, do_flip = self._draw_flags(B, do_color_aug, do_flip, generator)
-        inputs, _ = self._colors([raw[f] for f in self.frame_idxs], B, (do_color_aug, do_flip, jitter, generator))
+        inputs, _ = self._colors(level0, B, (do_color_aug, do_flip, jitter, generator))
         if self.backend == "hip":
             from ppeadepth import ops
             KK = ops.repeat_rows(self.K_rows.view(-1, 4, 4), B).view(self.num_scales, 2, B, 4, 4)      # one launch

@@ -942,6 +942,75 @@ def lanczos_resize_view_u8(src, out_hw, taps_h, taps_v=None, flip=None, nonzero=
                                                               channel, item, tp, kmax, *rest))
 
 
+def ragged_row_prefix(desc):
+    """Host int32 [N,4] descriptor (byte offset, H, W, size class) -> int32 [N+1]: the rows of the images before n."""
+    prefix = torch.zeros(desc.shape[0] + 1, dtype=torch.int64)
+    prefix[1:] = desc[:, 1].to(torch.int64).cumsum(0)
+    return prefix.to(torch.int32)
+
+
+def _class_taps(table, outsize, what):
+    if table.dim() != 3 or table.shape[0] < 1 or table.shape[1] != outsize or table.shape[2] < 3:
+        raise _abi.PpeaKernelError(f"{what} class tap table {tuple(table.shape)} does not describe {outsize} outputs per class")
+    return ptr(table, torch.int32), table.shape[0], table.shape[2] - 2
+
+
+@torch.no_grad()
+def lanczos_resize_ragged_u8(buf, desc, out_hw, taps_h, taps_v, flip=None, nonzero=None, scratch=None):
+    """`lanczos_resize_view_u8` for N interleaved-RGB (HWC) frames of DIFFERENT sizes in one launch pair -> uint8
+    [N,3,Hout,Wout].  buf: 1-D uint8 device buffer, the frames back to back, fewer than 2^31 bytes.  desc: HOST int32 [N,4]
+    = (byte offset, H, W, size class), H = W = 0 an absent frame (written as zeros, its `nonzero` 0); or the pair (that host
+    tensor, its device copy: int32 [N * 4 + N + 1], the descriptor followed by `ragged_row_prefix`), as a caller has it that
+    uploads the words with its other parameters -- otherwise they are uploaded here.  The host descriptor is checked before
+    anything is launched.  taps_h [K,Wout,2+k] / taps_v [K,Hout,2+k] int32 device tables of the K size classes
+    (input_pipeline.compact_taps rows, zero-padded to the longest; identity_taps where a size stays).  flip / nonzero [N]
+    as in `lanczos_resize_u8`.  scratch: uint8 device tensor of at least N * 3 * max(H) * Wout elements to hold the 8-bit
+    intermediate (rows at or beyond an image's H are neither written nor read); default: allocated here."""
+    host, words = desc if isinstance(desc, (list, tuple)) else (desc, None)
+    if host.is_cuda or host.dtype != torch.int32 or host.dim() != 2 or host.shape[1] != 4 or host.shape[0] < 1:
+        raise _abi.PpeaKernelError("expected the descriptor as a host int32 [N,4] tensor (byte offset, H, W, size class)")
+    host = host.contiguous()
+    N, (Hout, Wout) = host.shape[0], out_hw
+    bp = ptr(buf, torch.uint8)
+    if buf.dim() != 1 or buf.numel() < 1:
+        raise _abi.PpeaKernelError(f"expected a 1-D byte buffer, got {tuple(buf.shape)}")
+    if buf.numel() >= 1 << 31:
+        raise _abi.PpeaKernelError(f"{buf.numel()} bytes of frames: the descriptor's offsets are 32 bits")
+    for t in (flip, nonzero):
+        if t is not None and tuple(t.shape) != (N,):
+            raise _abi.PpeaKernelError(f"expected one flag per image ({N}), got {tuple(t.shape)}")
+    th, K, kh = _class_taps(taps_h, Wout, "horizontal")
+    tv, Kv, kv = _class_taps(taps_v, Hout, "vertical")
+    if K != Kv:
+        raise _abi.PpeaKernelError(f"{K} horizontal and {Kv} vertical size classes")
+    off, H, W, cls = (host[:, i].to(torch.int64) for i in range(4))
+    if bool(((off < 0) | (H < 0) | (W < 0) | ((H == 0) != (W == 0))).any()):
+        raise _abi.PpeaKernelError("descriptor: negative entry, or only one of H and W zero")
+    if bool(((cls < 0) | (cls >= K)).any()):
+        raise _abi.PpeaKernelError(f"descriptor: size class outside the {K} classes of the tap tables")
+    if bool((off + H * W * 3 > buf.numel()).any()):
+        raise _abi.PpeaKernelError(f"descriptor: a frame reaches past the buffer's {buf.numel()} bytes")
+    Hcap = max(int(H.max()), 1)
+    if words is None:
+        words = torch.cat([host.reshape(-1), ragged_row_prefix(host)]).to(buf.device)
+    if tuple(words.shape) != (N * 5 + 1,):
+        raise _abi.PpeaKernelError(f"device descriptor {tuple(words.shape)}: expected {N * 5 + 1} words (descriptor, row prefix)")
+    dp = ptr(words, torch.int32)
+    pp = _ct.c_void_p(words.data_ptr() + N * 16)
+    hp = _ct.c_void_p(host.data_ptr())
+    if scratch is None:
+        scratch = torch.empty(N * 3 * Hcap * Wout, device=buf.device, dtype=torch.uint8)
+    elif scratch.device != buf.device or scratch.numel() < N * 3 * Hcap * Wout:
+        raise _abi.PpeaKernelError(f"scratch holds {scratch.numel()} bytes on {scratch.device}, the intermediate needs "
+                                   f"{N * 3 * Hcap * Wout} on {buf.device}")
+    sp = ptr(scratch, torch.uint8)
+    out = torch.empty(N, 3, Hout, Wout, device=buf.device, dtype=torch.uint8)
+    call("ppea_lanczos_h_ragged_u8", bp, buf.numel(), hp, dp, pp, N, th, K, kh, ptr(flip, torch.int32),
+         ptr(nonzero, torch.int32), sp, Hcap, Wout, stream_ptr())
+    call("ppea_lanczos_v_ragged_u8", sp, hp, dp, N, tv, K, kv, ptr(out), Hcap, Hout, Wout, stream_ptr())
+    return out
+
+
 @torch.no_grad()
 def color_jitter_u8(img, params, nonzero=None):
     """img uint8 [N,3,H,W]; params int32 [N,10] (input_pipeline.pack_jitter_params); nonzero [N] int32 or None (0 = the
