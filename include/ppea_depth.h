@@ -738,6 +738,39 @@ int ppea_depth_errors_f32(const float* pred_disp, const float* gt, long gt_len, 
 int ppea_depth_errors_mean_f64(const double* errors, double* mean, int n, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Prediction export (ABI 29), csrc/depth_export.hip: a predicted plane at the frame's own size, as metric depth (fp32, or the
+ * KITTI depth benchmark's uint16 of depth * 256, eval_depth_ori.py:325-328) or as a colour picture (vis.colorize).
+ *   The resize is the one of ppea_depth_errors_f32: cv2.resize(INTER_LINEAR) -- half-pixel centres, no antialiasing, source
+ *   coordinate s = max((o + 0.5) * n_in / n_out - 0.5, 0) (in fp64; the weight s - i0 is rounded once to fp32 and the
+ *   interpolation is fp32), the horizontal pair first, then the vertical; a target of the source's size reads the pixel itself.  table [B][3] int64 (device) = (offset, H, W) of image b in the flat output, counted in pixels
+ *   (DeviceGroundTruth's table; dense [B,H,W] output: offsets b * H * W); out_len = pixels the output holds: a row that does
+ *   not fit it writes nothing; max_pixels >= the largest H * W of the batch (it sizes the grid: pixels of an image past it
+ *   are not written).  One launch for any B <= 65535 and any mix of sizes, on `stream`, no synchronisation, no workspace.
+ * ppea_disp_export_f32 / _u16: pred [B][h][w] fp32 scaled disparity, scale [B] fp32 (device), fp32 throughout:
+ *   mode 0 (Trainer.val, the benchmark writer): r = resize(pred),     depth = clamp(scale[b] / r, lo, hi);
+ *   mode 1 (Trainer.val_ddad):                  r = resize(1 / pred), depth = clamp(scale[b] * r, lo, hi);
+ *   any other mode: PPEA_ERR_UNSUPPORTED.  A NaN stays a NaN (np.clip).  _f32 writes depth; _u16 writes (uint16)(depth *
+ *   256.0f), the truncation of exactly the value _f32 writes, and refuses lo < 0 or hi * 256 > 65535 with PPEA_ERR_ARG.
+ * ppea_plane_range_f32: x [B][n] fp32 -> range [B][2] fp32 = (minimum, q-th percentile) of each plane's values that are
+ *   not NaN; percentile = 100: the maximum.  np.percentile's default (linear) rule: the two neighbouring order statistics
+ *   are exact (radix select on the order-mapped bit pattern, 8 bits per pass, LDS histograms, integer atomics: two calls
+ *   agree bit for bit), their interpolation is done in fp64 and rounded once.  A plane of NaNs only gives (NaN, NaN).  One
+ *   workgroup per plane.  percentile outside [0, 100]: PPEA_ERR_ARG.
+ * ppea_colorize_u8: x [B][h][w] fp32, range [B][2] fp32 (device) = (vmin, vmax), lut [256][3] uint8 (device, 4-byte
+ *   aligned) -> out uint8 HWC, image b at byte 3 * offset_b (out 4-byte aligned, 3 * out_len bytes).  Per pixel, v the
+ *   resized value: x = (v - vmin) / (vmax - vmin) in fp32, or v * 0 when vmin == vmax (vis.colorize); then matplotlib's
+ *   Colormap.__call__(bytes=True) for N = 256: row floor(x * 256), x < 0 row 0, x >= 1 row 255, NaN the bytes (0, 0, 0).
+ *   Bytes between the images are left as they were.
+ * ---------------------------------------------------------------------------------------- */
+int ppea_disp_export_f32(const float* pred, const float* scale, const int64_t* table, float* out, long out_len, int B, int h,
+                         int w, long max_pixels, float lo, float hi, int mode, void* stream);
+int ppea_disp_export_u16(const float* pred, const float* scale, const int64_t* table, uint16_t* out, long out_len, int B,
+                         int h, int w, long max_pixels, float lo, float hi, int mode, void* stream);
+int ppea_plane_range_f32(const float* x, float* range, int B, long n, double percentile, void* stream);
+int ppea_colorize_u8(const float* x, const float* range, const uint8_t* lut, const int64_t* table, uint8_t* out,
+                     long out_len, int B, int h, int w, long max_pixels, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * KITTI ground truth from raw LiDAR (kitti_utils.py:50-102 generate_depth_map, export_gt_depth.py), ABI 25: B velodyne scans
  * projected into B sparse depth maps, written into the flat layout ppea_depth_errors_f32 reads.  csrc/kitti_gt.hip.
  *   points [sum N][4] fp32 (device): the scans one after another, x forward; column 3 is ignored (the reference sets it to 1);

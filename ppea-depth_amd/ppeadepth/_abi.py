@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 28
+ABI_VERSION = 29
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -213,6 +213,10 @@ SIGNATURES = {
     "ppea_color_jitter_workspace_bytes": [_i, _i, _i],
     "ppea_color_jitter_u8": [_vp] * 6 + [_i] * 3 + [_vp],
     "ppea_repeat_rows_f32": [_vp, _vp, _i, _i, _i, _vp],
+    "ppea_disp_export_f32": [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _l, _f, _f, _i, _vp],
+    "ppea_disp_export_u16": [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _l, _f, _f, _i, _vp],
+    "ppea_plane_range_f32": [_vp, _vp, _i, _l, ctypes.c_double, _vp],
+    "ppea_colorize_u8": [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _l, _vp],
     "ppea_pack_unit_bytes": [],
     "ppea_pack_segments": [_vp, _i, _l, _vp, _vp],
     "ppea_unpack_segments": [_vp, _i, _l, _vp, _vp],

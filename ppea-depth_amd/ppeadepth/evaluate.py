@@ -38,6 +38,29 @@ def resize_linear(img, width, height):
     return F.interpolate(t, (height, width), mode="bilinear", align_corners=False)[0, 0].numpy()
 
 
+def export_depth(pred_disp, size, scale=1.0, lo=1e-3, hi=80.0, mode="disp", dtype=np.float32):
+    """The host statement of `ops.disp_export` for one image: pred_disp [h,w] scaled disparity -> depth [H,W] at size (H, W),
+    fp32 throughout.  mode "disp": clip(scale / resize(pred), lo, hi) (with scale 5.4, lo 0, hi 80 and (352, 1216):
+    eval_depth_ori.py:325-327); mode "depth": clip(scale * resize(1 / pred), lo, hi) (val_ddad).  dtype np.uint16:
+    np.uint16(depth * 256) (eval_depth_ori.py:328)."""
+    H, W = size
+    pred = np.asarray(pred_disp, dtype=np.float32)
+    s = np.float32(scale)
+    same = (H, W) == pred.shape
+    if mode == "disp":
+        depth = s / (pred if same else resize_linear(pred, W, H))
+    elif mode == "depth":
+        depth = s * (1 / pred if same else resize_linear(1 / pred, W, H))
+    else:
+        raise ValueError(f"mode {mode!r}: 'disp' or 'depth'")
+    depth = np.clip(depth, np.float32(lo), np.float32(hi))
+    if np.dtype(dtype) == np.uint16:
+        if not (lo >= 0 and np.float32(hi) * np.float32(256) <= 65535):
+            raise ValueError(f"clamp [{lo}, {hi}] times 256 does not fit 16 bits")
+        return np.uint16(depth * np.float32(256))
+    return depth
+
+
 def eigen_crop_mask(gt_depth):
     """trainer.py:804-811: valid LiDAR returns inside Garg/Eigen's crop."""
     gt_height, gt_width = gt_depth.shape[:2]

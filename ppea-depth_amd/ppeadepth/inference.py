@@ -451,6 +451,34 @@ class DepthPredictor:
         """State for B parallel cameras at (opt.height, opt.width): see `DepthStream`."""
         return DepthStream(self, B)
 
+    # ---- export: calls of their own, after predict* (they may be captured after it) ---------------------------------
+    def render(self, x, size=None, **kw):
+        """A colour picture of a predicted plane x [B,1,h,w] / [B,h,w] (`disp`, `lowest_cost`) at `size` (None: its own):
+        `vis.colorize_device` on the current stream -> uint8 [B,H,W,3], or (flat, table) for B different sizes."""
+        from . import vis
+        return vis.colorize_device(x, size, **kw)
+
+    @torch.no_grad()
+    def depth(self, disp, sizes, scale=1.0, lo=1e-3, hi=80.0, mode="disp", dtype=torch.float32, out=None, min_depth=None,
+              max_depth=None):
+        """Metric depth at the frames' own sizes from the network's disparity `disp` [B,1,h,w]: the disparity is scaled with
+        `layers.disp_to_depth(disp, opt.min_depth, opt.max_depth)` (min_depth / max_depth: other ends, e.g. `Trainer.val`'s
+        1e-3 and 80) and handed to `ops.disp_export` (there: sizes, scale, clamp, mode, dtype, out and what is returned).
+        A device="cpu" predictor computes the same in numpy (`evaluate.export_depth`)."""
+        from .layers import disp_to_depth
+        scaled, _ = disp_to_depth(disp.float(), self.opt.min_depth if min_depth is None else min_depth,
+                                  self.opt.max_depth if max_depth is None else max_depth)
+        if not self.cpu:
+            return ops.disp_export(scaled.contiguous(), sizes, scale, lo, hi, mode, dtype, out)
+        import numpy as np
+        from .evaluate import export_depth
+        planes = ops._planes(scaled, "depth").numpy()
+        B = planes.shape[0]
+        hw = ops.target_sizes(sizes, B)
+        sc = scale.tolist() if torch.is_tensor(scale) else [scale] * B
+        np_dtype = np.uint16 if dtype == torch.uint16 else np.float32
+        return ops.host_export([export_depth(planes[b], hw[b], sc[b], lo, hi, mode, np_dtype) for b in range(B)], hw, out)
+
 
 class DepthStream:
     """Video streaming on a `DepthPredictor`: `push` takes the NEXT frame of each of B cameras and matches it against the last
@@ -563,6 +591,14 @@ class DepthStream:
             g["graph"].replay()
             out = tuple(t.clone() for t in g["out"])
         return {"disp": out[0], "lowest_cost": out[1], "pose": out[2], "present": out[3]}
+
+    def render(self, out, /, what="disp", size=None, **kw):
+        """A colour picture of what a push returned: out (positional) = `push`'s dict, what "disp" or "lowest_cost"; `size`
+        and the keywords as `vis.colorize_device` (range, percentile, cmap, and its own `out=`: the picture's buffer).  A
+        call of its own on the current stream."""
+        if what not in ("disp", "lowest_cost"):
+            raise PpeaKernelError(f"render: what {what!r}, expected 'disp' or 'lowest_cost'")
+        return self.p.render(out[what], size, **kw)
 
     def capture(self):
         """One torch.cuda.graph over static buffers for a whole push, state update included (single stream, no parallel

@@ -814,6 +814,144 @@ def depth_errors_mean(errors):
 
 
 # ---------------------------------------------------------------------------------------------
+# Prediction export: depth at the frame's own size, 16-bit maps, value ranges and colour frames   (csrc/depth_export.hip)
+# ---------------------------------------------------------------------------------------------
+EXPORT_MODES = {"disp": 0, "depth": 1}      # what is resized: the disparity (val, the benchmark writer) / 1 / disp (val_ddad)
+_TARGETS = {}       # (sizes, device) -> the target table on the device; built once, so that a captured call copies nothing
+_SCALES = {}        # (value, B, device) -> [B] fp32
+
+
+def target_sizes(sizes, B):
+    """(H, W) or B pairs -> B (H, W) pairs of ints."""
+    if len(sizes) == 2 and all(isinstance(v, int) or (torch.is_tensor(v) and v.dim() == 0) for v in sizes):
+        sizes = [sizes] * B
+    hw = tuple((int(s[0]), int(s[1])) for s in sizes)
+    if len(hw) != B:
+        raise _abi.PpeaKernelError(f"{len(hw)} target sizes for a batch of {B}")
+    if any(h <= 0 or w <= 0 for h, w in hw):
+        raise _abi.PpeaKernelError(f"target sizes {hw}")
+    return hw
+
+
+def target_rows(hw):
+    """B (H, W) pairs -> ([B] rows (offset, H, W) in pixels, the images back to back; total pixels)."""
+    rows, total = [], 0
+    for h, w in hw:
+        rows.append((total, h, w))
+        total += h * w
+    return rows, total
+
+
+def export_targets(sizes, B, device):
+    """sizes (H, W) or B pairs -> (table [B,3] int64 on `device` = (offset, H, W) in pixels, the images back to back; the
+    dense (H, W) when all sizes are equal, else None; total pixels; largest image).  The device table is kept per size list:
+    only the first call with a new list copies anything."""
+    hw = target_sizes(sizes, B)
+    key = (hw, torch.device(device))
+    if key not in _TARGETS:
+        rows, total = target_rows(hw)
+        _TARGETS[key] = (torch.tensor(rows, dtype=torch.int64).to(key[1]), total, max(h * w for h, w in hw))
+    table, total, largest = _TARGETS[key]
+    return table, (hw[0] if len(set(hw)) == 1 else None), total, largest
+
+
+def host_export(images, hw, out=None):
+    """What disp_export / colorize return, from B host arrays (the numpy paths of a device="cpu" predictor): the stacked
+    tensor when all sizes are equal, else (flat, table)."""
+    import numpy as np
+    if len(set(hw)) == 1:
+        res = torch.from_numpy(np.stack(images))
+        return res if out is None else out.view(res.shape).copy_(res)
+    flat = torch.from_numpy(np.concatenate([m.reshape((-1,) + m.shape[2:]) for m in images]))
+    return (flat if out is None else out.view(flat.shape).copy_(flat)), torch.tensor(target_rows(hw)[0], dtype=torch.int64)
+
+
+def _planes(x, what):
+    if x.dim() == 4 and x.shape[1] == 1:
+        x = x[:, 0]
+    if x.dim() != 3:
+        raise _abi.PpeaKernelError(f"{what}: expected [B,h,w] (or [B,1,h,w]) planes, got {tuple(x.shape)}")
+    return x
+
+
+def _export_out(out, numel, dtype, device, what):
+    if out is None:
+        return torch.empty(numel, device=device, dtype=dtype)
+    if out.dtype != dtype or out.numel() != numel or out.device != device:
+        raise _abi.PpeaKernelError(f"{what}: out {out.dtype} {tuple(out.shape)} on {out.device}, expected {numel} values of "
+                                   f"{dtype} on {device}")
+    return out
+
+
+@torch.no_grad()
+def disp_export(pred, sizes, scale=1.0, lo=1e-3, hi=80.0, mode="disp", dtype=torch.float32, out=None):
+    """pred [B,h,w] fp32 scaled disparity -> metric depth at `sizes` ((H, W) or B pairs), cv2.resize(INTER_LINEAR) semantics:
+    mode "disp": depth = clamp(scale / resize(pred), lo, hi) (Trainer.val; with scale 5.4, lo 0, hi 80 and (352, 1216) the
+    KITTI benchmark writer, eval_depth_ori.py:325-328); mode "depth": clamp(scale * resize(1 / pred), lo, hi) (val_ddad).
+    scale: a float, or a [B] fp32 device tensor (`depth_errors`' median ratio, without a copy).  dtype torch.float32: the
+    depth; torch.uint16: trunc(depth * 256), the truncation of that same fp32 depth (hi * 256 > 65535 is refused).
+    -> [B,H,W] when all sizes are equal, else (flat [sum H W], table [B,3] int64 (offset, H, W)).  out: a contiguous tensor
+    of that many values.  One launch; the first call with a new size list also copies its table to the device."""
+    pred = _planes(pred, "disp_export")
+    B, h, w = pred.shape
+    dev = pred.device
+    p = ptr(pred, _F32)
+    if mode not in EXPORT_MODES:
+        raise _abi.PpeaKernelError(f"disp_export: mode {mode!r}, expected one of {sorted(EXPORT_MODES)}")
+    if dtype not in (torch.float32, torch.uint16):
+        raise _abi.PpeaKernelError(f"disp_export writes float32 or uint16, not {dtype}")
+    if torch.is_tensor(scale):
+        if tuple(scale.shape) != (B,):
+            raise _abi.PpeaKernelError(f"scale {tuple(scale.shape)} for a batch of {B}")
+        sc = scale
+    else:
+        key = (float(scale), B, dev)
+        if key not in _SCALES:
+            _SCALES[key] = torch.full((B,), float(scale), device=dev, dtype=_F32)
+        sc = _SCALES[key]
+    table, dense, total, largest = export_targets(sizes, B, dev)
+    o = _export_out(out, total, dtype, dev, "disp_export")
+    call("ppea_disp_export_f32" if dtype == torch.float32 else "ppea_disp_export_u16", p, ptr(sc, _F32),
+         ptr(table, torch.int64), ptr(o, dtype), total, B, h, w, largest, float(lo), float(hi), EXPORT_MODES[mode],
+         stream_ptr())
+    return o.view(B, *dense) if dense is not None else (o.view(-1), table)
+
+
+@torch.no_grad()
+def plane_range(x, percentile=100.0, out=None):
+    """x [B,h,w] fp32 -> [B,2] fp32 (minimum, `percentile`-th percentile) of each plane's values that are not NaN;
+    percentile 100: the maximum.  np.percentile's default linear rule on exact order statistics, interpolated in fp64 and
+    rounded once; bitwise reproducible.  One launch, no workspace; with `out` nothing is allocated."""
+    x = _planes(x, "plane_range")
+    B = x.shape[0]
+    xp = ptr(x, _F32)
+    o = _export_out(out, B * 2, _F32, x.device, "plane_range")
+    call("ppea_plane_range_f32", xp, ptr(o, _F32), B, x.shape[1] * x.shape[2], float(percentile), stream_ptr())
+    return o.view(B, 2)
+
+
+@torch.no_grad()
+def colorize(x, sizes, rng, lut, out=None):
+    """x [B,h,w] fp32 -> RGB uint8 pictures at `sizes` ((H, W) or B pairs): resize (cv2 INTER_LINEAR), (v - vmin) / (vmax -
+    vmin) with rng [B,2] fp32 = (vmin, vmax) on the device, and matplotlib's 256-entry lookup in `lut` [256,3] uint8 (vis.lut)
+    in one launch.  -> [B,H,W,3] when all sizes are equal, else (flat [sum H W, 3], table).  The bytes of a given `out`
+    that belong to no image are left alone; with `out` nothing is allocated."""
+    x = _planes(x, "colorize")
+    B, h, w = x.shape
+    dev = x.device
+    xp = ptr(x, _F32)
+    if tuple(rng.shape) != (B, 2):
+        raise _abi.PpeaKernelError(f"colorize: range {tuple(rng.shape)} for a batch of {B}")
+    if tuple(lut.shape) != (256, 3):
+        raise _abi.PpeaKernelError(f"colorize: a [256,3] uint8 table, got {tuple(lut.shape)}")
+    table, dense, total, largest = export_targets(sizes, B, dev)
+    o = _export_out(out, total * 3, torch.uint8, dev, "colorize")
+    call("ppea_colorize_u8", xp, ptr(rng, _F32), ptr(lut, torch.uint8), ptr(table, torch.int64), ptr(o, torch.uint8), total, B,
+         h, w, largest, stream_ptr())
+    return o.view(B, *dense, 3) if dense is not None else (o.view(-1, 3), table)
+
+
+# ---------------------------------------------------------------------------------------------
 # KITTI ground truth from raw LiDAR: kitti_utils.generate_depth_map for a ragged batch of scans   (csrc/kitti_gt.hip)
 # ---------------------------------------------------------------------------------------------
 def _host_i64(t, what):
