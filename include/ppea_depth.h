@@ -941,6 +941,26 @@ long ppea_pack_unit_bytes(void);
 int ppea_pack_segments(const void* table, int nseg, long units, void* packed, void* stream);
 int ppea_unpack_segments(const void* table, int nseg, long units, const void* packed, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Run monitor (ABI 30), csrc/run_monitor.hip: one row per training step appended to a ring on the device, in TWO launches
+ * (a scan that leaves one fp64 partial per block in `scratch`, and one block that adds the partials in a fixed order and
+ * writes the row; stream order is the hand-off, there are no atomics: the same input gives the same bits).
+ *   scalars  HOST array of 8 device pointers to fp32 scalars, NULL = absent; passed on as kernel arguments
+ *   grads    fp32 [n] at any 4-byte aligned address; NULL or n == 0: the gradient columns are 0
+ *   scratch  fp64 [scratch_blocks][3], scratch_blocks >= ppea_run_monitor_max_blocks()
+ *   ring     32-bit words [capacity][ppea_run_monitor_row_words() = 16]:
+ *            [0..7] the scalars' bits (0 where absent), [8] grad_l2 = grad_scale * sqrt(fp64 sum of squares of the finite
+ *            elements) as fp32, [9] grad_max_abs = grad_scale * max |x| over the finite elements as fp32, [10] bit k set =
+ *            scalar k present, [11] 0, [12,13] step (int64), [14,15] count of NaN / Inf elements (int64)
+ *   state    int64 [2] = {rows appended so far, first_bad_step}; the caller initialises it to {0, -1}.  The row goes to
+ *            slot (rows appended so far) % capacity and the counter is advanced; first_bad_step is set once, to `step` of
+ *            the first row with a non-finite present scalar or a non-finite count > 0.
+ * ---------------------------------------------------------------------------------------- */
+int ppea_run_monitor_row_words(void);
+int ppea_run_monitor_max_blocks(void);
+int ppea_run_monitor_f32(const void* const* scalars, const float* grads, long n, long step, float grad_scale,
+                         double* scratch, int scratch_blocks, void* ring, int capacity, void* state, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 29
+ABI_VERSION = 30
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -220,6 +220,9 @@ SIGNATURES = {
     "ppea_pack_unit_bytes": [],
     "ppea_pack_segments": [_vp, _i, _l, _vp, _vp],
     "ppea_unpack_segments": [_vp, _i, _l, _vp, _vp],
+    "ppea_run_monitor_row_words": [],
+    "ppea_run_monitor_max_blocks": [],
+    "ppea_run_monitor_f32": [_vp, _vp, _l, _l, _f, _vp, _i, _vp, _i, _vp, _vp],
 }
 
 

@@ -3168,3 +3168,93 @@ def unpack_segments(buffer, layout, tensors):
     if buffer.dtype != torch.uint8 or buffer.numel() < layout.total or buffer.device != table.device or buffer.data_ptr() % 16:
         raise PpeaKernelError(f"unpack_segments: the buffer must be 16-byte aligned uint8 of >= {layout.total} bytes on {table.device}")
     call("ppea_unpack_segments", ptr(table), len(tensors), layout.units, ptr(buffer), stream_ptr())
+
+
+# ---------------------------------------------------------------------------------------------
+# run monitor: one row per training step on a device ring (csrc/run_monitor.hip; the ring's owner is runlog.RunLog)
+# ---------------------------------------------------------------------------------------------
+MONITOR_MAX_SCALARS = 8
+MONITOR_ROW_WORDS = 16
+
+
+def run_monitor_scratch(device):
+    """The scan's per-block partials, sized by the library for this device: fp64 [blocks * 3]."""
+    return torch.zeros(int(_abi.lib.ppea_run_monitor_max_blocks()) * 3, device=device, dtype=torch.float64)
+
+
+def _monitor_row_host(scalars, grads, step, grad_scale, ring, state):
+    """The row of `ppea_run_monitor_f32` computed with torch in float64 on host tensors, same layout and same roundings."""
+    import numpy as np
+    words = ring.numpy().view(np.uint32)
+    st = state.numpy()
+    row = words[int(st[0]) % ring.shape[0]]
+    row[:] = 0
+    bad = False
+    for k, s in enumerate(scalars):
+        if s is None:
+            continue
+        bits = s.detach().reshape(1).numpy().view(np.uint32)[0]
+        row[k] = bits
+        row[10] |= np.uint32(1 << k)
+        bad = bad or (int(bits) & 0x7f800000) == 0x7f800000
+    gs = float(np.float32(grad_scale))
+    total, biggest, nonfinite = 0.0, 0.0, 0
+    if grads is not None and grads.numel():
+        g = grads.detach().double()
+        finite = torch.isfinite(g)
+        nonfinite = int(g.numel() - int(finite.sum()))
+        g = torch.where(finite, g, torch.zeros_like(g))
+        total, biggest = float((g * g).sum()), float(g.abs().max())
+    row[8:10] = np.array([gs * float(np.sqrt(total)), gs * biggest], dtype=np.float64).astype(np.float32).view(np.uint32)
+    row[12:16] = np.array([int(step), nonfinite], dtype=np.int64).view(np.uint32)
+    st[0] += 1
+    if (bad or nonfinite > 0) and st[1] < 0:
+        st[1] = int(step)
+
+
+@torch.no_grad()
+def run_monitor(scalars, grads, n, step, grad_scale, ring, state, scratch=None):
+    """Append one row to `ring` (int32 [capacity,16]; `state` int64 [2] = rows appended, first_bad_step): up to 8 fp32
+    scalars (0-dim or one-element tensors, None = absent) copied bit for bit, and of the first `n` elements of the flat fp32
+    buffer `grads` (None / n = 0: none) the norm grad_scale * sqrt(sum of squares of the finite elements) accumulated in
+    fp64, grad_scale * max |x| over the finite elements and the exact count of non-finite ones.  Row layout:
+    include/ppea_depth.h.  On a HIP device: TWO launches on the current stream, no host read, no allocation; the scalars'
+    addresses travel as kernel arguments.  Every tensor on the host: the same arithmetic with torch in float64."""
+    scalars = list(scalars)
+    if len(scalars) > MONITOR_MAX_SCALARS:
+        raise PpeaKernelError(f"run_monitor: {len(scalars)} scalars, a row holds {MONITOR_MAX_SCALARS}")
+    if ring.dtype != torch.int32 or ring.dim() != 2 or ring.shape[1] != MONITOR_ROW_WORDS or ring.shape[0] < 1 \
+            or not ring.is_contiguous() or state.dtype != torch.int64 or state.numel() != 2 or not state.is_contiguous() \
+            or state.device != ring.device:
+        raise PpeaKernelError("run_monitor: ring is int32 [capacity,16] and state int64 [2], contiguous, on one device")
+    dev = ring.device
+    for k, s in enumerate(scalars):
+        if s is None:
+            continue
+        if s.device != dev:
+            raise PpeaKernelError(f"run_monitor: scalar {k} is on {s.device}, the ring on {dev}: host and device tensors "
+                                  "do not mix")
+        if s.dtype != torch.float32 or s.numel() != 1:
+            raise PpeaKernelError(f"run_monitor: scalar {k} is {tuple(s.shape)} {s.dtype}; expected one fp32 element")
+    if grads is not None:
+        if grads.device != dev:
+            raise PpeaKernelError(f"run_monitor: the gradient buffer is on {grads.device}, the ring on {dev}: host and "
+                                  "device tensors do not mix")
+        if grads.dtype != torch.float32:
+            raise PpeaKernelError(f"run_monitor: the gradient buffer is {grads.dtype}; expected torch.float32")
+        if not grads.is_contiguous():
+            raise PpeaKernelError("run_monitor: non-contiguous gradient buffer")
+        n = grads.numel() if n is None else int(n)
+        if n < 0 or n > grads.numel():
+            raise PpeaKernelError(f"run_monitor: n = {n} of a buffer of {grads.numel()} elements")
+    else:
+        n = 0
+    if dev.type != "cuda":
+        _monitor_row_host(scalars, None if grads is None else grads.reshape(-1)[:n], step, grad_scale, ring, state)
+        return
+    if n > 0 and (scratch is None or scratch.device != dev or scratch.dtype != torch.float64 or not scratch.is_contiguous()):
+        raise PpeaKernelError("run_monitor: scratch is a contiguous fp64 buffer on the ring's device (run_monitor_scratch)")
+    ptrs = (_ct.c_void_p * MONITOR_MAX_SCALARS)(*[None if s is None else s.data_ptr() for s in scalars])
+    call("ppea_run_monitor_f32", ptrs, _ct.c_void_p(grads.data_ptr()) if n > 0 else None, n, int(step), float(grad_scale),
+         ptr(scratch) if n > 0 else None, scratch.numel() // 3 if n > 0 else 0, ptr(ring), ring.shape[0], ptr(state),
+         stream_ptr())
