@@ -1,6 +1,6 @@
 """TEST INFRASTRUCTURE ONLY -- case tables, seeded inputs, float64 references and per-element error bounds for the pointwise
 GEMM family: csrc/pwconv.hip (v1 pwconv_kernel, v2 pwconv2_kernel on the LDS-DMA ring), csrc/pwgrad.hip (pwgrad_kernel,
-pwgrad2_kernel<32>, pwgrad2_pair_kernel<32> and the three reduce kernels) and csrc/tapsum.hip.  Pure torch; everything is a
+pwgrad2_kernel<32>, pwgrad2_pair_kernel<32> and the two reduce kernels) and csrc/tapsum.hip.  Pure torch; everything is a
 function of its arguments and the seed.  Which kernel a row reaches is NOT restated here: a row names the arm it claims and how
 it gets there (`natural`: no switch set; `hook`: under the variables in `env`), and tests/test_pw_arms_cpu.py asks the
 library's own plan queries (ops.pwconv_plan / pwgrad_plan / pwgrad_pair_plan, the functions the launches go by) whether it
@@ -70,8 +70,8 @@ ALL_PW_ARMS = frozenset(
     + [arm(1, 0, bm, bk, e) for bm, bk in V1_TILES for e in (0, 1, 2, 4)]
     + [arm(1, 1, bm, bk, e) for bm, bk in V1_TILES for e in (0, 1, 2)])
 assert len(ALL_PW_ARMS) == 63
-PWGRAD_KERNELS = frozenset(("pwgrad_kernel", "pwgrad2_kernel<32>", "pwgrad2_pair_kernel<32>", "pwgrad_reduce_kernel",
-                            "pwgrad_reduce_ex_kernel", "pwgrad_reduce_ex2_kernel"))
+PWGRAD_KERNELS = frozenset(("pwgrad_kernel", "pwgrad2_kernel<32>", "pwgrad2_pair_kernel<32>", "pwgrad_reduce_ex_kernel",
+                            "pwgrad_reduce_ex2_kernel"))
 
 
 def epis_of(ta):

@@ -24,7 +24,6 @@ typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
 constexpr int TH = 8, TW = 16;
 
-__device__ __forceinline__ uint16_t f2bf(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
 constexpr int kp_of(int ks) { return (ks * 8 + 31) / 32 * 32; }
 
 struct ImgArgs {

@@ -46,9 +46,6 @@ constexpr int halo_cap(int stride, int ks) {
     return ks <= 3 ? (stride == 1 ? 4 * 66 : 9 * 65) : (stride == 1 ? 14 * 22 : 21 * 37);
 }
 
-__device__ __forceinline__ float bf2f(uint16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
-
 struct ConvArgs {
     const uint16_t* x;      // [N][H][W][Cin]
     const uint16_t* w;      // packed [R*S][Cout][CinP], CinP = Cin rounded up to 32, zero filled

@@ -28,7 +28,6 @@ typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 constexpr int TILE_PX = 128;          // output pixels per staged patch: TR rows x TC columns (4 K steps of 32 pixels)
 constexpr int MAX_TAPS = 9;
 
-__device__ __forceinline__ float bf2f(uint16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
 // XOR on the 8-byte chunk index of an LDS row of CH channels (bank windows of the transposing reads, see header)
 template <int CH> __device__ __forceinline__ int swz(int row) {
     if constexpr (CH == 64) return 4 * ((row >> 1) & 1) + 8 * ((row >> 3) & 1);

@@ -14,16 +14,12 @@
 //     reads are bank-conflict free (cdna_hip_programming.md 2, T10);
 //   * global -> register prefetch of the next K-tile overlaps the MFMAs of the current one; LDS is
 //     double buffered so a K step costs one barrier.
-#include "common.h"
+#include "gemm_bf16.h"
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
 
 constexpr int BN = 128;
 constexpr int B_STRIDE = 256;                   // bytes per B row (128 pixels), swizzled
@@ -33,17 +29,63 @@ constexpr int a_stride(int bk) { return bk == 32 ? 96 : 160; }   // bytes per A 
 
 __device__ __forceinline__ int b_swz(int row) { return 4 * (row & 3) + 16 * ((row >> 3) & 1); }
 
-__device__ __forceinline__ float bf2f(uint16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-__device__ __forceinline__ float dgelu_f(float x) {
-    return 0.5f * (1.f + erff(x * 0.70710678118654752f)) + x * 0.3989422804014327f * __expf(-0.5f * x * x);
-}
-
-// EPI 4: as EPI 0, and per-channel partial sums (sum, sum of squares) of the values AS STORED, per pixel-wave of the
-// workgroup, into (float*)Y2 [M][B * pixel tiles * WN][2] -- the BatchNorm that follows needs no statistics pass.
+// ---- epilogue values: one accumulator quad (4 consecutive pixels of one channel) -> the packed bf16 pairs both kernels store
 // EPI 0: Y = acc + bias.   EPI 1: Y = pre = acc + bias, Y2 = GELU(pre) (pre rounded to bf16 first, like an
 // autocast nn.GELU on the stored tensor).   EPI 2: Y = acc * GELU'(aux[n][m][p]) (data gradient through GELU).
+// EPI 4: as EPI 0, and per-channel partial sums (sum, sum of squares) of the values AS STORED, per pixel-wave of the
+// workgroup, into (float*)Y2 [M][B * pixel tiles * WN][2] -- the BatchNorm that follows needs no statistics pass.
+struct PwQuad { uint2 y, y2; };
+struct Bf16x4 { uint16_t v[4]; };
+__device__ __forceinline__ Bf16x4 unpack4(uint2 a) {
+    return {{(uint16_t)(a.x & 0xffffu), (uint16_t)(a.x >> 16), (uint16_t)(a.y & 0xffffu), (uint16_t)(a.y >> 16)}};
+}
+
+// `aux`: the quad's four bf16 of aux (EPI 2);  `count`: the quad lies inside the plane and joins the statistics (EPI 4).
+// The form is the one hipcc compiles like the code spelled out in each kernel: the quad by value and the dwords packed here (with
+// uint16_t[4] results handed back by reference every value is converted alone, twice the v_cvt_pk_bf16_f32); GELU of the stored
+// values in a loop of its own (inside the first, the 128-row v1 kernels take 4 more VGPRs).
+template <int EPI>
+__device__ __forceinline__ PwQuad pw_values(f32x4 acc, float bv, uint2 aux, bool count, float& st_s, float& st_q) {
+    uint16_t e[4], f[4] = {0, 0, 0, 0};
+    if constexpr (EPI == 2) {
+        const Bf16x4 x = unpack4(aux);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) e[r] = f2bf(acc[r] * dgelu_f(bf2f(x.v[r])));
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            e[r] = f2bf(acc[r] + bv);
+            if constexpr (EPI == 4) {
+                if (count) { const float t = bf2f(e[r]); st_s += t; st_q += t * t; }
+            }
+        }
+        if constexpr (EPI == 1) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) f[r] = f2bf(gelu_f(bf2f(e[r])));
+        }
+    }
+    return {make_uint2(e[0] | ((uint32_t)e[1] << 16), e[2] | ((uint32_t)e[3] << 16)),
+            make_uint2(f[0] | ((uint32_t)f[1] << 16), f[2] | ((uint32_t)f[3] << 16))};
+}
+
+// the bias of channel m (fp32 or bf16; none: 0)
+__device__ __forceinline__ float pw_bias(const void* bias, int bias_bf16, int m) {
+    if (bias == nullptr) return 0.f;
+    return bias_bf16 ? bf2f(reinterpret_cast<const uint16_t*>(bias)[m]) : reinterpret_cast<const float*>(bias)[m];
+}
+
+// EPI 4: the four lane groups g hold the other pixels of channel m -- fixed-order butterfly, lane group 0 writes partial
+// `part + wn` of P; channel-major [M][P][2]: the finalize kernel reads a channel's P partials as one contiguous run
+__device__ __forceinline__ void pw_store_stats(float* stats, float st_s, float st_q, bool writer, int m, long P, long part, int wn) {
+    st_s += __shfl_xor(st_s, 16, WAVE); st_q += __shfl_xor(st_q, 16, WAVE);
+    st_s += __shfl_xor(st_s, 32, WAVE); st_q += __shfl_xor(st_q, 32, WAVE);
+    if (writer) {
+        float* sp = stats + ((long)m * P + part + wn) * 2;
+        sp[0] = st_s; sp[1] = st_q;
+    }
+}
+
+// v1: register prefetch into a double-buffered LDS tile.
 // TA: the matrix is given transposed, At [K][M] (m contiguous) -- its tile is staged like the X tile and the A
 // fragments come out of the transposing LDS read as well, so a data gradient uses the forward weight as is.
 template <int BM, int WM, int WN, int EPI, bool TA, int BK>
@@ -146,12 +188,7 @@ __global__ __launch_bounds__(256) void pwconv_kernel(const uint16_t* __restrict_
             for (int i = 0; i < MT; ++i) {
                 if constexpr (TA) {
                     const int chunk = (((wm * TM + 16 * i) >> 2) + pp) ^ b_swz(b_rowi);
-                    const uint8_t* ap = buf + a_off + h * 32 * B_STRIDE + (chunk << 3);
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(ap));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(ap + 4 * B_STRIDE));
-                    typedef __attribute__((ext_vector_type(8))) short s16x8;
-                    const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    af[i] = __builtin_bit_cast(bf16x8, both);
+                    af[i] = tr_frag(buf + a_off + h * 32 * B_STRIDE + (chunk << 3), B_STRIDE);
                 } else {
                     af[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(buf + a_off + i * 16 * A_STRIDE + h * 64));
                 }
@@ -159,12 +196,7 @@ __global__ __launch_bounds__(256) void pwconv_kernel(const uint16_t* __restrict_
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const int chunk = (((wn * TN + 16 * j) >> 2) + pp) ^ b_s;
-                const uint8_t* bp = buf + b_off + h * 32 * B_STRIDE + (chunk << 3);
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bp));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bp + 4 * B_STRIDE));
-                typedef __attribute__((ext_vector_type(8))) short s16x8;
-                const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                bfr[j] = __builtin_bit_cast(bf16x8, both);
+                bfr[j] = tr_frag(buf + b_off + h * 32 * B_STRIDE + (chunk << 3), B_STRIDE);
             }
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -185,66 +217,32 @@ __global__ __launch_bounds__(256) void pwconv_kernel(const uint16_t* __restrict_
     for (int i = 0; i < MT; ++i) {
         const int m = m0 + wm * TM + 16 * i + li;
         if (m >= M) continue;
-        float bv = 0.f;
-        if (bias != nullptr)
-            bv = bias_bf16 ? bf2f(reinterpret_cast<const uint16_t*>(bias)[m]) : reinterpret_cast<const float*>(bias)[m];
+        const float bv = pw_bias(bias, bias_bf16, m);
         float st_s = 0.f, st_q = 0.f;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int p = p0 + wn * TN + 16 * j + 4 * g;
             if (p >= HW) continue;
             const long o = (long)n * M * HW + (long)m * HW + p;
-            uint16_t v[4];
-            if constexpr (EPI == 0 || EPI == 4) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = f2bf(acc[i][j][r] + bv);
-                if constexpr (EPI == 4) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { const float f = bf2f(v[r]); st_s += f; st_q += f * f; }
-                }
-            } else if constexpr (EPI == 1) {
-                uint16_t w[4];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    v[r] = f2bf(acc[i][j][r] + bv);
-                    w[r] = f2bf(gelu_f(bf2f(v[r])));
-                }
-                *reinterpret_cast<uint2*>(Y2 + o) = make_uint2(w[0] | ((uint32_t)w[1] << 16), w[2] | ((uint32_t)w[3] << 16));
-            } else {
-                const uint2 a = *reinterpret_cast<const uint2*>(aux + o);
-                const uint16_t x[4] = {(uint16_t)(a.x & 0xffffu), (uint16_t)(a.x >> 16), (uint16_t)(a.y & 0xffffu),
-                                       (uint16_t)(a.y >> 16)};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = f2bf(acc[i][j][r] * dgelu_f(bf2f(x[r])));
-            }
-            *reinterpret_cast<uint2*>(Y + o) = make_uint2(v[0] | ((uint32_t)v[1] << 16), v[2] | ((uint32_t)v[3] << 16));
+            uint2 a = make_uint2(0, 0);
+            if constexpr (EPI == 2) a = *reinterpret_cast<const uint2*>(aux + o);
+            const PwQuad v = pw_values<EPI>(acc[i][j], bv, a, true, st_s, st_q);
+            if constexpr (EPI == 1) *reinterpret_cast<uint2*>(Y2 + o) = v.y2;
+            *reinterpret_cast<uint2*>(Y + o) = v.y;
         }
-        if constexpr (EPI == 4) {
-            // the four lane groups g hold the other pixels of channel m: fixed-order butterfly, lane group 0 writes
-            st_s += __shfl_xor(st_s, 16, WAVE); st_q += __shfl_xor(st_q, 16, WAVE);
-            st_s += __shfl_xor(st_s, 32, WAVE); st_q += __shfl_xor(st_q, 32, WAVE);
-            if (g == 0) {
-                // channel-major [M][P][2]: the finalize kernel reads a channel's P partials as one contiguous run
-                const long P = (long)gridDim.z * gridDim.x * WN;
-                float* sp = reinterpret_cast<float*>(Y2) + ((long)m * P + ((long)n * gridDim.x + blockIdx.x) * WN + wn) * 2;
-                sp[0] = st_s; sp[1] = st_q;
-            }
-        }
+        if constexpr (EPI == 4)
+            pw_store_stats(reinterpret_cast<float*>(Y2), st_s, st_q, g == 0, m, (long)gridDim.z * gridDim.x * WN,
+                           ((long)n * gridDim.x + blockIdx.x) * WN, wn);
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// v2: the same GEMM with a three-stage LDS ring filled by LDS-DMA (`global_load_lds`, 16 bytes per lane, no staging
-// registers), counted `s_waitcnt vmcnt(N)` + ONE raw `s_barrier` per K step (two K tiles in flight across it), an
-// XCD-aware tile order and 16-byte epilogue stores.
-//   * LDS-DMA writes wave-uniform base + lane * 16, so both tiles are dense images and every swizzle sits on the SOURCE
-//     address (the inverse permutation of the fragment reads):
+// v2: the same GEMM on the three-stage LDS-DMA ring of gemm_bf16.h (one raw barrier per K step, two K tiles in flight
+// across it), an XCD-aware tile order and 16-byte epilogue stores.
+//   * both tiles are dense images with the swizzle on the SOURCE address:
 //       X tile [BK k][128 pixels] (256-byte rows): 16-byte slot s of row r holds pixel chunk s ^ (2 (r & 3) + 8 ((r >> 3) & 1))
 //         -- the 8-byte swizzle of v1, which is a multiple of two 8-byte chunks; read with `ds_read_b64_tr_b16`;
-//       A tile [BM m][BK k] (128- / 64-byte rows): slot s of row r holds k chunk s ^ ((r >> 1) & 7)  /  s ^ (2 ((r >> 2) & 1));
-//         read with `ds_read_b128` (conflict free for its four 16-lane service groups, MI355X_MICROARCH.md LDS).
-//   * a wave waits for ITS loads of stage t (vmcnt leaves the newer stage in flight), the barrier publishes all four
-//     waves' pieces and retires everybody's reads of stage t - 1, whose buffer the loads for stage t + 2 then overwrite.
+//       A tile [BM m][BK k] (128- / 64-byte rows): swz16<BK>, read with `ds_read_b128`.
 //   * epilogue: `v_permlane16_swap` between the packed results of two neighbouring 16-pixel tiles gives every lane 8
 //     consecutive pixels of one channel: one 16-byte store instead of two 8-byte ones (a wave writes 64 contiguous bytes
 //     per channel row).
@@ -253,7 +251,6 @@ __global__ __launch_bounds__(256) void pwconv_kernel(const uint16_t* __restrict_
 //     the same transposing read -- the adapters' data gradients ran 17-22 us on v1's transposed mode against 5-9 us for
 //     the same GEMM with a row-major matrix.
 // Requirements: K % BK == 0, HW % 8 == 0; TA: BM = 128, M % 8 == 0.
-constexpr int NSTAGE = 3;
 
 // EPI 5 (inference, eval-mode BatchNorm folded to a per-channel table; ppea_pwconv_infer_bf16):
 //     t = act(s[m] * acc + o[m])   Y = t (+ r1) (+ r2_scale * r2)   Y2 = s2[m] * Y + o2[m]  (Y as stored; Y2 optional)
@@ -265,8 +262,23 @@ struct PwInfer {
 template <int EPI> struct PwExtra {};
 template <> struct PwExtra<5> { PwInfer v; };
 
-template <int BK> __device__ __forceinline__ int a_swz16(int row) {
-    return BK == 64 ? ((row >> 1) & 7) : (2 * ((row >> 2) & 1));
+// this lane's channel of the tables (s, o: 1, 0 where absent; s2, o2 only with a second output), then pw_values' shape
+struct PwInferLane { float sc = 1.f, sh = 0.f, sc2 = 0.f, sh2 = 0.f; };
+__device__ __forceinline__ PwQuad pw_infer_values(f32x4 acc, const PwInferLane& t, uint2 r1, uint2 r2, const PwInfer& ex) {
+    const Bf16x4 x1 = unpack4(r1), x2 = unpack4(r2);
+    uint16_t e[4], f[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        float v = fmaf(t.sc, acc[r], t.sh);
+        if (ex.act == 1) v = fmaxf(v, 0.f);
+        else if (ex.act == 2) v = gelu_f(v);
+        v += bf2f(x1.v[r]);
+        v = fmaf(ex.r2_scale, bf2f(x2.v[r]), v);
+        e[r] = f2bf(v);
+        f[r] = f2bf(fmaf(t.sc2, bf2f(e[r]), t.sh2));          // the next block's pre-BN of the tensor as stored
+    }
+    return {make_uint2(e[0] | ((uint32_t)e[1] << 16), e[2] | ((uint32_t)e[3] << 16)),
+            make_uint2(f[0] | ((uint32_t)f[1] << 16), f[2] | ((uint32_t)f[3] << 16))};
 }
 
 template <int BM, int BK, int EPI, bool TA = false>
@@ -310,7 +322,7 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
         } else {
             const int row = t * (1024 / ARB) + lane / (ARB / 16), slot = lane % (ARB / 16);
             const int m = min(m0 + row, M - 1);                  // rows past M: any valid row (their outputs are not stored)
-            a_src[c] = A + (long)m * K + 8 * (slot ^ a_swz16<BK>(row));
+            a_src[c] = A + (long)m * K + 8 * (slot ^ swz16<BK>(row));
         }
     }
 #pragma unroll
@@ -321,15 +333,7 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
         if (p >= HW) p = p0;                                     // chunks past the plane: any valid chunk (not stored)
         x_src[c] = Xn + (long)row * HW + p;
     }
-    // LDS-DMA through inline asm: hipcc's wait-count pass would otherwise drain EVERY pending LDS-DMA (`vmcnt(0)`) in front of
-    // the first transposing LDS read after an issue -- it cannot tell the stage being filled from the stage being read --
-    // which is the whole pipeline.  M0 (the LDS destination base) is written in the statement that uses it and restored.
-    const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
-    auto glds16 = [&](const uint16_t* src, unsigned dst) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-    };
+    const unsigned lds_base = lds_address(lds);
     auto issue = [&](int kt, int stage) {
         const unsigned base = __builtin_amdgcn_readfirstlane(lds_base + stage * STAGE + wave * 1024);
         const long ka = TA ? (long)kt * BK * M : (long)kt * BK, kx = (long)kt * BK * HW;
@@ -354,7 +358,7 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
 #pragma unroll
         for (int h = 0; h < KH; ++h) {
             const int row = wm * TM + 16 * i + li;
-            a_off[i][h] = row * ARB + 16 * ((4 * h + g) ^ a_swz16<BK>(row));
+            a_off[i][h] = row * ARB + 16 * ((4 * h + g) ^ swz16<BK>(row));
         }
     const int x_off = A_BYTES + b_rowi * B_STRIDE;
 
@@ -363,10 +367,8 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
     if (nk > 1) issue(1, 1);
     int cur = 0;
     for (int kt = 0; kt < nk; ++kt) {
-        if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (kt + 2 < nk) issue(kt + 2, cur >= 1 ? cur - 1 : NSTAGE - 1);       // (cur + 2) % 3: the buffer read one step ago
+        ring_wait<LPS>(kt + 1 < nk);
+        if (kt + 2 < nk) issue(kt + 2, ring_refill(cur));
         const uint8_t* buf = lds + cur * STAGE;
 #pragma unroll
         for (int h = 0; h < KH; ++h) {
@@ -375,12 +377,7 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
             for (int i = 0; i < MT; ++i) {
                 if constexpr (TA) {
                     const int chunk = (((wm * TM + 16 * i) >> 2) + pp) ^ b_s;
-                    const uint8_t* ap = buf + b_rowi * B_STRIDE + h * 32 * B_STRIDE + (chunk << 3);
-                    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(ap));
-                    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(ap + 4 * B_STRIDE));
-                    typedef __attribute__((ext_vector_type(8))) short s16x8a;
-                    const s16x8a both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                    af[i] = __builtin_bit_cast(bf16x8, both);
+                    af[i] = tr_frag(buf + b_rowi * B_STRIDE + h * 32 * B_STRIDE + (chunk << 3), B_STRIDE);
                 } else {
                     af[i] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(buf + a_off[i][h]));
                 }
@@ -388,12 +385,7 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
 #pragma unroll
             for (int j = 0; j < NT; ++j) {
                 const int chunk = (((wn * TN + 16 * j) >> 2) + pp) ^ b_s;
-                const uint8_t* bp = buf + x_off + h * 32 * B_STRIDE + (chunk << 3);
-                const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bp));
-                const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(bp + 4 * B_STRIDE));
-                typedef __attribute__((ext_vector_type(8))) short s16x8;
-                const s16x8 both = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-                bfr[j] = __builtin_bit_cast(bf16x8, both);
+                bfr[j] = tr_frag(buf + x_off + h * 32 * B_STRIDE + (chunk << 3), B_STRIDE);
             }
 #pragma unroll
             for (int i = 0; i < MT; ++i)
@@ -401,7 +393,7 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
                 for (int j = 0; j < NT; ++j)
                     acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[j], af[i], acc[i][j], 0, 0, 0);
         }
-        cur = cur == NSTAGE - 1 ? 0 : cur + 1;
+        cur = ring_next(cur);
     }
 
     // ---- epilogue: transposed C layout (col = lane & 15 = channel, rows 4 g + r = pixels); pairs of pixel tiles exchange
@@ -410,17 +402,15 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
     for (int i = 0; i < MT; ++i) {
         const int m = m0 + wm * TM + 16 * i + li;
         const bool m_ok = m < M;
-        float bv = 0.f;
-        if (bias != nullptr && m_ok)
-            bv = bias_bf16 ? bf2f(reinterpret_cast<const uint16_t*>(bias)[m]) : reinterpret_cast<const float*>(bias)[m];
+        const float bv = m_ok ? pw_bias(bias, bias_bf16, m) : 0.f;
         float st_s = 0.f, st_q = 0.f;
         uint2 v[NT], w[NT];
-        float sc = 1.f, sh = 0.f, sc2 = 0.f, sh2 = 0.f;              // EPI 5: this lane's channel of the tables
+        PwInferLane tab;
         if constexpr (EPI == 5) {
             if (m_ok) {
-                if (ex.v.s != nullptr) sc = ex.v.s[m];
-                if (ex.v.o != nullptr) sh = ex.v.o[m];
-                if (Y2 != nullptr) { sc2 = ex.v.s2[m]; sh2 = ex.v.o2[m]; }
+                if (ex.v.s != nullptr) tab.sc = ex.v.s[m];
+                if (ex.v.o != nullptr) tab.sh = ex.v.o[m];
+                if (Y2 != nullptr) { tab.sc2 = ex.v.s2[m]; tab.sh2 = ex.v.o2[m]; }
             }
         }
 #pragma unroll
@@ -428,44 +418,19 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
             const int p = p0 + wn * TN + 16 * j + 4 * g;
             const bool ok = m_ok && p < HW;
             const long o = (long)n * M * HW + (long)m * HW + p;
-            uint16_t e[4], f[4] = {0, 0, 0, 0};
-            if constexpr (EPI == 2) {
-                uint2 a = make_uint2(0, 0);
-                if (ok) a = *reinterpret_cast<const uint2*>(aux + o);
-                const uint16_t x[4] = {(uint16_t)(a.x & 0xffffu), (uint16_t)(a.x >> 16), (uint16_t)(a.y & 0xffffu),
-                                       (uint16_t)(a.y >> 16)};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) e[r] = f2bf(acc[i][j][r] * dgelu_f(bf2f(x[r])));
-            } else if constexpr (EPI == 5) {
-                uint2 a1 = make_uint2(0, 0), a2 = make_uint2(0, 0);
-                if (ok && ex.v.r1 != nullptr) a1 = *reinterpret_cast<const uint2*>(ex.v.r1 + o);
+            uint2 a = make_uint2(0, 0), a2 = make_uint2(0, 0);      // aux (EPI 2) / r1, r2 (EPI 5): absent or outside = 0
+            PwQuad r;
+            if constexpr (EPI == 5) {
+                if (ok && ex.v.r1 != nullptr) a = *reinterpret_cast<const uint2*>(ex.v.r1 + o);
                 if (ok && ex.v.r2 != nullptr) a2 = *reinterpret_cast<const uint2*>(ex.v.r2 + o);
-                const uint16_t x1[4] = {(uint16_t)(a1.x & 0xffffu), (uint16_t)(a1.x >> 16), (uint16_t)(a1.y & 0xffffu),
-                                        (uint16_t)(a1.y >> 16)};
-                const uint16_t x2[4] = {(uint16_t)(a2.x & 0xffffu), (uint16_t)(a2.x >> 16), (uint16_t)(a2.y & 0xffffu),
-                                        (uint16_t)(a2.y >> 16)};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    float t = fmaf(sc, acc[i][j][r], sh);
-                    if (ex.v.act == 1) t = fmaxf(t, 0.f);
-                    else if (ex.v.act == 2) t = gelu_f(t);
-                    t += bf2f(x1[r]);
-                    t = fmaf(ex.v.r2_scale, bf2f(x2[r]), t);
-                    e[r] = f2bf(t);
-                    f[r] = f2bf(fmaf(sc2, bf2f(e[r]), sh2));          // the next block's pre-BN of the tensor as stored
-                }
+                r = pw_infer_values(acc[i][j], tab, a, a2, ex.v);
             } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    e[r] = f2bf(acc[i][j][r] + bv);
-                    if constexpr (EPI == 1) f[r] = f2bf(gelu_f(bf2f(e[r])));
-                    if constexpr (EPI == 4) {
-                        if (ok) { const float t = bf2f(e[r]); st_s += t; st_q += t * t; }
-                    }
+                if constexpr (EPI == 2) {
+                    if (ok) a = *reinterpret_cast<const uint2*>(aux + o);
                 }
+                r = pw_values<EPI>(acc[i][j], bv, a, ok, st_s, st_q);
             }
-            v[j] = make_uint2(e[0] | ((uint32_t)e[1] << 16), e[2] | ((uint32_t)e[3] << 16));
-            w[j] = make_uint2(f[0] | ((uint32_t)f[1] << 16), f[2] | ((uint32_t)f[3] << 16));
+            v[j] = r.y; w[j] = r.y2;
         }
 #pragma unroll
         for (int j = 0; j < NT; j += 2) {
@@ -483,15 +448,8 @@ __global__ __launch_bounds__(256) void pwconv2_kernel(const uint16_t* __restrict
                     *reinterpret_cast<uint4*>(Y2 + o) = make_uint4(tx[0], ty[0], tx[1], ty[1]);
             }
         }
-        if constexpr (EPI == 4) {
-            st_s += __shfl_xor(st_s, 16, WAVE); st_q += __shfl_xor(st_q, 16, WAVE);
-            st_s += __shfl_xor(st_s, 32, WAVE); st_q += __shfl_xor(st_q, 32, WAVE);
-            if (g == 0 && m_ok) {
-                const long P = (long)(total / mtiles) * WN;
-                float* sp = reinterpret_cast<float*>(Y2) + ((long)m * P + (long)pt * WN + wn) * 2;
-                sp[0] = st_s; sp[1] = st_q;
-            }
-        }
+        if constexpr (EPI == 4)
+            pw_store_stats(reinterpret_cast<float*>(Y2), st_s, st_q, g == 0 && m_ok, m, (long)(total / mtiles) * WN, (long)pt * WN, wn);
     }
 }
 
@@ -580,31 +538,64 @@ int launch_pw2_t(const void* A, const void* X, const void* bias, int bias_bf16, 
     return launch_status();
 }
 
+// THE tile dispatch: f(BM, BK), as integral constants, for the tile of `c`.  v2 has 128/64, 128/32, 64/64, 64/32 and 32/64;
+// v1 has no 128-row tile with 64-channel steps, and has 32/32.
+template <bool V2, class F>
+int pw_tile(const PwCfg& c, F&& f) {
+    typedef std::integral_constant<int, 32> i32;
+    typedef std::integral_constant<int, 64> i64;
+    typedef std::integral_constant<int, 128> i128;
+    if (c.bm == 128) {
+        if constexpr (V2) { if (c.bk == 64) return f(i128{}, i64{}); }
+        return f(i128{}, i32{});
+    }
+    if (c.bm == 64) return c.bk == 64 ? f(i64{}, i64{}) : f(i64{}, i32{});
+    if constexpr (!V2) { if (c.bk != 64) return f(i32{}, i32{}); }
+    return f(i32{}, i64{});
+}
+
 template <int EPI, bool TA>
 int launch_pw(const void* A, const void* X, const void* bias, int bias_bf16, const void* aux, void* Y, void* Y2, int B,
               int M, int K, int HW, hipStream_t st) {
     const PwCfg c = pw_choose(B, M, K, HW, TA);
     if (c.v2) {
-        if constexpr (TA) {
-            return launch_pw2_t<128, 32, EPI, true>(A, X, bias, bias_bf16, aux, Y, Y2, B, M, K, HW, st);
-        } else {
-#define PW2(BM_, BK_) return launch_pw2_t<BM_, BK_, EPI>(A, X, bias, bias_bf16, aux, Y, Y2, B, M, K, HW, st)
-            if (c.bm == 128) { if (c.bk == 64) PW2(128, 64); else PW2(128, 32); }
-            if (c.bm == 64) { if (c.bk == 64) PW2(64, 64); else PW2(64, 32); }
-            PW2(32, 64);
-#undef PW2
-        }
+        if constexpr (TA) return launch_pw2_t<128, 32, EPI, true>(A, X, bias, bias_bf16, aux, Y, Y2, B, M, K, HW, st);
+        else return pw_tile<true>(c, [&](auto bm, auto bk) {
+            return launch_pw2_t<decltype(bm)::value, decltype(bk)::value, EPI>(A, X, bias, bias_bf16, aux, Y, Y2, B, M, K, HW, st);
+        });
     }
-    const int nb = (HW + BN - 1) / BN;
-#define PW_LAUNCH(BM_, WM_, WN_, BK_)                                                                                 \
-    hipLaunchKernelGGL((pwconv_kernel<BM_, WM_, WN_, EPI, TA, BK_>), dim3(nb, (M + BM_ - 1) / BM_, B), dim3(256), 0, st, \
-                       (const uint16_t*)A, (const uint16_t*)X, bias, bias_bf16, (const uint16_t*)aux, (uint16_t*)Y, \
-                       (uint16_t*)Y2, M, K, HW)
-    if (c.bm == 128) PW_LAUNCH(128, 2, 2, 32);
-    else if (c.bm == 64) { if (c.bk == 64) PW_LAUNCH(64, 2, 2, 64); else PW_LAUNCH(64, 2, 2, 32); }
-    else { if (c.bk == 64) PW_LAUNCH(32, 1, 4, 64); else PW_LAUNCH(32, 1, 4, 32); }
-#undef PW_LAUNCH
-    return launch_status();
+    return pw_tile<false>(c, [&](auto bm, auto bk) {
+        constexpr int BM = decltype(bm)::value, WM = BM >= 64 ? 2 : 1;
+        hipLaunchKernelGGL((pwconv_kernel<BM, WM, 4 / WM, EPI, TA, decltype(bk)::value>), dim3((HW + BN - 1) / BN, (M + BM - 1) / BM, B),
+                           dim3(256), 0, st, (const uint16_t*)A, (const uint16_t*)X, bias, bias_bf16, (const uint16_t*)aux,
+                           (uint16_t*)Y, (uint16_t*)Y2, M, K, HW);
+        return launch_status();
+    });
+}
+
+// ppea_pwconv_bf16 / _stats_bf16 / _ex_bf16: the shape check, then the (epilogue, A mode) instantiation
+int pw_run(int epi, bool ta, const void* A, const void* X, const void* bias, int bias_bf16, const void* aux, void* Y, void* Y2,
+           int B, int M, int K, int HW, void* stream) {
+    if (!pw_served(B, M, K, HW, ta)) return PPEA_ERR_UNSUPPORTED;
+    if ((epi == 1 || epi == 4) && !Y2) return PPEA_ERR_ARG;
+    if (epi == 2 && !aux) return PPEA_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    auto go = [&](auto e, auto t) {
+        constexpr int EPI = decltype(e)::value;
+        return launch_pw<EPI, decltype(t)::value>(A, X, EPI == 2 ? nullptr : bias, EPI == 2 ? 0 : bias_bf16, EPI == 2 ? aux : nullptr, Y,
+                                                  (EPI == 1 || EPI == 4) ? Y2 : nullptr, B, M, K, HW, st);
+    };
+    using std::integral_constant;
+    switch (ta ? epi + 8 : epi) {
+        case 0: return go(integral_constant<int, 0>{}, std::false_type{});
+        case 1: return go(integral_constant<int, 1>{}, std::false_type{});
+        case 2: return go(integral_constant<int, 2>{}, std::false_type{});
+        case 4: return go(integral_constant<int, 4>{}, std::false_type{});
+        case 8: return go(integral_constant<int, 0>{}, std::true_type{});
+        case 9: return go(integral_constant<int, 1>{}, std::true_type{});
+        case 10: return go(integral_constant<int, 2>{}, std::true_type{});
+    }
+    return PPEA_ERR_ARG;
 }
 
 }  // namespace
@@ -615,8 +606,7 @@ extern "C" {
 // Requirements of the fast path: K % 32 == 0, HW % 8 == 0 (else PPEA_ERR_UNSUPPORTED).
 int ppea_pwconv_bf16(const void* A, const void* X, const float* bias, void* Y, int B, int M, int K, int HW,
                      void* stream) {
-    if (!pw_served(B, M, K, HW, false)) return PPEA_ERR_UNSUPPORTED;
-    return launch_pw<0, false>(A, X, bias, 0, nullptr, Y, nullptr, B, M, K, HW, (hipStream_t)stream);
+    return pw_run(0, false, A, X, bias, 0, nullptr, Y, nullptr, B, M, K, HW, stream);
 }
 
 // ppea_pwconv_bf16 plus the statistics of the BatchNorm that follows (conv_bn / conv_bn_relu, rka.py:182-197): per output
@@ -631,9 +621,7 @@ int ppea_pwconv_stats_partials(int B, int M, int K, int HW) {
 }
 int ppea_pwconv_stats_bf16(const void* A, const void* X, const float* bias, void* Y, float* stats, int B, int M, int K,
                            int HW, void* stream) {
-    if (!pw_served(B, M, K, HW, false)) return PPEA_ERR_UNSUPPORTED;
-    if (stats == nullptr) return PPEA_ERR_ARG;
-    return launch_pw<4, false>(A, X, bias, 0, nullptr, Y, stats, B, M, K, HW, (hipStream_t)stream);
+    return pw_run(4, false, A, X, bias, 0, nullptr, Y, stats, B, M, K, HW, stream);
 }
 
 // Host only: what ppea_pwconv_bf16 / _stats_bf16 / _ex_bf16 / _infer_bf16 launch for these arguments, answered by pw_choose
@@ -679,24 +667,7 @@ int ppea_pwconv_plan_sweep(int B, int a_transposed, int Mstep, int nM, int nK, i
 // `bias` is fp32 or, with bias_bf16 != 0, bf16.  a_transposed != 0: A is given as At [K][M] (M % 8 == 0).
 int ppea_pwconv_ex_bf16(const void* A, const void* X, const void* bias, int bias_bf16, int epi, const void* aux,
                         void* Y, void* Y2, int B, int M, int K, int HW, int a_transposed, void* stream) {
-    if (!pw_served(B, M, K, HW, a_transposed != 0)) return PPEA_ERR_UNSUPPORTED;
-    hipStream_t st = (hipStream_t)stream;
-    if (epi == 1 && !Y2) return PPEA_ERR_ARG;
-    if (epi == 2 && !aux) return PPEA_ERR_ARG;
-    if (a_transposed) {
-        switch (epi) {
-            case 0: return launch_pw<0, true>(A, X, bias, bias_bf16, nullptr, Y, nullptr, B, M, K, HW, st);
-            case 1: return launch_pw<1, true>(A, X, bias, bias_bf16, nullptr, Y, Y2, B, M, K, HW, st);
-            case 2: return launch_pw<2, true>(A, X, nullptr, 0, aux, Y, nullptr, B, M, K, HW, st);
-        }
-    } else {
-        switch (epi) {
-            case 0: return launch_pw<0, false>(A, X, bias, bias_bf16, nullptr, Y, nullptr, B, M, K, HW, st);
-            case 1: return launch_pw<1, false>(A, X, bias, bias_bf16, nullptr, Y, Y2, B, M, K, HW, st);
-            case 2: return launch_pw<2, false>(A, X, nullptr, 0, aux, Y, nullptr, B, M, K, HW, st);
-        }
-    }
-    return PPEA_ERR_ARG;
+    return pw_run(epi >= 0 && epi <= 2 ? epi : -1, a_transposed != 0, A, X, bias, bias_bf16, aux, Y, Y2, B, M, K, HW, stream);
 }
 
 // Inference form of the 1x1 conv + BatchNorm (+ activation, residual, adapter add, next block's first BatchNorm) of the
@@ -717,11 +688,9 @@ int ppea_pwconv_infer_bf16(const void* A, const void* X, const float* s, const f
     PwExtra<5> ex;
     ex.v = PwInfer{s, o, (const uint16_t*)r1, (const uint16_t*)r2, r2_scale, s2, o2, act};
     hipStream_t st = (hipStream_t)stream;
-#define PW2I(BM_, BK_) return launch_pw2_t<BM_, BK_, 5>(A, X, nullptr, 0, nullptr, Y, Y2, B, M, K, HW, st, ex)
-    if (c.bm == 128) { if (c.bk == 64) PW2I(128, 64); else PW2I(128, 32); }
-    if (c.bm == 64) { if (c.bk == 64) PW2I(64, 64); else PW2I(64, 32); }
-    PW2I(32, 64);
-#undef PW2I
+    return pw_tile<true>(c, [&](auto bm, auto bk) {
+        return launch_pw2_t<decltype(bm)::value, decltype(bk)::value, 5>(A, X, nullptr, 0, nullptr, Y, Y2, B, M, K, HW, st, ex);
+    });
 }
 
 }  // extern "C"

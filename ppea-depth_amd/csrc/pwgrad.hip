@@ -11,19 +11,31 @@
 //   * split partial results go to a workspace [S][M*N + M] fp32 with plain coalesced stores and are summed
 //     by a second tiny kernel: deterministic, and no cross-XCD atomics;
 //   * the row sums (bias gradients) ride along in the n-tile-0 workgroups.
-#include "common.h"
+#include "gemm_bf16.h"
 #include <cstdlib>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(4))) float f32x4;
 
 constexpr int TM = 128, TN = 128, TK = 64;
 constexpr int STRIDE = 160;                      // bytes per LDS row (128 data + 32 pad)
 
 __device__ __forceinline__ float bf_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
 __device__ __forceinline__ float bf_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
+
+// ---- what the two main kernels share -------------------------------------------------------------------------------
+// the workspace slice of one split: [M][N] partial tile sums, then [M] partial row sums
+__device__ __forceinline__ float* split_slice(float* ws, int split, int M, int N) { return ws + (long)split * ((long)M * N + M); }
+
+// the 8 pixels of one A fragment, added pairwise
+__device__ __forceinline__ float rowsum8(uint4 a) {
+    return (bf_lo(a.x) + bf_hi(a.x)) + (bf_lo(a.y) + bf_hi(a.y)) + (bf_lo(a.z) + bf_hi(a.z)) + (bf_lo(a.w) + bf_hi(a.w));
+}
+
+// the four lane groups hold the other pixels of the row: fixed-order butterfly, the sum in every lane
+__device__ __forceinline__ void rowsum_fold(float& v) {
+    v += __shfl_xor(v, 16, WAVE);
+    v += __shfl_xor(v, 32, WAVE);
+}
 
 __global__ __launch_bounds__(256) void pwgrad_kernel(const uint16_t* __restrict__ P, const uint16_t* __restrict__ Q,
                                                      float* __restrict__ ws, int M, int N, int HW, int spi,
@@ -89,9 +101,7 @@ __global__ __launch_bounds__(256) void pwgrad_kernel(const uint16_t* __restrict_
             for (int j = 0; j < 4; ++j) bu[j] = *reinterpret_cast<const uint4*>(b_frag + j * 16 * STRIDE + h * 64);
             if (do_rs) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    rs[i] += (bf_lo(au[i].x) + bf_hi(au[i].x)) + (bf_lo(au[i].y) + bf_hi(au[i].y)) +
-                             (bf_lo(au[i].z) + bf_hi(au[i].z)) + (bf_lo(au[i].w) + bf_hi(au[i].w));
+                for (int i = 0; i < 4; ++i) rs[i] += rowsum8(au[i]);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -104,7 +114,7 @@ __global__ __launch_bounds__(256) void pwgrad_kernel(const uint16_t* __restrict_
     }
 
     // partial tile -> workspace slice of this split: C layout col = lane & 15 (n), row = 4 * (lane >> 4) + r (m)
-    float* out = ws + (long)split * ((long)M * N + M);
+    float* out = split_slice(ws, split, M, N);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -121,8 +131,7 @@ __global__ __launch_bounds__(256) void pwgrad_kernel(const uint16_t* __restrict_
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float v = rs[i];
-            v += __shfl_xor(v, 16, WAVE);
-            v += __shfl_xor(v, 32, WAVE);
+            rowsum_fold(v);
             const int m = m0 + wm * 64 + 16 * i + li;
             if (g == 0 && m < M) out[(long)M * N + m] = v;
         }
@@ -130,16 +139,13 @@ __global__ __launch_bounds__(256) void pwgrad_kernel(const uint16_t* __restrict_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// v2: the same contraction with a three-stage LDS ring filled by LDS-DMA (`global_load_lds`, 16 bytes per lane), counted
-// `s_waitcnt vmcnt(N)` + ONE raw `s_barrier` per step (two steps in flight across it) -- the pipeline of pwconv v2
-// (pwconv.hip).  Both operand tiles are [128 rows][BK pixels] row-major images read with `ds_read_b128`; LDS-DMA writes
-// wave-uniform base + lane * 16, so the bank swizzle sits on the SOURCE address: slot s of row r holds pixel chunk
-// s ^ ((r >> 1) & 7) (128-byte rows) / s ^ (2 ((r >> 2) & 1)) (64-byte rows).  The MFMA operands are swapped (the
-// accumulator holds the transposed tile): a lane owns 4 consecutive columns n of one row m = one 16-byte slab store.
+// v2: the same contraction on the three-stage LDS-DMA ring of gemm_bf16.h (one raw barrier per step, two steps in flight
+// across it).  Both operand tiles are [128 rows][BK pixels] row-major images read with `ds_read_b128`, swizzled on the
+// SOURCE address by swz16<BK>.  The MFMA operands are swapped (the accumulator holds the transposed tile): a lane owns 4
+// consecutive columns n of one row m = one 16-byte slab store.
 // Requirement: HW % BK == 0 (a step never straddles two images); other shapes stay on v1.
-constexpr int NSTAGE2 = 3;
-
-template <int BK> __device__ __forceinline__ int g_swz16(int row) { return BK == 64 ? ((row >> 1) & 7) : (2 * ((row >> 2) & 1)); }
+constexpr int RING_BK = 32;                                      // the one instantiation the launches use
+constexpr int RING_LDS = NSTAGE * 2 * TM * RING_BK * 2;          // dynamic LDS: per stage two [TM][RING_BK] bf16 tiles
 
 template <int BK>
 __device__ __forceinline__ void pwgrad2_body(const uint16_t* __restrict__ P, const uint16_t* __restrict__ Q,
@@ -162,16 +168,11 @@ __device__ __forceinline__ void pwgrad2_body(const uint16_t* __restrict__ P, con
     for (int c = 0; c < INS; ++c) {
         const int t = c * 4 + wave;
         const int row = t * (1024 / RB) + lane / (RB / 16), slot = lane % (RB / 16);
-        const int chunk = slot ^ g_swz16<BK>(row);
+        const int chunk = slot ^ swz16<BK>(row);
         p_src[c] = P + (long)min(m0 + row, M - 1) * HW + 8 * chunk;          // rows past M / N: any valid row (not stored)
         q_src[c] = Q + (long)min(n0 + row, N - 1) * HW + 8 * chunk;
     }
-    const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
-    auto glds16 = [&](const uint16_t* src, unsigned dst) {
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
-    };
+    const unsigned lds_base = lds_address(lds);
     auto issue = [&](int step, int stage) {
         const int b = step / spi, p0 = (step - b * spi) * BK;
         const long po = (long)b * M * HW + p0, qo = (long)b * N * HW + p0;
@@ -196,8 +197,8 @@ __device__ __forceinline__ void pwgrad2_body(const uint16_t* __restrict__ P, con
 #pragma unroll
         for (int h = 0; h < KH; ++h) {
             const int ra = wm * 64 + 16 * i + li, rb = wn * 64 + 16 * i + li;
-            a_off[i][h] = ra * RB + 16 * ((4 * h + g) ^ g_swz16<BK>(ra));
-            b_off[i][h] = TILE + rb * RB + 16 * ((4 * h + g) ^ g_swz16<BK>(rb));
+            a_off[i][h] = ra * RB + 16 * ((4 * h + g) ^ swz16<BK>(ra));
+            b_off[i][h] = TILE + rb * RB + 16 * ((4 * h + g) ^ swz16<BK>(rb));
         }
     const bool do_rs = rowsum_tile && wn == 0;
 
@@ -206,10 +207,8 @@ __device__ __forceinline__ void pwgrad2_body(const uint16_t* __restrict__ P, con
     if (nsteps > 1) issue(s_begin + 1, 1);
     int cur = 0;
     for (int k = 0; k < nsteps; ++k) {
-        if (k + 1 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LPS) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        if (k + 2 < nsteps) issue(s_begin + k + 2, cur >= 1 ? cur - 1 : NSTAGE2 - 1);
+        ring_wait<LPS>(k + 1 < nsteps);
+        if (k + 2 < nsteps) issue(s_begin + k + 2, ring_refill(cur));
         const uint8_t* buf = lds + cur * STAGE;
 #pragma unroll
         for (int h = 0; h < KH; ++h) {
@@ -220,9 +219,7 @@ __device__ __forceinline__ void pwgrad2_body(const uint16_t* __restrict__ P, con
             for (int j = 0; j < 4; ++j) bu[j] = *reinterpret_cast<const uint4*>(buf + b_off[j][h]);
             if (do_rs) {
 #pragma unroll
-                for (int i = 0; i < 4; ++i)
-                    rs[i] += (bf_lo(au[i].x) + bf_hi(au[i].x)) + (bf_lo(au[i].y) + bf_hi(au[i].y)) +
-                             (bf_lo(au[i].z) + bf_hi(au[i].z)) + (bf_lo(au[i].w) + bf_hi(au[i].w));
+                for (int i = 0; i < 4; ++i) rs[i] += rowsum8(au[i]);
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i)
@@ -232,11 +229,11 @@ __device__ __forceinline__ void pwgrad2_body(const uint16_t* __restrict__ P, con
                                                                         __builtin_bit_cast(bf16x8, au[i]), acc[i][j],
                                                                         0, 0, 0);
         }
-        cur = cur == NSTAGE2 - 1 ? 0 : cur + 1;
+        cur = ring_next(cur);
     }
 
     // transposed C layout: col = lane & 15 = row m of the result, rows 4 g + r = 4 consecutive columns n
-    float* out = ws + (long)split * ((long)M * N + M);
+    float* out = split_slice(ws, split, M, N);
     const bool vec = (N & 3) == 0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -260,8 +257,7 @@ __device__ __forceinline__ void pwgrad2_body(const uint16_t* __restrict__ P, con
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             float v = rs[i];
-            v += __shfl_xor(v, 16, WAVE);
-            v += __shfl_xor(v, 32, WAVE);
+            rowsum_fold(v);
             const int m = m0 + wm * 64 + 16 * i + li;
             if (g == 0 && m < M) out[(long)M * N + m] = v;
         }
@@ -291,26 +287,8 @@ __global__ __launch_bounds__(256) void pwgrad2_pair_kernel(PwgProb a, PwgProb b,
                      ni * TN);
 }
 
-// out[i] = sum_s ws[s * pitch + i], i < len.  Block = 32 columns x 8 split groups, combined through LDS.
-__global__ __launch_bounds__(256) void pwgrad_reduce_kernel(const float* __restrict__ ws, float* __restrict__ out,
-                                                            long len, long pitch, int S) {
-    __shared__ float part[8][33];
-    const int x = threadIdx.x & 31, y = threadIdx.x >> 5;
-    const long i = (long)blockIdx.x * 32 + x;
-    float v = 0.f;
-    if (i < len)
-        for (int s = y; s < S; s += 8) v += ws[(long)s * pitch + i];
-    part[y][x] = v;
-    __syncthreads();
-    if (y == 0 && i < len) {
-        float t = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t += part[k][x];
-        out[i] = t;
-    }
-}
-
-// Same reduction, written straight into the parameter gradients: weights as fp32 or bf16, either [M][N] or,
+// The split sum, out[i] = sum_s ws[s * pitch + i] (block = 32 columns x 8 split groups, combined through LDS in a fixed
+// order), written straight into the parameter gradients: weights as fp32 or bf16, either [M][N] or,
 // for the tap-major 3x3 form (taps = 9, M = 9 * Ch rows t * Ch + m), in nn.Conv2d layout [Ch][N][3][3];
 // bias = row sums of rows [b_row0, b_row0 + b_rows).
 struct PwgOut { const float* ws; long pitch; int M, N, taps; void* out_w; int w_bf16; void* out_b; int b_bf16, b_row0, b_rows; };
@@ -341,12 +319,12 @@ __device__ __forceinline__ void pwgrad_reduce_ex_body(const PwgOut& o_, int S, l
             const int Ch = M / taps, tp = m / Ch, mo = m - tp * Ch;
             o = ((long)mo * N + n) * taps + tp;
         }
-        if (w_bf16) reinterpret_cast<uint16_t*>(out_w)[o] = __builtin_bit_cast(uint16_t, (__bf16)t);
+        if (w_bf16) reinterpret_cast<uint16_t*>(out_w)[o] = f2bf(t);
         else reinterpret_cast<float*>(out_w)[o] = t;
     } else if (out_b != nullptr) {
         const int r = (int)(i - (long)M * N) - b_row0;
         if (r >= 0 && r < b_rows) {
-            if (b_bf16) reinterpret_cast<uint16_t*>(out_b)[r] = __builtin_bit_cast(uint16_t, (__bf16)t);
+            if (b_bf16) reinterpret_cast<uint16_t*>(out_b)[r] = f2bf(t);
             else reinterpret_cast<float*>(out_b)[r] = t;
         }
     }
@@ -370,35 +348,54 @@ int pwgrad_bk(int HW) {
     return (HW % 32) == 0 ? 32 : 0;
 }
 
-void plan(int B, int M, int N, int HW, int& spi, int& total, int& sps, int& S) {
-    const int bk = pwgrad_bk(HW);
-    const int tk = bk ? bk : TK;
-    spi = (HW + tk - 1) / tk;
-    total = B * spi;
-    const int tiles = ((M + TM - 1) / TM) * ((N + TN - 1) / TN);
-    // enough work items to fill the chip once, but every split writes (and the reduce kernel re-reads) a full fp32 copy
-    // of the result: v2's deeper pipeline needs fewer, longer items
-    int want = ((bk ? 288 : 384) + tiles - 1) / tiles;
-    const int min_steps = bk ? 8 : 4;
-    if (want > (total + min_steps - 1) / min_steps) want = (total + min_steps - 1) / min_steps;
+int tiles_of(int M, int N) { return ((M + TM - 1) / TM) * ((N + TN - 1) / TN); }
+
+// B * spi steps over `tiles` tiles -> steps per split and the number of splits S: enough work items (want_items) to fill the
+// chip once, but every split writes (and the reduce kernel re-reads) a full fp32 copy of the result, so no item is shorter
+// than min_steps
+struct Split { int spi, total, sps, S; };       // steps per image, steps in all, steps per split, splits
+Split split_plan(int tiles, int spi, int B, int want_items, int min_steps) {
+    Split s{spi, B * spi, 0, 0};
+    int want = (want_items + tiles - 1) / tiles;
+    if (want > (s.total + min_steps - 1) / min_steps) want = (s.total + min_steps - 1) / min_steps;
     if (want < 1) want = 1;
-    sps = (total + want - 1) / want;
-    S = (total + sps - 1) / sps;
+    s.sps = (s.total + want - 1) / want;
+    s.S = (s.total + s.sps - 1) / s.sps;
+    return s;
+}
+Split plan(int B, int M, int N, int HW) {
+    const int bk = pwgrad_bk(HW), tk = bk ? bk : TK;
+    return split_plan(tiles_of(M, N), (HW + tk - 1) / tk, B, bk ? 288 : 384, bk ? 8 : 4);   // v2's deeper pipeline: fewer, longer items
+}
+// the pair form (v2 only): the tiles of both problems share the splits
+int pair_tiles(const int* M, const int* N) { return tiles_of(M[0], N[0]) + tiles_of(M[1], N[1]); }
+Split pair_plan(int B, const int* M, const int* N, int HW) { return split_plan(pair_tiles(M, N), HW / RING_BK, B, 288, 8); }
+
+// out[0..8] of the plan queries
+void plan_out(int* out, int bk, const Split& s, int t0, int t1, long bytes) {
+    out[0] = bk; out[1] = s.spi; out[2] = s.total; out[3] = s.sps; out[4] = s.S; out[5] = t0; out[6] = t1;
+    out[7] = (int)(bytes & 0x7fffffffL); out[8] = (int)(bytes >> 31);
 }
 
-int launch_main(const void* P, const void* Q, void* workspace, int B, int M, int N, int HW, int want_rowsum, hipStream_t st) {
-    int spi, total, sps, S;
-    plan(B, M, N, HW, spi, total, sps, S);
-    dim3 grid(S, (M + TM - 1) / TM, (N + TN - 1) / TN);
+// One problem: the GEMM into the split workspace, then the split sum into the outputs (out_b NULL: no row sums).
+int run(const void* P, const void* Q, void* workspace, int B, int M, int N, int HW, void* out_w, int w_bf16, int taps, void* out_b,
+        int b_bf16, int b_row0, int b_rows, hipStream_t st) {
+    const Split s = plan(B, M, N, HW);
+    dim3 grid(s.S, (M + TM - 1) / TM, (N + TN - 1) / TN);
     if (grid.y > 65535 || grid.z > 65535) return PPEA_ERR_UNSUPPORTED;
-    if (pwgrad_bk(HW) == 32) {
-        constexpr int smem = NSTAGE2 * 2 * TM * 64;
-        hipLaunchKernelGGL(pwgrad2_kernel<32>, grid, dim3(256), smem, st, (const uint16_t*)P, (const uint16_t*)Q,
-                           (float*)workspace, M, N, HW, spi, total, sps, want_rowsum);
+    const int want_rowsum = out_b != nullptr ? 1 : 0;
+    if (pwgrad_bk(HW) == RING_BK) {
+        hipLaunchKernelGGL(pwgrad2_kernel<RING_BK>, grid, dim3(256), RING_LDS, st, (const uint16_t*)P, (const uint16_t*)Q,
+                           (float*)workspace, M, N, HW, s.spi, s.total, s.sps, want_rowsum);
     } else {
         hipLaunchKernelGGL(pwgrad_kernel, grid, dim3(256), 0, st, (const uint16_t*)P, (const uint16_t*)Q,
-                           (float*)workspace, M, N, HW, spi, total, sps, want_rowsum);
+                           (float*)workspace, M, N, HW, s.spi, s.total, s.sps, want_rowsum);
     }
+    const int err = launch_status();
+    if (err != 0) return err;
+    const long pitch = (long)M * N + M, len = out_b != nullptr ? pitch : (long)M * N;
+    hipLaunchKernelGGL(pwgrad_reduce_ex_kernel, dim3((unsigned)((len + 31) / 32)), dim3(256), 0, st,
+                       (const float*)workspace, pitch, s.S, M, N, taps, out_w, w_bf16, out_b, b_bf16, b_row0, b_rows);
     return launch_status();
 }
 
@@ -407,26 +404,14 @@ int launch_main(const void* P, const void* Q, void* workspace, int B, int M, int
 extern "C" {
 
 // Bytes of workspace ppea_pwgrad_bf16 needs for these shapes.
-long ppea_pwgrad_workspace_bytes(int B, int M, int N, int HW) {
-    int spi, total, sps, S;
-    plan(B, M, N, HW, spi, total, sps, S);
-    return (long)S * ((long)M * N + M) * 4;
-}
+long ppea_pwgrad_workspace_bytes(int B, int M, int N, int HW) { return (long)plan(B, M, N, HW).S * ((long)M * N + M) * 4; }
 
 // out [M*N + M] fp32: C row-major followed by the row sums of P (written only when want_rowsum != 0).
-// P [B][M][HW], Q [B][N][HW] bf16; HW % 8 == 0.
+// P [B][M][HW], Q [B][N][HW] bf16; HW % 8 == 0.  The fp32, taps = 1 case of ppea_pwgrad_ex_bf16 with the bias window [0, M).
 int ppea_pwgrad_bf16(const void* P, const void* Q, float* out, void* workspace, int B, int M, int N, int HW,
                      int want_rowsum, void* stream) {
     if (B <= 0 || M <= 0 || N <= 0 || HW <= 0 || (HW % 8) != 0) return PPEA_ERR_UNSUPPORTED;
-    int spi, total, sps, S;
-    plan(B, M, N, HW, spi, total, sps, S);
-    hipStream_t st = (hipStream_t)stream;
-    const int err = launch_main(P, Q, workspace, B, M, N, HW, want_rowsum, st);
-    if (err != 0) return err;
-    const long len = (long)M * N + (want_rowsum ? M : 0), pitch = (long)M * N + M;
-    hipLaunchKernelGGL(pwgrad_reduce_kernel, dim3((unsigned)((len + 31) / 32)), dim3(256), 0, st,
-                       (const float*)workspace, out, len, pitch, S);
-    return launch_status();
+    return run(P, Q, workspace, B, M, N, HW, out, 0, 1, want_rowsum ? out + (long)M * N : nullptr, 0, 0, M, (hipStream_t)stream);
 }
 
 // As ppea_pwgrad_bf16, results written straight into the parameter gradients (see pwgrad_reduce_ex_kernel).
@@ -435,68 +420,45 @@ int ppea_pwgrad_ex_bf16(const void* P, const void* Q, void* workspace, int B, in
     if (B <= 0 || M <= 0 || N <= 0 || HW <= 0 || (HW % 8) != 0 || taps < 1 || (M % taps) != 0)
         return PPEA_ERR_UNSUPPORTED;
     if (out_w == nullptr || (out_b != nullptr && (b_row0 < 0 || b_row0 + b_rows > M))) return PPEA_ERR_ARG;
-    int spi, total, sps, S;
-    plan(B, M, N, HW, spi, total, sps, S);
-    hipStream_t st = (hipStream_t)stream;
-    const int err = launch_main(P, Q, workspace, B, M, N, HW, out_b != nullptr ? 1 : 0, st);
-    if (err != 0) return err;
-    const long pitch = (long)M * N + M;
-    const long len = out_b != nullptr ? pitch : (long)M * N;
-    hipLaunchKernelGGL(pwgrad_reduce_ex_kernel, dim3((unsigned)((len + 31) / 32)), dim3(256), 0, st,
-                       (const float*)workspace, pitch, S, M, N, taps, out_w, out_w_bf16, out_b, out_b_bf16, b_row0,
-                       b_rows);
-    return launch_status();
+    return run(P, Q, workspace, B, M, N, HW, out_w, out_w_bf16, taps, out_b, out_b_bf16, b_row0, b_rows, (hipStream_t)stream);
 }
-
 
 // Two ppea_pwgrad_ex_bf16 problems over the same [B][.][HW] pixels in one GEMM launch and one reduce launch (an adapter's
 // two weight gradients).  Arrays of two: P, Q, M, N, out_w, out_w_bf16, taps, out_b, out_b_bf16, b_row0, b_rows; workspace
 // of ppea_pwgrad_pair_workspace_bytes (-1: not served).  PPEA_ERR_UNSUPPORTED (HW % 32 != 0 ...): call the single form twice.
-static void pair_plan(int B, const int* M, const int* N, int HW, int& tiles, int& spi, int& total, int& sps, int& S) {
-    tiles = ((M[0] + TM - 1) / TM) * ((N[0] + TN - 1) / TN) + ((M[1] + TM - 1) / TM) * ((N[1] + TN - 1) / TN);
-    spi = HW / 32;
-    total = B * spi;
-    int want = (288 + tiles - 1) / tiles;
-    if (want > (total + 7) / 8) want = (total + 7) / 8;
-    if (want < 1) want = 1;
-    sps = (total + want - 1) / want;
-    S = (total + sps - 1) / sps;
-}
 long ppea_pwgrad_pair_workspace_bytes(int B, const int* M, const int* N, int HW) {
-    if (B <= 0 || HW <= 0 || pwgrad_bk(HW) != 32 || M[0] <= 0 || M[1] <= 0 || N[0] <= 0 || N[1] <= 0) return -1;
-    int tiles, spi, total, sps, S;
-    pair_plan(B, M, N, HW, tiles, spi, total, sps, S);
-    return (long)S * ((long)M[0] * N[0] + M[0] + (long)M[1] * N[1] + M[1]) * 4;
+    if (B <= 0 || HW <= 0 || pwgrad_bk(HW) != RING_BK || M[0] <= 0 || M[1] <= 0 || N[0] <= 0 || N[1] <= 0) return -1;
+    return (long)pair_plan(B, M, N, HW).S * ((long)M[0] * N[0] + M[0] + (long)M[1] * N[1] + M[1]) * 4;
 }
 int ppea_pwgrad_ex_pair_bf16(const void* const* P, const void* const* Q, void* workspace, int B, const int* M, const int* N,
                              int HW, void* const* out_w, const int* out_w_bf16, const int* taps, void* const* out_b,
                              const int* out_b_bf16, const int* b_row0, const int* b_rows, void* stream) {
-    if (B <= 0 || HW <= 0 || pwgrad_bk(HW) != 32) return PPEA_ERR_UNSUPPORTED;
+    if (B <= 0 || HW <= 0 || pwgrad_bk(HW) != RING_BK) return PPEA_ERR_UNSUPPORTED;
     if (workspace == nullptr) return PPEA_ERR_ARG;
     for (int k = 0; k < 2; ++k) {
         if (P[k] == nullptr || Q[k] == nullptr) return PPEA_ERR_ARG;
         if (M[k] <= 0 || N[k] <= 0 || taps[k] < 1 || (M[k] % taps[k]) != 0) return PPEA_ERR_UNSUPPORTED;
         if (out_w[k] == nullptr || (out_b[k] != nullptr && (b_row0[k] < 0 || b_row0[k] + b_rows[k] > M[k]))) return PPEA_ERR_ARG;
     }
-    int tiles, spi, total, sps, S;
-    pair_plan(B, M, N, HW, tiles, spi, total, sps, S);
+    const Split s = pair_plan(B, M, N, HW);
+    const int tiles = pair_tiles(M, N);
     if (tiles > 65535) return PPEA_ERR_UNSUPPORTED;
-    const int mt0 = (M[0] + TM - 1) / TM, nt0 = (N[0] + TN - 1) / TN, mt1 = (M[1] + TM - 1) / TM;
+    const int mt0 = (M[0] + TM - 1) / TM, mt1 = (M[1] + TM - 1) / TM;
     const long pitch0 = (long)M[0] * N[0] + M[0], pitch1 = (long)M[1] * N[1] + M[1];
     float* ws0 = (float*)workspace;
-    float* ws1 = ws0 + (long)S * pitch0;
+    float* ws1 = ws0 + (long)s.S * pitch0;
     hipStream_t st = (hipStream_t)stream;
-    constexpr int smem = NSTAGE2 * 2 * TM * 64;
     const PwgProb a{(const uint16_t*)P[0], (const uint16_t*)Q[0], ws0, M[0], N[0], out_b[0] != nullptr ? 1 : 0, mt0};
     const PwgProb b{(const uint16_t*)P[1], (const uint16_t*)Q[1], ws1, M[1], N[1], out_b[1] != nullptr ? 1 : 0, mt1};
-    hipLaunchKernelGGL(pwgrad2_pair_kernel<32>, dim3(S, tiles, 1), dim3(256), smem, st, a, b, mt0 * nt0, HW, spi, total, sps);
+    hipLaunchKernelGGL(pwgrad2_pair_kernel<RING_BK>, dim3(s.S, tiles, 1), dim3(256), RING_LDS, st, a, b, tiles_of(M[0], N[0]), HW, s.spi,
+                       s.total, s.sps);
     const int err = launch_status();
     if (err != 0) return err;
     const long len0 = out_b[0] != nullptr ? pitch0 : (long)M[0] * N[0], len1 = out_b[1] != nullptr ? pitch1 : (long)M[1] * N[1];
     const int nb0 = (int)((len0 + 31) / 32), nb1 = (int)((len1 + 31) / 32);
     const PwgOut oa{ws0, pitch0, M[0], N[0], taps[0], out_w[0], out_w_bf16[0], out_b[0], out_b_bf16[0], b_row0[0], b_rows[0]};
     const PwgOut ob{ws1, pitch1, M[1], N[1], taps[1], out_w[1], out_w_bf16[1], out_b[1], out_b_bf16[1], b_row0[1], b_rows[1]};
-    hipLaunchKernelGGL(pwgrad_reduce_ex2_kernel, dim3((unsigned)(nb0 + nb1)), dim3(256), 0, st, oa, ob, S, nb0);
+    hipLaunchKernelGGL(pwgrad_reduce_ex2_kernel, dim3((unsigned)(nb0 + nb1)), dim3(256), 0, st, oa, ob, s.S, nb0);
     return launch_status();
 }
 
@@ -507,27 +469,18 @@ int ppea_pwgrad_ex_pair_bf16(const void* const* P, const void* const* Q, void* w
 int ppea_pwgrad_plan(int B, int M, int N, int HW, int* out) {
     if (out == nullptr) return PPEA_ERR_ARG;
     if (B <= 0 || M <= 0 || N <= 0 || HW <= 0 || (HW % 8) != 0) return PPEA_ERR_UNSUPPORTED;
-    int spi, total, sps, S;
-    plan(B, M, N, HW, spi, total, sps, S);
     const int mt = (M + TM - 1) / TM, nt = (N + TN - 1) / TN;
     if (mt > 65535 || nt > 65535) return PPEA_ERR_UNSUPPORTED;
-    const long bytes = ppea_pwgrad_workspace_bytes(B, M, N, HW);
-    out[0] = pwgrad_bk(HW); out[1] = spi; out[2] = total; out[3] = sps; out[4] = S; out[5] = mt; out[6] = nt;
-    out[7] = (int)(bytes & 0x7fffffffL); out[8] = (int)(bytes >> 31);
+    plan_out(out, pwgrad_bk(HW), plan(B, M, N, HW), mt, nt, ppea_pwgrad_workspace_bytes(B, M, N, HW));
     return 0;
 }
 
 // The same for ppea_pwgrad_ex_pair_bf16 (pair_plan()): out[5], out[6] = tiles of problem 0 and of problem 1.
 int ppea_pwgrad_pair_plan(int B, const int* M, const int* N, int HW, int* out) {
     if (out == nullptr || M == nullptr || N == nullptr) return PPEA_ERR_ARG;
-    if (B <= 0 || HW <= 0 || pwgrad_bk(HW) != 32 || M[0] <= 0 || M[1] <= 0 || N[0] <= 0 || N[1] <= 0) return PPEA_ERR_UNSUPPORTED;
-    int tiles, spi, total, sps, S;
-    pair_plan(B, M, N, HW, tiles, spi, total, sps, S);
-    if (tiles > 65535) return PPEA_ERR_UNSUPPORTED;
-    const long bytes = ppea_pwgrad_pair_workspace_bytes(B, M, N, HW);
-    out[0] = 32; out[1] = spi; out[2] = total; out[3] = sps; out[4] = S;
-    out[5] = ((M[0] + TM - 1) / TM) * ((N[0] + TN - 1) / TN); out[6] = tiles - out[5];
-    out[7] = (int)(bytes & 0x7fffffffL); out[8] = (int)(bytes >> 31);
+    if (B <= 0 || HW <= 0 || pwgrad_bk(HW) != RING_BK || M[0] <= 0 || M[1] <= 0 || N[0] <= 0 || N[1] <= 0) return PPEA_ERR_UNSUPPORTED;
+    if (pair_tiles(M, N) > 65535) return PPEA_ERR_UNSUPPORTED;
+    plan_out(out, RING_BK, pair_plan(B, M, N, HW), tiles_of(M[0], N[0]), tiles_of(M[1], N[1]), ppea_pwgrad_pair_workspace_bytes(B, M, N, HW));
     return 0;
 }
 

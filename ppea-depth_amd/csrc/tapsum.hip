@@ -11,10 +11,6 @@
 
 namespace {
 
-__device__ __forceinline__ float bf2f(uint16_t v) { return __builtin_bit_cast(float, (uint32_t)v << 16); }
-__device__ __forceinline__ uint16_t f2bf(float v) { return __builtin_bit_cast(uint16_t, (__bf16)v); }
-__device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.f + erff(x * 0.70710678118654752f)); }
-
 struct Px4 { uint16_t v[4]; };
 
 __device__ __forceinline__ Px4 ld4(const uint16_t* p) {

@@ -1949,25 +1949,35 @@ def pwconv_raw(a_mat, x, bias=None):
     return y if served else None
 
 
+def _pw_forward(a, x, want_sums):
+    """pwconv_raw(a, x), or with want_sums (y, sums [M, P, 2]): the epilogue also leaves per-channel partial sums of the
+    stored output, so the BatchNorm that follows needs no statistics pass (batchnorm.fused_bn_act(..., sums=...))."""
+    if not want_sums:
+        return pwconv_raw(a, x)
+    B, K, H, W = x.shape
+    M = a.shape[0]
+    y = torch.empty(B, M, H, W, device=x.device, dtype=_BF16)
+    P = _abi.lib.ppea_pwconv_stats_partials(B, M, K, H * W)
+    sums = torch.empty(M, P, 2, device=x.device, dtype=_F32)
+    call("ppea_pwconv_stats_bf16", ptr(a, _BF16), ptr(x, _BF16), None, ptr(y), ptr(sums), B, M, K, H * W, stream_ptr())
+    return y, sums
+
+
+def _pw_gate(x, w):
+    """The shapes the 1x1 GEMM serves for a weight [Cout, Cin, 1, 1]."""
+    B, K, H, W = x.shape
+    return x.dtype == _BF16 and x.is_cuda and K % 32 == 0 and w.shape[0] % 32 == 0 and (H * W) % 8 == 0
+
+
 class _PwConvFrozen(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, want_sums=False):
-        a, at = _pw_matrices(w)
-        ctx.at = at
-        x = x.contiguous()
-        if not want_sums:
-            return pwconv_raw(a, x)
-        # the epilogue also leaves per-channel partial sums of the stored output: the BatchNorm that follows needs no
-        # statistics pass (batchnorm.fused_bn_act(..., sums=...))
-        B, K, H, W = x.shape
-        M = a.shape[0]
-        y = torch.empty(B, M, H, W, device=x.device, dtype=_BF16)
-        P = _abi.lib.ppea_pwconv_stats_partials(B, M, K, H * W)
-        sums = torch.empty(M, P, 2, device=x.device, dtype=_F32)
-        call("ppea_pwconv_stats_bf16", ptr(a, _BF16), ptr(x, _BF16), None, ptr(y), ptr(sums), B, M, K, H * W, stream_ptr())
-        ctx.mark_non_differentiable(sums)
-        ctx.set_materialize_grads(False)
-        return y, sums
+        a, ctx.at = _pw_matrices(w)
+        out = _pw_forward(a, x.contiguous(), want_sums)
+        if want_sums:
+            ctx.mark_non_differentiable(out[1])
+            ctx.set_materialize_grads(False)
+        return out
 
     @staticmethod
     def backward(ctx, dy, _dsums=None):
@@ -1978,13 +1988,9 @@ def pwconv_frozen(x, w, want_sums=False):
     """1x1 conv with a frozen weight [Cout,Cin,1,1] on the MFMA kernel; None when the shape is not served
     (caller falls back to the library conv).  want_sums: -> (y, sums [Cout, P, 2]) with the per-channel partial
     (sum, sum of squares) of y for the BatchNorm that follows."""
-    B, K, H, W = x.shape
-    if (x.dtype != _BF16 or not x.is_cuda or K % 32 != 0 or w.shape[0] % 32 != 0 or (H * W) % 8 != 0
-            or w.requires_grad):
+    if not _pw_gate(x, w) or w.requires_grad:
         return None
-    if want_sums:
-        return _PwConvFrozen.apply(x, w, True)
-    return _PwConvFrozen.apply(x, w)
+    return _PwConvFrozen.apply(x, w, True) if want_sums else _PwConvFrozen.apply(x, w)
 
 
 class _PwConvTrainable(torch.autograd.Function):
@@ -1995,22 +2001,16 @@ class _PwConvTrainable(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, want_sums=False):
-        M, K = w.shape[0], w.shape[1]
-        a = w.detach().reshape(M, K)
+        a = w.detach().reshape(w.shape[0], w.shape[1])
         a = a if a.dtype == _BF16 and a.is_contiguous() else a.to(_BF16).contiguous()
         x = x.contiguous()
         ctx.save_for_backward(x, a)
         ctx.w_meta = (w.shape, _grad_dtype(w))
-        if not want_sums:
-            return pwconv_raw(a, x)
-        B, _, H, W = x.shape
-        y = torch.empty(B, M, H, W, device=x.device, dtype=_BF16)
-        P = _abi.lib.ppea_pwconv_stats_partials(B, M, K, H * W)
-        sums = torch.empty(M, P, 2, device=x.device, dtype=_F32)
-        call("ppea_pwconv_stats_bf16", ptr(a, _BF16), ptr(x, _BF16), None, ptr(y), ptr(sums), B, M, K, H * W, stream_ptr())
-        ctx.mark_non_differentiable(sums)
-        ctx.set_materialize_grads(False)
-        return y, sums
+        out = _pw_forward(a, x, want_sums)
+        if want_sums:
+            ctx.mark_non_differentiable(out[1])
+            ctx.set_materialize_grads(False)
+        return out
 
     @staticmethod
     def backward(ctx, dy, _dsums=None):
@@ -2024,13 +2024,9 @@ class _PwConvTrainable(torch.autograd.Function):
 def pwconv_trainable(x, w, want_sums=False):
     """pwconv_frozen for a weight that takes a gradient: same shape conditions (None when the GEMM does not serve them:
     the caller keeps ops.Conv2d), same forward arithmetic, and x.grad / w.grad from the bf16 GEMM kernels."""
-    B, K, H, W = x.shape
-    if (x.dtype != _BF16 or not x.is_cuda or K % 32 != 0 or w.shape[0] % 32 != 0 or (H * W) % 8 != 0
-            or w.dim() != 4 or w.shape[2:] != (1, 1)):
+    if not _pw_gate(x, w) or w.dim() != 4 or w.shape[2:] != (1, 1):
         return None
-    if want_sums:
-        return _PwConvTrainable.apply(x, w, True)
-    return _PwConvTrainable.apply(x, w)
+    return _PwConvTrainable.apply(x, w, True) if want_sums else _PwConvTrainable.apply(x, w)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1,43 +1,25 @@
 """Every instantiation of the pointwise GEMM family an exported entry point can launch -- csrc/pwconv.hip (v1 and the v2 LDS-DMA
-ring, both A modes, every tile and epilogue), csrc/pwgrad.hip (both main kernels, the pair form, the three reduce kernels) and
+ring, both A modes, every tile and epilogue), csrc/pwgrad.hip (both main kernels, the pair form, the two reduce kernels) and
 csrc/tapsum.hip -- against the float64 references of oracle/pw_inputs.py, element by element, each element held to the bound
 derived there.  Outputs (and the split workspace and the statistics partials) are NaN-filled views into guarded buffers: an
 element never stored is outside its bound, a store past either end changes a guard.  Every row asserts that the entry point
 served it exactly when the library's plan query has a plan for it; a failure names the arm from that query on the launch's own
 arguments (tests/test_pw_arms_cpu.py proves that the plan names the arm the row is there for, the references, the bounds, and
 that the bounds catch index faults).  Hook rows set their variables for the one call; the hooks are read per call."""
-import ctypes
-
 import pytest
 import torch
 
+import pw_launch as L
 from oracle import pw_inputs as P
+from pw_launch import hooks as _hooks, to as _to
 
 pytestmark = pytest.mark.gpu
 
 BF16, F32 = torch.bfloat16, torch.float32
-HOOKS = ("PPEA_PW_TILE", "PPEA_PW_V2", "PPEA_PWGRAD_V2")
 
 
 def _ids(rows):
     return [r.name for r in rows]
-
-
-class _hooks:
-    """The row's hook variables for the calls inside, removed after."""
-
-    def __init__(self, monkeypatch, env):
-        self.mp, self.env = monkeypatch, env
-
-    def __enter__(self):
-        for k in HOOKS:
-            self.mp.delenv(k, raising=False)
-        for k, v in self.env.items():
-            self.mp.setenv(k, v)
-
-    def __exit__(self, *exc):
-        for k in self.env:
-            self.mp.delenv(k, raising=False)
 
 
 def _hold(tag, arm, got, ref, bufs=()):
@@ -52,10 +34,6 @@ def _hold(tag, arm, got, ref, bufs=()):
         assert P.guards_intact(buf, dtype), f"{tag} ({arm}): a guard element was overwritten"
 
 
-def _to(inp, device):
-    return {k: (v.to(device) if torch.is_tensor(v) else v) for k, v in inp.items()}
-
-
 def _bits(t):
     return t.contiguous().view(torch.int16 if t.dtype == BF16 else torch.int32)
 
@@ -63,39 +41,12 @@ def _bits(t):
 # ---------------------------------------------------------------------------------------------
 # pwconv
 # ---------------------------------------------------------------------------------------------
-def _launch_pw(ops, c, inp, plan):
-    """One row through its entry point into guarded outputs -> (served, outputs, guarded buffers)."""
-    dev = inp["x"].device
-    shape = (c.B, c.M, 1, c.HW)
-    ptr, st = ops.ptr, ops.stream_ptr()
-    buf, y = P.guarded(shape, BF16, dev)
-    bufs, out = [(buf, BF16)], dict(y=y)
-    bp, bflag = ops._bias_arg(inp["bias"])
-    if c.epi == 4:
-        Pn = plan["partials"] if plan else 1
-        buf, sums = P.guarded((c.M, Pn, 2), F32, dev)
-        bufs.append((buf, F32))
-        out["sums"] = sums
-        served = ops.try_call("ppea_pwconv_stats_bf16", ptr(inp["a_arg"]), ptr(inp["x"]), bp, ptr(y), ptr(sums), c.B, c.M, c.K, c.HW, st)
-    elif c.epi == 0 and not c.ta and not bflag:
-        served = ops.try_call("ppea_pwconv_bf16", ptr(inp["a_arg"]), ptr(inp["x"]), bp, ptr(y), c.B, c.M, c.K, c.HW, st)
-    else:
-        y2 = None
-        if c.epi == 1:
-            buf, y2 = P.guarded(shape, BF16, dev)
-            bufs.append((buf, BF16))
-            out["y2"] = y2
-        served = ops.try_call("ppea_pwconv_ex_bf16", ptr(inp["a_arg"]), ptr(inp["x"]), bp, bflag, c.epi, ptr(inp["aux"]), ptr(y), ptr(y2),
-                              c.B, c.M, c.K, c.HW, int(c.ta), st)
-    return served, out, bufs
-
-
 def _pw_row(device, monkeypatch, c):
     from ppeadepth import _abi, ops
     inp = _to(P.make_pw_inputs(c), device)
     with _hooks(monkeypatch, c.env):
         plan = ops.pwconv_plan(c.B, c.M, c.K, c.HW, c.ta)
-        served, got, bufs = _launch_pw(ops, c, inp, plan)
+        served, got, bufs = L.launch_pw(ops, c, inp, plan)
         torch.cuda.synchronize()
         if c.epi == 4:
             assert _abi.lib.ppea_pwconv_stats_partials(c.B, c.M, c.K, c.HW) == plan["partials"]
@@ -117,8 +68,7 @@ def _infer_row(device, monkeypatch, c):
     inp = _to(P.make_pw_inputs(c), device)
     with _hooks(monkeypatch, c.env):
         plan = ops.pwconv_plan(c.B, c.M, c.K, c.HW, False)
-        out = ops.pwconv_table(inp["x"], inp["a"], torch.stack([inp["s"], inp["o"]]), inp["act"], inp["r1"], inp["r2"], inp["r2_scale"],
-                               torch.stack([inp["s2"], inp["o2"]]))
+        out = L.launch_infer(ops, inp)
         torch.cuda.synchronize()
     arm = P.arm_of_plan(plan, False, 5)
     assert out is not None and arm == c.arm, (arm, c.arm)
@@ -182,7 +132,7 @@ def test_unsupported_pwconv_shapes_are_refused_and_nothing_is_written(device, c)
     inp["a_arg"] = torch.randn((c.K, c.M) if c.ta else (c.M, c.K), generator=g).bfloat16().to(device)
     assert ops.pwconv_plan(c.B, c.M, c.K, c.HW, c.ta) is None
     for epi in ((0, 1) if c.ta else (0, 1, 4)):
-        served, got, bufs = _launch_pw(ops, c._replace(epi=epi), inp, None)
+        served, got, bufs = L.launch_pw(ops, c._replace(epi=epi), inp, None)
         torch.cuda.synchronize()
         assert not served
         assert all(bool(torch.isnan(t).all()) for t in got.values()) and all(P.guards_intact(b, dt) for b, dt in bufs)
@@ -193,34 +143,26 @@ def test_unsupported_pwconv_shapes_are_refused_and_nothing_is_written(device, c)
 # ---------------------------------------------------------------------------------------------
 # pwgrad
 # ---------------------------------------------------------------------------------------------
-def _workspace(nbytes, device):
-    buf, ws = P.guarded((max(nbytes // 4, 1),), F32, device)
-    return buf, ws
-
-
 def _pwgrad_arm(p):
     return f"{'pwgrad2_kernel<32>' if p['step'] else 'pwgrad_kernel'} S={p['S']} x{p['steps_per_split']} tiles {p['tiles_m']}x{p['tiles_n']}"
 
 
 @pytest.mark.parametrize("c", P.PWGRAD_CASES, ids=_ids(P.PWGRAD_CASES))
 def test_pwgrad_rows(device, monkeypatch, c):
-    """ppea_pwgrad_bf16 (pwgrad_kernel / pwgrad2_kernel<32> + pwgrad_reduce_kernel): C and the row sums; with the row sums off
+    """ppea_pwgrad_bf16 (pwgrad_kernel / pwgrad2_kernel<32> + pwgrad_reduce_ex_kernel, fp32, taps = 1): C and the row sums; with the row sums off
     the tail of `out` stays untouched; a second launch is bit-identical."""
     from ppeadepth import ops
     inp = _to(P.make_pwgrad_inputs(c), device)
     M, N, HW = c.M, c.N, c.H * c.W
-    ptr, st = ops.ptr, ops.stream_ptr()
     runs = []
     with _hooks(monkeypatch, c.env):
         p = ops.pwgrad_plan(c.B, M, N, HW)
         for _ in range(2):
-            wbuf, ws = _workspace(p["workspace_bytes"], device)
-            obuf, out = P.guarded((M * N + M,), F32, device)
-            served = ops.try_call("ppea_pwgrad_bf16", ptr(inp["p"]), ptr(inp["q"]), ptr(out), ptr(ws), c.B, M, N, HW, int(c.rowsum), st)
+            served, o, bufs = L.launch_pwgrad(ops, c, inp, device, p)
             torch.cuda.synchronize()
-            runs.append((served, out, obuf, wbuf))
+            runs.append((served, o["out"], bufs))
     arm = _pwgrad_arm(p)
-    served, out, obuf, wbuf = runs[0]
+    served, out, bufs = runs[0]
     assert served and p["step"] == c.claims["step"], arm
     ref = P.pwgrad_reference(inp["p"], inp["q"])
     got = dict(w=out[:M * N].view(M, N))
@@ -229,7 +171,7 @@ def test_pwgrad_rows(device, monkeypatch, c):
     else:
         ref.pop("rowsum")
         assert bool(torch.isnan(out[M * N:]).all()), f"{c.name} ({arm}): the row-sum tail was written with the row sums off"
-    _hold(c.name, arm, got, ref, [(obuf, F32), (wbuf, F32)])
+    _hold(c.name, arm, got, ref, bufs)
     assert torch.equal(_bits(runs[1][1]), _bits(out)), f"{c.name} ({arm}): the second launch differs"
     # through the operator as well
     with _hooks(monkeypatch, c.env):
@@ -238,38 +180,15 @@ def test_pwgrad_rows(device, monkeypatch, c):
     assert torch.equal(w2, got["w"]) and (r2 is None) == (not c.rowsum) and (r2 is None or torch.equal(r2, got["rowsum"]))
 
 
-def _into_launch(ops, c, inp, device, plan):
-    """ppea_pwgrad_ex_bf16 into guarded parameter-layout outputs -> (served, outputs, guarded buffers)."""
-    M, HW = c.taps * c.Ch, c.H * c.W
-    wdt, bdt = (BF16 if c.wdt == "bf16" else F32), (None if c.bdt is None else (BF16 if c.bdt == "bf16" else F32))
-    r0, rn = P.bias_window(c) if bdt is not None else (0, 0)
-    wbuf, ws = _workspace(plan["workspace_bytes"], device)
-    dbuf, dw = P.guarded((c.Ch, c.N, 3, 3) if c.taps == 9 else (c.Ch, c.N), wdt, device)
-    bufs, out = [(wbuf, F32), (dbuf, wdt)], dict(dw=dw)
-    db = None
-    if bdt is not None:
-        bbuf, db = P.guarded((rn,), bdt, device)
-        bufs.append((bbuf, bdt))
-        out["db"] = db
-    served = ops.try_call("ppea_pwgrad_ex_bf16", ops.ptr(inp["p"]), ops.ptr(inp["q"]), ops.ptr(ws), c.B, M, c.N, HW, ops.ptr(dw),
-                          int(wdt == BF16), c.taps, ops.ptr(db), int(bdt == BF16), r0, rn, ops.stream_ptr())
-    return served, out, bufs
-
-
-def _op_args(c, inp):
-    wdt, bdt = (BF16 if c.wdt == "bf16" else F32), (None if c.bdt is None else (BF16 if c.bdt == "bf16" else F32))
-    return (inp["p"], inp["q"], (c.Ch, c.N, 3, 3) if c.taps == 9 else (c.Ch, c.N), wdt, c.taps, P.bias_window(c) if bdt is not None else None, bdt)
-
-
 def _into_row(device, monkeypatch, c, env, tag):
     from ppeadepth import ops
     inp = _to(P.make_into_inputs(c), device)
     with _hooks(monkeypatch, env):
         p = ops.pwgrad_plan(c.B, c.taps * c.Ch, c.N, c.H * c.W)
-        served, got, bufs = _into_launch(ops, c, inp, device, p)
+        served, got, bufs = L.launch_into(ops, c, inp, device, p)
         torch.cuda.synchronize()
-        served2, again, _ = _into_launch(ops, c, inp, device, p)
-        dw_op, db_op = ops.pwgrad_into(*_op_args(c, inp))
+        served2, again, _ = L.launch_into(ops, c, inp, device, p)
+        dw_op, db_op = ops.pwgrad_into(*L.op_args(c, inp))
         torch.cuda.synchronize()
     arm = _pwgrad_arm(p) + f" reduce_ex taps {c.taps}"
     assert served and served2, arm
@@ -297,28 +216,9 @@ def test_pwgrad_pair_rows(device, monkeypatch, row):
     Ms, Ns, HW = (a.taps * a.Ch, b.taps * b.Ch), (a.N, b.N), a.H * a.W
     inps = [_to(P.make_into_inputs(c), device) for c in (a, b)]
     refs = [P.into_reference(c, i) for c, i in zip((a, b), inps)]
-    i2, vp2 = ctypes.c_int * 2, ctypes.c_void_p * 2
 
     def launch(plan):
-        nbytes = plan["workspace_bytes"] if plan else 4096
-        wbuf, ws = _workspace(nbytes, device)
-        bufs, outs = [(wbuf, F32)], []
-        for c in (a, b):
-            wdt, bdt = (BF16 if c.wdt == "bf16" else F32), (None if c.bdt is None else (BF16 if c.bdt == "bf16" else F32))
-            dbuf, dw = P.guarded((c.Ch, c.N, 3, 3) if c.taps == 9 else (c.Ch, c.N), wdt, device)
-            bufs.append((dbuf, wdt))
-            o = dict(dw=dw)
-            if bdt is not None:
-                bbuf, db = P.guarded((P.bias_window(c)[1],), bdt, device)
-                bufs.append((bbuf, bdt))
-                o["db"] = db
-            outs.append(o)
-        p_ = lambda ts: vp2(*(None if t is None else t.data_ptr() for t in ts))                  # noqa: E731
-        wins = [P.bias_window(c) if c.bdt is not None else (0, 0) for c in (a, b)]
-        served = ops.try_call("ppea_pwgrad_ex_pair_bf16", p_([i["p"] for i in inps]), p_([i["q"] for i in inps]), ops.ptr(ws), a.B,
-                              i2(*Ms), i2(*Ns), HW, p_([o["dw"] for o in outs]), i2(*(int(c.wdt == "bf16") for c in (a, b))),
-                              i2(a.taps, b.taps), p_([o.get("db") for o in outs]), i2(*(int(c.bdt == "bf16") for c in (a, b))),
-                              i2(wins[0][0], wins[1][0]), i2(wins[0][1], wins[1][1]), ops.stream_ptr())
+        served, outs, bufs = L.launch_pair(ops, a, b, inps, device, plan)
         torch.cuda.synchronize()
         return served, outs, bufs
 
@@ -326,7 +226,7 @@ def test_pwgrad_pair_rows(device, monkeypatch, row):
         plan = ops.pwgrad_pair_plan(a.B, Ms, Ns, HW)
         served, outs, bufs = launch(plan)
         served2, again, _ = launch(plan)
-        (dwa, dba), (dwb, dbb) = ops.pwgrad_into_pair(_op_args(a, inps[0]), _op_args(b, inps[1]))
+        (dwa, dba), (dwb, dbb) = ops.pwgrad_into_pair(L.op_args(a, inps[0]), L.op_args(b, inps[1]))
         torch.cuda.synchronize()
     assert served == served2 == claimed == (plan is not None), plan
     if served:
@@ -358,16 +258,11 @@ def test_tapsum_rows(device, c):
     the gather) down to W = 4, H = 1, Ch = 1, with every bias form."""
     from ppeadepth import ops
     inp = _to(P.make_tapsum_inputs(c), device)
-    shape = (c.B, c.Ch, c.H, c.W)
-    ptr, st = ops.ptr, ops.stream_ptr()
-    pbuf, pre = P.guarded(shape, BF16, device)
-    hbuf, h = P.guarded(shape, BF16, device)
-    tbuf, dT = P.guarded((c.B, 9 * c.Ch, c.H, c.W), BF16, device)
-    bp, bflag = ops._bias_arg(inp["bias"])
-    assert ops.try_call("ppea_tapsum_fwd_bf16", ptr(inp["T"]), bp, bflag, ptr(pre), ptr(h), c.B, c.Ch, c.H, c.W, st)
-    assert ops.try_call("ppea_tapsum_bwd_bf16", ptr(inp["g"]), ptr(dT), c.B, c.Ch, c.H, c.W, st)
+    served, got, bufs = L.launch_tapsum(ops, c, inp, device)
+    assert served
     torch.cuda.synchronize()
-    _hold(c.name, "tapsum", dict(pre=pre, h=h, dT=dT), P.tapsum_reference(c, inp, pre), [(pbuf, BF16), (hbuf, BF16), (tbuf, BF16)])
+    pre, h, dT = got["pre"], got["h"], got["dT"]
+    _hold(c.name, "tapsum", got, P.tapsum_reference(c, inp, pre), bufs)
     assert torch.equal(dT, P.shift_taps(inp["g"]))
     pre_op, h_op = ops.tapsum_fwd(inp["T"], inp["bias"], c.Ch)
     assert torch.equal(pre_op, pre) and torch.equal(h_op, h) and torch.equal(ops.tapsum_bwd(inp["g"]), dT)
