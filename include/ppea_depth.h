@@ -96,6 +96,11 @@ int ppea_dwconv3x3_fwd_f32(const void* x, const float* w, void* y, int N, int C,
 int ppea_dwconv3x3_fwd_bf16(const void* x, const float* w, void* y, int N, int C, int H, int W, int stride, void* stream);
 int ppea_dwconv3x3_bwd_data_f32(const void* dy, const float* w, void* dx, int N, int C, int H, int W, int stride, void* stream);
 int ppea_dwconv3x3_bwd_data_bf16(const void* dy, const float* w, void* dx, int N, int C, int H, int W, int stride, void* stream);
+/* The kernel these four and ppea_dwconv3x3_fwd_affine_* launch (host only, no device needed): elem_bytes 4 (f32) | 2 (bf16);
+ * mode 0 forward, 1 data gradient, 2 affine forward.  Returns 0 the one-pixel-per-thread kernel, 1 dw3v_s1 (bf16, stride 1,
+ * W % 8 == 0), 2 dw3v_s2_fwd / 3 dw3v_s2_bwd (bf16, stride 2, H and W even, Wo % 8 == 0), or PPEA_ERR_UNSUPPORTED exactly
+ * where the entry points return it (stride not in {1, 2}, N * C > 65535, a size <= 0). */
+int ppea_dwconv3x3_plan(int elem_bytes, int mode, int N, int C, int H, int W, int stride);
 
 /* wgrad (only needed with --fullft_reb, repdepth.py:47, and by the plug-in's weight.grad):
  * dw[c,0,u,v] = sum_{n,i,j} dy[n,c,i,j] * x[n,c,i+u-K/2,j+v-K/2].  dw is overwritten. */

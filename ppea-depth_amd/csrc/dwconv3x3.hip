@@ -245,42 +245,61 @@ __global__ __launch_bounds__(256) void dw3v_s2_bwd(const uint16_t* __restrict__ 
     st8(dx + (plane * H + iy) * (long)W + x0, acc);
 }
 
+// ---- dispatch ----------------------------------------------------------------------------------------------
+// ONE choice of kernel for the forward, the data gradient and the affine forward (ppea_dwconv3x3_plan is this function):
+//   DW3_GENERIC    dw3_fwd / dw3_bwd / dw3_fwd_aff<T, stride>: one thread per pixel, grid (<= 64, planes)
+//   DW3_V_S1       dw3v_s1<FLIP> / dw3v_s1_aff: bf16, stride 1, W % 8 == 0
+//   DW3_V_S2_FWD   dw3v_s2_fwd / dw3v_s2_fwd_aff: bf16, stride 2, H and W even, Wo % 8 == 0
+//   DW3_V_S2_BWD   dw3v_s2_bwd: the data gradient of the same shapes
+enum { DW3_GENERIC = 0, DW3_V_S1 = 1, DW3_V_S2_FWD = 2, DW3_V_S2_BWD = 3 };
+enum { DW3_MODE_FWD = 0, DW3_MODE_BWD = 1, DW3_MODE_AFFINE = 2 };
+inline bool dw3_shape_ok(int N, int C, int H, int W, int stride) {
+    return N > 0 && C > 0 && H > 0 && W > 0 && (stride == 1 || stride == 2);
+}
+inline int dw3_plan(int elem_bytes, int mode, int N, int C, int H, int W, int stride) {
+    if ((elem_bytes != 2 && elem_bytes != 4) || mode < DW3_MODE_FWD || mode > DW3_MODE_AFFINE) return PPEA_ERR_UNSUPPORTED;
+    if (!dw3_shape_ok(N, C, H, W, stride) || (long)N * C > 65535) return PPEA_ERR_UNSUPPORTED;   // planes ride on gridDim.y
+    if (elem_bytes == 2) {                                 // bf16: 8 outputs per thread when the rows allow it
+        const int Wo = (W + 2 - 3) / stride + 1;
+        if (stride == 1 && (W & 7) == 0) return DW3_V_S1;
+        if (stride == 2 && (W & 1) == 0 && (H & 1) == 0 && (Wo & 7) == 0) return mode == DW3_MODE_BWD ? DW3_V_S2_BWD : DW3_V_S2_FWD;
+    }
+    return DW3_GENERIC;
+}
+
 template <typename T>
 int run(bool bwd, const void* a, const float* w, void* o, int N, int C, int H, int W, int stride, void* stream) {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2) || (long)N * C > 65535L * 32)
-        return PPEA_ERR_UNSUPPORTED;
+    const int arm = dw3_plan((int)sizeof(T), bwd ? DW3_MODE_BWD : DW3_MODE_FWD, N, C, H, W, stride);
+    if (arm < 0) return arm;
     const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
     const long planes = (long)N * C;
-    if (planes > 65535) return PPEA_ERR_UNSUPPORTED;
-    if constexpr (sizeof(T) == 2) {                        // bf16: 8 outputs per thread when the rows allow it
-        hipStream_t st = (hipStream_t)stream;
-        const uint16_t* in = (const uint16_t*)a;
-        uint16_t* out = (uint16_t*)o;
-        if (stride == 1 && (W & 7) == 0) {
-            const long total = planes * H * (W >> 3);
-            const unsigned blocks = (unsigned)((total + 255) / 256);
-            if (!bwd) hipLaunchKernelGGL(dw3v_s1<false>, dim3(blocks), dim3(256), 0, st, in, w, out, C, H, W, total);
-            else hipLaunchKernelGGL(dw3v_s1<true>, dim3(blocks), dim3(256), 0, st, in, w, out, C, H, W, total);
-            return launch_status();
-        }
-        if (stride == 2 && (W & 1) == 0 && (H & 1) == 0 && (Wo & 7) == 0) {
-            if (!bwd) {
-                const long total = planes * Ho * (Wo >> 3);
-                hipLaunchKernelGGL(dw3v_s2_fwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H,
-                                   W, Ho, Wo, total);
-            } else {
-                const long total = planes * H * (W >> 3);
-                hipLaunchKernelGGL(dw3v_s2_bwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H,
-                                   W, Ho, Wo, total);
-            }
-            return launch_status();
-        }
+    hipStream_t st = (hipStream_t)stream;
+    const uint16_t* in = (const uint16_t*)a;
+    uint16_t* out = (uint16_t*)o;
+    switch (arm) {
+    case DW3_V_S1: {
+        const long total = planes * H * (W >> 3);
+        const unsigned blocks = (unsigned)((total + 255) / 256);
+        if (!bwd) hipLaunchKernelGGL(dw3v_s1<false>, dim3(blocks), dim3(256), 0, st, in, w, out, C, H, W, total);
+        else hipLaunchKernelGGL(dw3v_s1<true>, dim3(blocks), dim3(256), 0, st, in, w, out, C, H, W, total);
+        return launch_status();
+    }
+    case DW3_V_S2_FWD: {
+        const long total = planes * Ho * (Wo >> 3);
+        hipLaunchKernelGGL(dw3v_s2_fwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H, W, Ho, Wo, total);
+        return launch_status();
+    }
+    case DW3_V_S2_BWD: {
+        const long total = planes * H * (W >> 3);
+        hipLaunchKernelGGL(dw3v_s2_bwd, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H, W, Ho, Wo, total);
+        return launch_status();
+    }
+    default: break;
     }
     const int work = bwd ? H * W : Ho * Wo;
     int bx = (work + 255) / 256;
     if (bx > 64) bx = 64;
     dim3 g(bx, (unsigned)planes);
-    hipStream_t st = (hipStream_t)stream;
     if (!bwd) {
         if (stride == 1) hipLaunchKernelGGL((dw3_fwd<T, 1>), g, dim3(256), 0, st, (const T*)a, w, (T*)o, C, H, W, Ho, Wo);
         else hipLaunchKernelGGL((dw3_fwd<T, 2>), g, dim3(256), 0, st, (const T*)a, w, (T*)o, C, H, W, Ho, Wo);
@@ -294,27 +313,29 @@ int run(bool bwd, const void* a, const float* w, void* o, int N, int C, int H, i
 template <typename T>
 int run_affine(const void* a, const float* w, const float* s, const float* o, int relu, void* out_, int N, int C, int H, int W,
                int stride, void* stream) {
-    if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (stride != 1 && stride != 2)) return PPEA_ERR_UNSUPPORTED;
+    if (!dw3_shape_ok(N, C, H, W, stride)) return PPEA_ERR_UNSUPPORTED;
     if (a == nullptr || w == nullptr || s == nullptr || o == nullptr || out_ == nullptr) return PPEA_ERR_ARG;
+    const int arm = dw3_plan((int)sizeof(T), DW3_MODE_AFFINE, N, C, H, W, stride);
+    if (arm < 0) return arm;
     const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
     const long planes = (long)N * C;
-    if (planes > 65535) return PPEA_ERR_UNSUPPORTED;
     hipStream_t st = (hipStream_t)stream;
     const Aff af{s, o, relu};
-    if constexpr (sizeof(T) == 2) {
-        const uint16_t* in = (const uint16_t*)a;
-        uint16_t* out = (uint16_t*)out_;
-        if (stride == 1 && (W & 7) == 0) {
-            const long total = planes * H * (W >> 3);
-            hipLaunchKernelGGL(dw3v_s1_aff, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H, W, total, af);
-            return launch_status();
-        }
-        if (stride == 2 && (W & 1) == 0 && (H & 1) == 0 && (Wo & 7) == 0) {
-            const long total = planes * Ho * (Wo >> 3);
-            hipLaunchKernelGGL(dw3v_s2_fwd_aff, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H, W, Ho,
-                               Wo, total, af);
-            return launch_status();
-        }
+    const uint16_t* in = (const uint16_t*)a;
+    uint16_t* out = (uint16_t*)out_;
+    switch (arm) {
+    case DW3_V_S1: {
+        const long total = planes * H * (W >> 3);
+        hipLaunchKernelGGL(dw3v_s1_aff, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H, W, total, af);
+        return launch_status();
+    }
+    case DW3_V_S2_FWD: {
+        const long total = planes * Ho * (Wo >> 3);
+        hipLaunchKernelGGL(dw3v_s2_fwd_aff, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, in, w, out, C, H, W, Ho,
+                           Wo, total, af);
+        return launch_status();
+    }
+    default: break;
     }
     int bx = (Ho * Wo + 255) / 256;
     if (bx > 64) bx = 64;
@@ -447,6 +468,12 @@ int ppea_dwconv3x3_fwd_affine_f32(const void* x, const float* w, const float* s,
 int ppea_dwconv3x3_fwd_affine_bf16(const void* x, const float* w, const float* s, const float* o, int relu, void* y, int N, int C,
                                    int H, int W, int stride, void* stream) {
     return run_affine<uint16_t>(x, w, s, o, relu, y, N, C, H, W, stride, stream);
+}
+// The kernel the entry points below and the affine ones above launch (host only): elem_bytes 4 (f32) | 2 (bf16); mode 0 forward,
+// 1 data gradient, 2 affine forward -> 0 generic, 1 dw3v_s1, 2 dw3v_s2_fwd, 3 dw3v_s2_bwd; PPEA_ERR_UNSUPPORTED exactly where
+// they return it.
+int ppea_dwconv3x3_plan(int elem_bytes, int mode, int N, int C, int H, int W, int stride) {
+    return dw3_plan(elem_bytes, mode, N, C, H, W, stride);
 }
 // x [N,C,H,W] -> y [N,C,Ho,Wo], Ho = (H-1)/stride + 1; w [C,1,3,3] fp32
 int ppea_dwconv3x3_fwd_f32(const void* x, const float* w, void* y, int N, int C, int H, int W, int stride, void* stream) {

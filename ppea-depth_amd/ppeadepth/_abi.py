@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 30
+ABI_VERSION = 31
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -34,6 +34,7 @@ SIGNATURES = {
     "ppea_dwconv3x3_fwd_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ppea_dwconv3x3_bwd_data_f32": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "ppea_dwconv3x3_bwd_data_bf16": [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "ppea_dwconv3x3_plan": [_i] * 7,
     "ppea_dwconv_lk_packed_bytes": [_i, _i],
     "ppea_dwconv_lk_pack_bf16": [_vp, _vp, _i, _i, _i, _vp],
     "ppea_dwconv_lk_fwd_bf16p": [_vp] * 5 + [_i] * 6 + [_vp],

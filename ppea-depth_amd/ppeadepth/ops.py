@@ -1832,8 +1832,11 @@ class _BiasElu(torch.autograd.Function):
 def bias_elu(z, bias):
     """elu(z + bias[None, :, None, None]) in one pass; the bias gradient comes out of the backward pass.
     NCHW or channels_last input (output in the same format)."""
-    if _is_nhwc(z) and _nhwc_c_ok(z.shape[1]):
-        return _BiasEluNhwc.apply(z, bias)
+    if _is_nhwc(z):
+        if _nhwc_c_ok(z.shape[1]):
+            return _BiasEluNhwc.apply(z, bias)
+        # a channel count the channels_last kernel does not serve: the NCHW kernel, the result handed back in the input's format
+        return _BiasElu.apply(z, bias).contiguous(memory_format=torch.channels_last)
     return _BiasElu.apply(z, bias)
 
 
@@ -2740,6 +2743,22 @@ def pwconv_plan(B, M, K, HW, transposed=False):
     if not try_call("ppea_pwconv_plan", B, M, K, HW, int(transposed), out):
         return None
     return dict(zip(PWCONV_PLAN_FIELDS, out))
+
+
+DWCONV3X3_ARMS = ("generic", "dw3v_s1", "dw3v_s2_fwd", "dw3v_s2_bwd")
+DWCONV3X3_MODES = ("forward", "data_gradient", "affine_forward")
+
+
+def dwconv3x3_plan(dtype, mode, N, C, H, W, stride):
+    """The kernel ppea_dwconv3x3_fwd_* / _bwd_data_* / _fwd_affine_* launch for these arguments (host only, works without a
+    device): the index into DWCONV3X3_ARMS, or None where the entry points do not serve the shape.  `mode`: one of
+    DWCONV3X3_MODES or its index."""
+    m = DWCONV3X3_MODES.index(mode) if isinstance(mode, str) else int(mode)
+    arm = _abi.lib.ppea_dwconv3x3_plan(4 if dtype == _F32 else 2, m, N, C, H, W, stride)
+    if arm == -1:
+        return None
+    _abi.check(0 if arm >= 0 else arm, "ppea_dwconv3x3_plan")
+    return arm
 
 
 def pwconv_plan_sweep(B, transposed, Mstep, nM, nK, nHW):

@@ -44,7 +44,7 @@ def _build(batch):
     return opt, model, Trainer(opt, model, dev), dev
 
 
-def _worker(rank, world, port, q):
+def _worker(rank, world, port, q, taken):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
@@ -75,6 +75,7 @@ def _worker(rank, world, port, q):
                        sd["depth.upconvs_0.0.conv.conv.weight"].float().flatten()[:64].cpu()])
     q.put((rank, outputs[("disp", 0)].detach().float().cpu(), outputs[("mono_disp", 0)].detach().float().cpu(),
            probe, float(losses["loss"])))
+    taken.wait(240)                             # the tensors travel as file descriptors this process serves: stay until they are read
     dist.barrier()
     dist.destroy_process_group()
 
@@ -84,10 +85,12 @@ def test_two_ranks_match_global_batch(device):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = 29700 + os.getpid() % 200
-    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
+    taken = ctx.Event()
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, q, taken)) for r in range(2)]
     for p in procs:
         p.start()
     res = sorted([q.get(timeout=240) for _ in procs], key=lambda t: t[0])
+    taken.set()
     for p in procs:
         p.join(120)
         assert p.exitcode == 0
@@ -115,7 +118,7 @@ def test_two_ranks_match_global_batch(device):
 # ---------------------------------------------------------------------------------------------
 # real RCCL, two devices: skipped on a one-GPU box (the development box has one); runs wherever >= 2 GPUs are visible
 # ---------------------------------------------------------------------------------------------
-def _nccl_worker(rank, world, port, q):
+def _nccl_worker(rank, world, port, q, taken):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, root)
@@ -148,6 +151,7 @@ def _nccl_worker(rank, world, port, q):
     probe = torch.cat([sd["encoder.replk.stem.0.bn.running_var"].float().cpu(),
                        eng.P[:4096].float().cpu()])
     q.put((rank, probe, l_eager, l_graph))
+    taken.wait(600)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -159,10 +163,12 @@ def test_two_ranks_rccl_eager_and_captured(device):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = 29900 + os.getpid() % 90
-    procs = [ctx.Process(target=_nccl_worker, args=(r, 2, port, q)) for r in range(2)]
+    taken = ctx.Event()
+    procs = [ctx.Process(target=_nccl_worker, args=(r, 2, port, q, taken)) for r in range(2)]
     for p in procs:
         p.start()
     res = sorted([q.get(timeout=600) for _ in procs], key=lambda t: t[0])
+    taken.set()
     for p in procs:
         p.join(120)
         assert p.exitcode == 0
