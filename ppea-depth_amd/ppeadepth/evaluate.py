@@ -9,6 +9,8 @@ Two statements of the same protocol: host-side numpy like the reference (`evalua
 device path (`DeviceGroundTruth`, `evaluate_disps_device`, `Trainer.val(metrics="device")`) that scores the disparities
 where the predictor left them, on `ops.depth_errors` (csrc/eval_metrics.hip), with one copy to the host per split.
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -196,6 +198,44 @@ class DeviceGroundTruth:
         self = cls.__new__(cls)
         device = torch.device(device)
         self._set(*kitti_utils.project_depth_maps(clouds, matrices, shapes, vel_depth, device), device)
+        return self
+
+    @classmethod
+    def from_folder(cls, folder, count, device):
+        """The ground truth the reference keeps as single files, `<folder>/<str(i).zfill(3)>_depth.npy` for i < count
+        (trainer.py:760-780; Cityscapes: 1525 maps of 1024 x 2048).  One file at a time goes through one pinned staging
+        buffer into a preallocated device buffer: the split is never whole on the host.  The maps are uploaded whole
+        (`region_of` derives the crop from the nominal height); the layout is the constructor's."""
+        device = torch.device(device)
+        if count < 1:
+            raise ValueError(f"count {count}: a split has at least one ground-truth map")
+        paths = [os.path.join(folder, str(i).zfill(3) + "_depth.npy") for i in range(count)]
+        for p in [folder] + paths:
+            if not os.path.exists(p):
+                raise FileNotFoundError(f"{p} not found: the Cityscapes ground truth is <splits_dir>/cityscapes/gt_depths/"
+                                        "NNN_depth.npy, one file per line of the test split -- download ManyDepth's "
+                                        "gt_depths_cityscapes.zip (see the reference's README) and unzip it into "
+                                        "<splits_dir>/cityscapes")
+        shapes = []
+        for p in paths:                                       # the headers only: shapes and the size of the buffer
+            m = np.load(p, mmap_mode="r")
+            if m.ndim != 2:
+                raise ValueError(f"{p}: a [H,W] depth map, got shape {m.shape}")
+            shapes.append(tuple(int(d) for d in m.shape))
+        sizes = [h * w for h, w in shapes]
+        offsets = np.concatenate([[0], np.cumsum(sizes)])
+        flat = torch.empty(int(offsets[-1]), device=device, dtype=torch.float32)
+        stage = torch.empty(max(sizes), dtype=torch.float32)
+        if device.type == "cuda":
+            stage = stage.pin_memory()
+        for i, p in enumerate(paths):
+            if device.type == "cuda":
+                torch.cuda.current_stream(device).synchronize()      # the copy that still reads the staging buffer
+            np.copyto(stage[:sizes[i]].numpy().reshape(shapes[i]), np.load(p), casting="same_kind")
+            flat[int(offsets[i]):int(offsets[i + 1])].copy_(stage[:sizes[i]], non_blocking=True)
+        self = cls.__new__(cls)
+        table = torch.tensor([[int(offsets[i]), h, w] for i, (h, w) in enumerate(shapes)], dtype=torch.int64).to(device)
+        self._set(flat, table, shapes, device)
         return self
 
     def __len__(self):

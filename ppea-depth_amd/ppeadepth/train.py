@@ -2,11 +2,15 @@
 
     python -m ppeadepth.train --data_path KITTI --adapter --use_checkpoint --validate_every 3000 --num_epochs 30
     python -m ppeadepth.train --data_path KITTI --adapter --use_checkpoint --eval --load_weights_folder CKPT
+    python -m ppeadepth.train --data_path CS_TRIPLETS --cs_eval_path CS_RAW --train_cs --dc --adapter --use_checkpoint \\
+        --validate_every 1000 --learning_rate 1e-5 --load_weights_folder STAGE1_CKPT
+    python -m ppeadepth.train --data_path CS_TRIPLETS --cs_eval_path CS_RAW --train_cs --dc --adapter --use_checkpoint \\
+        --eval --load_weights_folder CKPT
 
 Run flags (this module's parser; every other flag is a model option of `options.MonodepthOptions`):
   reference names and defaults   --data_path --split (eigen_zhou) --eval_split (eigen) --png --num_workers (12)
                                  --validate_every (1000) --validate_from (0) --save_until (0) --saveoff --eval
-                                 --pytorch_random_seed (None -> 1)
+                                 --pytorch_random_seed (None -> 1) --cs_eval_path (../cityscapes)
   new here                       --splits_dir (splits) --ckpt_dir (./ckpt) --log_every (50) --early_val_step (250, 0 = off)
                                  --fp32 (default bf16 with bf16 parameters) --no_capture (eager steps) --resume --max_steps
 
@@ -20,8 +24,21 @@ on the items `item_indices(g, ...)` of the split file, and its augmentation draw
 `step_seed(seed, g)`.  The batch is therefore a function of (seed, global step) alone and a resumed run needs no loader state:
 the sampler starts at the right item.
 
-Not served (refused with a message): --train_cs and --ddad (their pipelines exist, a folder reader does not), several ranks
-(WORLD_SIZE > 1), --freeze_teacher_and_pose and --freeze_pose.
+Cityscapes (--train_cs; Stage 2 of the paper with --dc).  The same `Run` with other parts: `CityscapesPreprocessedDataset` +
+`collate_cityscapes` -> `CityscapesInputPipeline` for the steps, `CityscapesEvalDataset(--cs_eval_path)` +
+`collate_cityscapes_eval` -> `CityscapesEvalPipeline` for validation, the ground truth from `<splits_dir>/cityscapes/gt_depths`
+(`DeviceGroundTruth.from_folder`); --split and --eval_split follow the flag, and both split files are read from
+`<splits_dir>/cityscapes_preprocessed`.  With --dc `main` calls `model.dc_ft_init()` before the model moves to the device and
+before trainer and engine exist, so the decoder adapters are in the trainable set and train (the reference builds its Adam
+first and never steps them); a Stage-1 checkpoint leaves them as drawn and its adam.pth is skipped, a Stage-2 checkpoint of
+this loop restores both (the reference drops the adapter keys on load).
+
+Validation inputs never change during a run: the first validation reads them from disk and keeps what the predictor reads
+on the device as uint8 (`valstore.ValidationStore`, both datasets); later validations start no loader worker.
+
+Not served (refused with a message): --ddad (its pipeline exists, a folder reader does not), --train_cs with
+--use_future_frame or --num_matching_frames > 1 (the evaluation loader holds frames 0 and -1), several ranks
+(WORLD_SIZE > 1), --freeze_teacher_and_pose and --freeze_pose; --static_camera and --zero_cost_volume are not parsed.
 """
 import argparse
 import os
@@ -111,12 +128,40 @@ class _EpochSampler(torch.utils.data.Sampler):
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------
-def check_served(opt):
-    """SystemExit for what this loop does not serve, before anything is built."""
-    if getattr(opt, "train_cs", False) or getattr(opt, "ddad", False):
-        flag = "--ddad" if getattr(opt, "ddad", False) else "--train_cs"
-        raise SystemExit(f"{flag}: the input pipeline of that dataset exists (input_pipeline.py) but no folder reader does; "
-                         "ppeadepth.train serves KITTI raw folders only")
+def is_cityscapes(opt):
+    """`--train_cs`, before or after `options.apply_train_cs` has rewritten the options (`--ddad` wins, trainer.py:90-103)."""
+    if getattr(opt, "ddad", False):
+        return False
+    return bool(getattr(opt, "train_cs", False)) or getattr(opt, "dataset", None) == "cityscapes_preprocessed"
+
+
+def check_served(opt, args=None):
+    """SystemExit for what this loop does not serve, before anything is built.  args: the run flags; with them the files a
+    `--train_cs` run opens first are looked for as well (both split files, the first training image)."""
+    if getattr(opt, "ddad", False):
+        raise SystemExit("--ddad: the input pipeline of that dataset exists (input_pipeline.py) but no folder reader does; "
+                         "ppeadepth.train serves KITTI raw and Cityscapes folders only")
+    if is_cityscapes(opt):
+        # the wide training image holds frames -1, 0, +1 and the evaluation loader frames 0 and -1 (cityscapes_evaldataset.py)
+        if getattr(opt, "use_future_frame", False) or getattr(opt, "num_matching_frames", 1) > 1:
+            raise SystemExit("--train_cs with --use_future_frame or --num_matching_frames > 1: the Cityscapes evaluation "
+                             "loader holds frames 0 and -1 only, no other lookup frame can be validated")
+        if args is not None:
+            from . import datasets
+            folder = os.path.join(args.splits_dir, "cityscapes_preprocessed")
+            for name in ("train", "test"):
+                path = os.path.join(folder, f"{name}_files.txt")
+                if not os.path.isfile(path):
+                    raise SystemExit(f"--train_cs: {path} not found (the split files of the preprocessed triplets and of "
+                                     "the evaluation frames are both read from that folder: --splits_dir)")
+            lines = datasets.readlines(os.path.join(folder, "train_files.txt"))
+            if not lines:
+                raise SystemExit(f"--train_cs: {os.path.join(folder, 'train_files.txt')} is empty")
+            data = datasets.CityscapesPreprocessedDataset(args.data_path, lines)
+            path = data.get_image_path(*data.index_to_folder_and_frame_idx(0)[:2])
+            if not os.path.isfile(path):
+                raise SystemExit(f"--train_cs: {path} not found -- make sure --data_path is the folder of the preprocessed "
+                                 "triplets (<city>/<frame_name>.jpg and _cam.txt)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit(f"WORLD_SIZE={os.environ['WORLD_SIZE']}: ppeadepth.train runs on one rank; the step itself serves "
                          "several (dist.TrainEngine), the loop around it is not measured there")
@@ -124,6 +169,13 @@ def check_served(opt):
         if getattr(opt, flag, False):
             raise SystemExit(f"--{flag}: freeze_tp_net() and the tracker reset of trainer.py:166-173 are not wired into "
                              "ppeadepth.train")
+
+
+def follow_train_cs(args, opt):
+    """The split run flags follow `--train_cs` (trainer.py:90-96): split "cityscapes_preprocessed", eval_split "cityscapes"."""
+    if is_cityscapes(opt):
+        args.split, args.eval_split = "cityscapes_preprocessed", "cityscapes"
+    return args
 
 
 def load_gt_depths(splits_dir, eval_split):
@@ -138,6 +190,7 @@ def _run_parser():
     p = argparse.ArgumentParser(description="PPEA-Depth training run; other flags: options.MonodepthOptions")
     a = p.add_argument
     a("--data_path", required=True)
+    a("--cs_eval_path", default="../cityscapes", help="--train_cs: the raw Cityscapes folder the validation frames are in")
     a("--split", default="eigen_zhou")
     a("--eval_split", default="eigen")
     a("--png", action="store_true", help="the frames are .png files (default .jpg)")
@@ -176,23 +229,33 @@ class Run:
     """Trainer, engine, loaders, pipelines, ground truth, predictor and `RunLog` of one run; `train()` and `run_epoch()`.
     trainer, engine: built by the caller (`main` builds them from the flags).  args: the run flags (`_run_parser`)."""
 
-    def __init__(self, trainer, engine, args, seed=1, out=print, train_data=None, val_data=None):
-        """train_data / val_data: datasets with `KITTIRAWDataset`'s item contract to use instead of the split files' frames
-        (train_data with `opt.frame_ids` and the matching frames, val_data with frame 0 and the lookup frames)."""
+    def __init__(self, trainer, engine, args, seed=1, out=print, train_data=None, val_data=None, val_store=True):
+        """train_data / val_data: datasets with the item contract of the run's readers (`KITTIRAWDataset`, or under
+        `--train_cs` `CityscapesPreprocessedDataset` / `CityscapesEvalDataset`) to use instead of the split files' frames
+        (train_data with `opt.frame_ids` and the matching frames, val_data with frame 0 and the lookup frames).
+        val_store: keep the validation inputs on the device after the first validation (`valstore.ValidationStore`);
+        False: every validation goes through the loader."""
         from . import datasets
+        from . import input_pipeline as ip
         from .inference import DepthPredictor
-        from .input_pipeline import DeviceInputPipeline
         from .runlog import RunLog
+        from .valstore import ValidationStore
         self.trainer, self.engine, self.args, self.seed, self.out = trainer, engine, args, int(seed), out
         opt = self.opt = trainer.opt
-        check_served(opt)
+        follow_train_cs(args, opt)
+        check_served(opt, args if train_data is None and val_data is None else None)
         self.device = dev = trainer.device
+        self.cityscapes = cs = is_cityscapes(opt)
         model = trainer._module()
         ext = ".png" if args.png else ".jpg"
         fpath = os.path.join(args.splits_dir, args.split, "{}_files.txt")
         B = opt.batch_size
         train_ids = list(opt.frame_ids) + [int(f) for f in model.matching_ids if f not in opt.frame_ids]
-        if train_data is None:
+        self.collate, self.val_collate = ((datasets.collate_cityscapes, datasets.collate_cityscapes_eval) if cs
+                                          else (datasets.collate_raw, datasets.collate_raw))
+        if train_data is None and cs:
+            train_data = datasets.CityscapesPreprocessedDataset(args.data_path, datasets.readlines(fpath.format("train")))
+        elif train_data is None:
             train_data = datasets.KITTIRAWDataset(args.data_path, datasets.readlines(fpath.format("train")), train_ids, ext)
         self.train_data = train_data
         self.steps_in_epoch = steps_per_epoch(len(train_data), B)
@@ -205,18 +268,29 @@ class Run:
         loader_gen.manual_seed(self.seed)
         self.loader = torch.utils.data.DataLoader(self.train_data, B, shuffle=False, sampler=self.sampler, drop_last=True,
                                                   num_workers=args.num_workers, pin_memory=dev.type == "cuda",
-                                                  collate_fn=datasets.collate_raw, generator=loader_gen)
-        self.pipe = DeviceInputPipeline(None, opt.height, opt.width, dev, frame_idxs=tuple(train_ids))
-        # validation (trainer.py:128-134, 225-227): frame 0 and the lookup frames, no augmentation, the last batch kept
+                                                  collate_fn=self.collate, generator=loader_gen)
+        if cs:
+            self.pipe = ip.CityscapesInputPipeline(dev, opt.height, opt.width, train_data.raw_hw, frame_idxs=tuple(train_ids))
+        else:
+            self.pipe = ip.DeviceInputPipeline(None, opt.height, opt.width, dev, frame_idxs=tuple(train_ids))
+        # validation (trainer.py:128-134, 204-212, 225-227): frame 0 and the lookup frames, no augmentation, the last batch
+        # kept; under --train_cs the raw test frames of --cs_eval_path, listed by the same split folder
         self.predictor = DepthPredictor(model, opt, amp_dtype=trainer.amp_dtype)
         val_ids = [0] + self.predictor.lookup_ids
-        if val_data is None:
+        if val_data is None and cs:
+            val_data = datasets.CityscapesEvalDataset(args.cs_eval_path, datasets.readlines(fpath.format("test")), val_ids)
+        elif val_data is None:
             val_data = datasets.KITTIRAWDataset(args.data_path, datasets.readlines(fpath.format("test")), val_ids, ext)
         self.val_data = val_data
         self.val_loader = torch.utils.data.DataLoader(self.val_data, B, shuffle=False, drop_last=False,
                                                       num_workers=args.num_workers, pin_memory=dev.type == "cuda",
-                                                      collate_fn=datasets.collate_raw, generator=loader_gen)
-        self.val_pipe = DeviceInputPipeline(None, opt.height, opt.width, dev, frame_idxs=tuple(val_ids), is_train=False)
+                                                      collate_fn=self.val_collate, generator=loader_gen)
+        if cs:
+            self.val_pipe = ip.CityscapesEvalPipeline(dev, opt.height, opt.width, val_data.raw_hw, frame_idxs=tuple(val_ids))
+        else:
+            self.val_pipe = ip.DeviceInputPipeline(None, opt.height, opt.width, dev, frame_idxs=tuple(val_ids), is_train=False)
+        self.val_store = ValidationStore(val_ids, len(val_data), dev, self.val_pipe.unit, self.val_pipe.backend) \
+            if val_store else None
         self._gt = None
         self.log = RunLog(dev, capacity=max(256, 2 * args.log_every), names=LOG_NAMES)
         self.rows, self.validations = [], []          # everything logged / validated so far, for the caller
@@ -234,6 +308,11 @@ class Run:
         if not a.no_capture and not a.eval:
             if eng.stream is None:
                 raise SystemExit("the captured step needs a HIP device: pass --no_capture for eager steps on the host")
+            if opt.load_weights_folder and getattr(opt, "dc", False):
+                # Stage 2 freezes the decoder, whose weights are the checkpoint's and not this process's draws: the captured
+                # step reads images of the frozen weights built before the capture, so they are in place before it.  The
+                # load after the capture then finds them equal and puts everything the warm-up was restored to back again.
+                tr.load_model(opt.load_weights_folder, eng, transfer=opt.ktf)
             eng.capture(self.first_batch(), restore_state=True)
         if opt.load_weights_folder:
             tr.load_model(opt.load_weights_folder, eng, transfer=opt.ktf)
@@ -247,22 +326,45 @@ class Run:
     def batch(self, frames, global_step):
         """Packed frames of one step -> the step's inputs; the augmentation is a function of (seed, global_step)."""
         self._gen.manual_seed(step_seed(self.seed, global_step))
+        if self.cityscapes:
+            triplets, cameras = frames
+            return self.pipe(triplets, cameras, generator=self._gen)
         return self.pipe(frames, generator=self._gen)
 
     def first_batch(self):
         """The inputs of step 0, for `TrainEngine.capture` (the warm-up consumes no training step: restore_state=True)."""
-        from .datasets import collate_raw
         idx = item_indices(0, len(self.train_data), self.opt.batch_size)
-        return self.batch(collate_raw([self.train_data[i] for i in idx]), 0)
+        return self.batch(self.collate([self.train_data[i] for i in idx]), 0)
+
+    def loader_val_batches(self):
+        """The validation batches from disk: loader workers, decode, upload, the evaluation pipeline."""
+        for frames in self.val_loader:
+            yield self.val_pipe(*frames) if self.cityscapes else self.val_pipe(frames)
 
     def val_batches(self):
-        for frames in self.val_loader:
-            yield self.val_pipe(frames)
+        """The first validation of a run reads the loader's batches and keeps what the predictor reads of them on the
+        device; every later one reads that store (valstore.py)."""
+        store = self.val_store
+        if store is None:
+            yield from self.loader_val_batches()
+        elif store.complete:
+            yield from store.batches(self.opt.batch_size)
+        else:
+            store.begin()
+            for data in self.loader_val_batches():
+                store.add(data)
+                yield data
+            store.finish()
 
     def ground_truth(self):
         if self._gt is None:
             from .evaluate import DeviceGroundTruth
-            self._gt = DeviceGroundTruth(load_gt_depths(self.args.splits_dir, self.args.eval_split), self.device)
+            a = self.args
+            if a.eval_split == "cityscapes":               # single files, for their combined size (trainer.py:760-780)
+                self._gt = DeviceGroundTruth.from_folder(os.path.join(a.splits_dir, a.eval_split, "gt_depths"),
+                                                         len(self.val_data), self.device)
+            else:
+                self._gt = DeviceGroundTruth(load_gt_depths(a.splits_dir, a.eval_split), self.device)
         return self._gt
 
     # -- what follows a step ---------------------------------------------------------------------------------------------
@@ -364,7 +466,9 @@ def main(argv=None):
     from .trainer import Trainer
     args, rest = _run_parser().parse_known_args(argv)
     opt = options.MonodepthOptions().parse(rest)
-    check_served(opt)
+    follow_train_cs(args, opt)
+    check_served(opt, args)
+    options.apply_train_cs(opt)                # before the model is built (options.apply_train_cs)
     if args.resume and not opt.load_weights_folder:
         raise SystemExit("--resume goes on from a checkpoint: give --load_weights_folder")
     if args.eval and not opt.load_weights_folder:
@@ -374,7 +478,14 @@ def main(argv=None):
     device = torch.device(args.device if args.device else ("cuda" if torch.cuda.is_available() else "cpu"))
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    model = networks.RepDepth(opt).to(device).train()
+    model = networks.RepDepth(opt)
+    if opt.dc:
+        # Stage 2: the decoder adapters are built and the rest of the decoders frozen BEFORE the engine exists, so the
+        # engine's trainable set and its fresh Adam are the Stage-2 ones; their initialisation draws follow the model's own
+        # (trainer.py:154).  `Run.start` loads --load_weights_folder afterwards: a Stage-1 checkpoint has no adapter keys
+        # and leaves them as drawn, a Stage-2 checkpoint of this loop restores them and their Adam moments.
+        model.dc_ft_init()
+    model.to(device).train()
     trainer = Trainer(opt, model, device, amp_dtype=None if args.fp32 else torch.bfloat16)
     engine = TrainEngine(trainer, bf16_params=not args.fp32)
     global last_run
