@@ -776,6 +776,49 @@ int ppea_colorize_u8(const float* x, const float* range, const uint8_t* lut, con
                      long out_len, int B, int h, int w, long max_pixels, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Point clouds (ABI 32), csrc/point_cloud.hip: 3D points from a predicted plane and the pose chain of a stream.
+ * ppea_point_cloud_f32: pred, scale, table (offset, H, W), max_pixels and mode are ppea_disp_export_f32's; d(u, v) of target
+ *   pixel (u, v) is the value that entry point computes BEFORE its clamp (same device function, csrc/export_sample.h), so a
+ *   kept pixel's d is bit-equal to what ppea_disp_export_f32 writes for it.  inv_K, cam_to_world: [B][4][4] fp32 (device);
+ *   inv_K belongs to the TARGET size of image b and only its upper-left 3x3 is read; cam_to_world NULL = identity (the
+ *   camera point is written as it is).
+ *   Candidates: pixels with u % stride == 0 && v % stride == 0.  A candidate is kept iff d > lo && d < hi (a NaN fails;
+ *   pixels on the clamp are dropped) and (edge <= 0, or every 4-neighbour n inside the image, at distance 1 in the target
+ *   plane whatever the stride, has |d_n - d| <= edge * d in fp32; a NaN neighbour does not drop the pixel).
+ *   Point, fp32 in this order, no contraction, (u, v) the integer pixel (layers.BackprojectDepth):
+ *     ray = ((k00 u + k01 v) + k02, (k10 u + k11 v) + k12, (k20 u + k21 v) + k22),  c = ray * d,
+ *     p_i = ((r_i0 c_0 + r_i1 c_1) + r_i2 c_2) + t_i.
+ *   colour_mode 0: none (colour, colour_off, rgb may be NULL); 1: uint8 HWC frames at the target sizes, image b at byte
+ *   colour_off[b] of `colour` (a RaggedFrames buffer, ppea_colorize_u8's output); 2: fp32 planar [B][3][H][W] in [0, 1],
+ *   every target (H, W) (the caller checks that: the launcher does not read the device table), byte = (uint8)rintf(c * 255)
+ *   clamped to 0..255.
+ *   Output: kept points in image order, raster order of (v, u) inside an image: a function of the inputs alone, bit for
+ *   bit.  Point k: xyz[k][3] fp32, rgb[k][3] uint8, index[k] int64 = offset_b + v * W + u.  cursor [2] int64 (device):
+ *   cursor[0] at entry = points the buffers already hold; the call appends behind them and never writes at or beyond
+ *   `capacity`; at exit cursor[0] = min(capacity, start + total) and cursor[1] has grown by the points that did not fit.
+ *   counts [B] int64 = kept pixels of image b, fitted or not.  Nothing is read on the host.
+ *   Three launches on `stream`: validity bits (one 64-bit __ballot word per wave) and counts per chunk of 2048 candidates
+ *   into the workspace; ONE workgroup scans the chunk counts, writes counts and cursor; the scatter takes a kept pixel's
+ *   rank from the stored bits.  No workgroup waits for another one; no atomics.  workspace: 8-byte aligned,
+ *   ppea_point_cloud_workspace_bytes(B, max_pixels, stride) bytes (a negative value for arguments the call refuses).
+ *   PPEA_ERR_ARG: stride < 1, capacity < 0, B <= 0 or B > 65535, colour_mode outside 0..2, a NULL required array (with
+ *   capacity 0 the three output arrays may be NULL);
+ *   PPEA_ERR_UNSUPPORTED: any other mode, max_pixels >= 2^31.  A refused call writes nothing.
+ * ppea_pose_accumulate_f32: world [B][4][4] fp32 in place, pose [B][F][4][4] fp32, present [B][F] uint8: where
+ *   present[b][0] != 0, world[b] = world[b] @ pose[b][0], element ij = ((w_i0 p_0j + w_i1 p_1j) + w_i2 p_2j) + w_i3 p_3j in
+ *   fp32; elsewhere world[b] = identity.  pose[b][0] is the stream's "0 -> -1" transform, so world stays the
+ *   camera-to-world matrix of the newest frame with the clip's first frame as the world.  A plain product chain: no
+ *   re-orthonormalisation.  One launch.
+ * ---------------------------------------------------------------------------------------- */
+long ppea_point_cloud_workspace_bytes(int B, long max_pixels, int stride);
+int ppea_point_cloud_f32(const float* pred, const float* scale, const int64_t* table, int B, int h, int w, long max_pixels,
+                         float lo, float hi, int mode, int stride, float edge, const float* inv_K,
+                         const float* cam_to_world, const void* colour, const int64_t* colour_off, int colour_mode,
+                         float* xyz, uint8_t* rgb, int64_t* index, long capacity, int64_t* cursor, int64_t* counts,
+                         void* workspace, void* stream);
+int ppea_pose_accumulate_f32(float* world, const float* pose, const uint8_t* present, int B, int F, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * KITTI ground truth from raw LiDAR (kitti_utils.py:50-102 generate_depth_map, export_gt_depth.py), ABI 25: B velodyne scans
  * projected into B sparse depth maps, written into the flat layout ppea_depth_errors_f32 reads.  csrc/kitti_gt.hip.
  *   points [sum N][4] fp32 (device): the scans one after another, x forward; column 3 is ignored (the reference sets it to 1);

@@ -15,6 +15,7 @@
 //                dword of the output and writes them as three dwords, the pixels of a quad that belong to no image or to a
 //                neighbouring one are left alone (the first and last quad of an image are written byte by byte)
 #include "common.h"
+#include "export_sample.h"
 
 namespace {
 
@@ -24,51 +25,10 @@ constexpr int SEL_THREADS = 1024;
 constexpr int NSEL = 3;                     // rank 0, the percentile's lower and upper neighbour
 constexpr int BINS = 256;
 
-struct Target {
-    long off;              // first pixel of the image in the flat output
-    int H, W;
-    long size;             // H * W, 0 for a row that does not fit
-};
-
-__device__ __forceinline__ Target target_of(const int64_t* __restrict__ table, int b, long out_len) {
-    Target t;
-    t.off = table[b * 3];
-    const long H = table[b * 3 + 1], W = table[b * 3 + 2];
-    t.H = (int)H, t.W = (int)W;
-    t.size = H * W;
-    if (H <= 0 || W <= 0 || H > 0x7fffffffL / W || t.off < 0 || t.off > out_len || t.size > out_len - t.off) t.size = 0;
-    return t;
-}
-
-// Source index and weights for one axis, eval_metrics.hip's `source` with the coordinate s = max((o + 0.5) n_in / n_out -
-// 0.5, 0) taken in fp64 and the weight s - i0 rounded once to fp32: an fp32 coordinate near column 640 is 4e-5 off, which
-// at a noisy pixel is more than the 1e-5 the exported depth is held to; the interpolation itself stays fp32.
-__device__ __forceinline__ void source(double scale, int dst, int in, int& i0, int& step, float& l0, float& l1) {
-    double s = ((double)dst + 0.5) * scale - 0.5;
-    s = s < 0.0 ? 0.0 : s;
-    i0 = min((int)s, in - 1);
-    step = i0 < in - 1 ? 1 : 0;
-    l1 = fminf(fmaxf((float)(s - (double)i0), 0.f), 1.f);
-    l0 = 1.f - l1;
-}
-
-// The resized value of plane p [h][w] at pixel i of a [H][W] target.  RECIP: the reciprocals of the four sources are
-// interpolated (val_ddad resizes the depth).
-template <bool RECIP>
-__device__ __forceinline__ float sample(const float* __restrict__ p, int h, int w, const Target& t, double sy, double sx,
-                                        int i) {
-    if (t.H == h && t.W == w) return RECIP ? 1.f / p[i] : p[i];
-    const int y = i / t.W, x = i - y * t.W;
-    int yi, yp, xi, xp;
-    float ly0, ly1, lx0, lx1;
-    source(sy, y, h, yi, yp, ly0, ly1);
-    source(sx, x, w, xi, xp, lx0, lx1);
-    const float* row0 = p + (long)yi * w;
-    const float* row1 = row0 + (long)yp * w;
-    float a = row0[xi], c = row0[xi + xp], e = row1[xi], f = row1[xi + xp];
-    if (RECIP) a = 1.f / a, c = 1.f / c, e = 1.f / e, f = 1.f / f;
-    return ly0 * (lx0 * a + lx1 * c) + ly1 * (lx0 * e + lx1 * f);
-}
+using export_sample::Target;
+using export_sample::target_of;
+using export_sample::sample;
+using export_sample::depth_of;
 
 __device__ __forceinline__ void put_depth(float* p, float d) { *p = d; }
 // np.uint16(depth * 256): truncation of the fp32 product (depth <= hi, hi * 256 <= 65535 checked by the launcher)
@@ -90,7 +50,7 @@ __global__ __launch_bounds__(THREADS) void disp_export(const float* __restrict__
         const long i = base + it * THREADS + threadIdx.x;
         if (i >= t.size) break;
         const float r = sample<RECIP>(p, h, w, t, sy, sx, (int)i);
-        float d = RECIP ? sc * r : sc / r;
+        float d = depth_of<RECIP>(sc, r);
         d = d < lo ? lo : d;                  // np.clip: a NaN stays a NaN
         d = d > hi ? hi : d;
         put_depth(out + t.off + i, d);

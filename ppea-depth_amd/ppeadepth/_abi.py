@@ -12,7 +12,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "libppea_depth.so")
 
-ABI_VERSION = 31
+ABI_VERSION = 32
 
 _vp, _i, _l, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_long, ctypes.c_float
 
@@ -218,6 +218,10 @@ SIGNATURES = {
     "ppea_disp_export_u16": [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _l, _f, _f, _i, _vp],
     "ppea_plane_range_f32": [_vp, _vp, _i, _l, ctypes.c_double, _vp],
     "ppea_colorize_u8": [_vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _l, _vp],
+    "ppea_point_cloud_workspace_bytes": [_i, _l, _i],
+    "ppea_point_cloud_f32": [_vp, _vp, _vp, _i, _i, _i, _l, _f, _f, _i, _i, _f, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _l,
+                             _vp, _vp, _vp, _vp],
+    "ppea_pose_accumulate_f32": [_vp, _vp, _vp, _i, _i, _vp],
     "ppea_pack_unit_bytes": [],
     "ppea_pack_segments": [_vp, _i, _l, _vp, _vp],
     "ppea_unpack_segments": [_vp, _i, _l, _vp, _vp],

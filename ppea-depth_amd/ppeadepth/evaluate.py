@@ -63,6 +63,54 @@ def export_depth(pred_disp, size, scale=1.0, lo=1e-3, hi=80.0, mode="disp", dtyp
     return depth
 
 
+def export_points(pred_disp, size, inv_K, color=None, pose=None, scale=1.0, lo=1e-3, hi=80.0, stride=1, edge=0.0,
+                  mode="disp", offset=0):
+    """The host statement of `ops.point_cloud` for one image: pred_disp [h,w] scaled disparity -> (xyz [N,3] fp32, rgb [N,3]
+    uint8 or None, index [N] int64) at size (H, W), float32 arithmetic in the kernel's order.  d = `export_depth` without its
+    clamp; candidates are the pixels with u % stride == v % stride == 0, kept iff lo < d < hi and (edge <= 0 or |d_n - d|
+    <= edge * d for the 4-neighbours inside the image; a NaN neighbour drops nothing); point = pose @ (d * inv_K[:3,:3] @
+    (u, v, 1)), pose None: the camera point.  inv_K, pose: [4,4] (inv_K at THIS size).  color: uint8 [H,W,3], or float
+    [3,H,W] in [0,1] (byte = rint(c * 255) clipped).  index = offset + v * W + u, ascending (raster order)."""
+    H, W = size
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError(f"stride {stride}")
+    f32 = np.float32
+    d = export_depth(pred_disp, size, scale, -np.inf, np.inf, mode)
+    lo, hi, edge = f32(lo), f32(hi), f32(edge)
+    with np.errstate(invalid="ignore", over="ignore"):
+        keep = np.zeros((H, W), dtype=bool)
+        keep[::stride, ::stride] = True
+        keep &= (d > lo) & (d < hi)
+        if edge > 0:
+            tol = edge * d
+            keep[:, 1:] &= ~(np.abs(d[:, :-1] - d[:, 1:]) > tol[:, 1:])
+            keep[:, :-1] &= ~(np.abs(d[:, 1:] - d[:, :-1]) > tol[:, :-1])
+            keep[1:] &= ~(np.abs(d[:-1] - d[1:]) > tol[1:])
+            keep[:-1] &= ~(np.abs(d[1:] - d[:-1]) > tol[:-1])
+        v, u = np.nonzero(keep)                                   # raster order
+        dk = d[v, u]
+        fu, fv = u.astype(f32), v.astype(f32)
+        k = np.asarray(inv_K, dtype=f32)
+        c = [((k[i, 0] * fu + k[i, 1] * fv) + k[i, 2]) * dk for i in range(3)]
+        if pose is not None:
+            m = np.asarray(pose, dtype=f32)
+            c = [((m[i, 0] * c[0] + m[i, 1] * c[1]) + m[i, 2] * c[2]) + m[i, 3] for i in range(3)]
+    xyz = np.stack(c, 1).astype(f32) if len(v) else np.zeros((0, 3), f32)
+    rgb = None
+    if color is not None:
+        color = np.asarray(color)
+        if color.dtype == np.uint8:
+            if color.shape != (H, W, 3):
+                raise ValueError(f"uint8 colour {color.shape}, expected {(H, W, 3)}")
+            rgb = color[v, u]
+        else:
+            if color.shape != (3, H, W):
+                raise ValueError(f"float colour {color.shape}, expected {(3, H, W)}")
+            rgb = np.clip(np.rint(color.astype(f32)[:, v, u].T * f32(255)), 0, 255).astype(np.uint8)
+    return xyz, rgb, offset + v.astype(np.int64) * W + u.astype(np.int64)
+
+
 def eigen_crop_mask(gt_depth):
     """trainer.py:804-811: valid LiDAR returns inside Garg/Eigen's crop."""
     gt_height, gt_width = gt_depth.shape[:2]

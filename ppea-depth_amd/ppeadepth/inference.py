@@ -480,6 +480,120 @@ class DepthPredictor:
         return ops.host_export([export_depth(planes[b], hw[b], sc[b], lo, hi, mode, np_dtype) for b in range(B)], hw, out)
 
 
+    @torch.no_grad()
+    def points(self, disp, sizes, inv_K, color=None, color_offsets=None, pose=None, scale=1.0, lo=1e-3, hi=80.0, stride=1,
+               edge=0.0, mode="disp", capacity=None, out=None, min_depth=None, max_depth=None):
+        """3D points at the frames' own sizes from the network's disparity `disp` [B,1,h,w]: the disparity is scaled as in
+        `depth` (`layers.disp_to_depth`) and handed to `ops.point_cloud` (there: sizes, scale, lo / hi, stride, edge, mode,
+        capacity, out and the `ops.PointCloud` that is returned).  inv_K [B,4,4] at each frame's OWN size (`full_inv_K`);
+        pose [B,4,4] camera-to-world or None (the camera frame); color: the frames' uint8 HWC bytes in one buffer
+        (color_offsets [B] int64 byte offsets, None: back to back) or fp32 [B,3,H,W] in [0,1].  A call of its own on the
+        current stream: it can be captured after a `predict*` or a `push`.  A device="cpu" predictor computes the same in
+        numpy (`evaluate.export_points`)."""
+        from .layers import disp_to_depth
+        scaled, _ = disp_to_depth(disp.float(), self.opt.min_depth if min_depth is None else min_depth,
+                                  self.opt.max_depth if max_depth is None else max_depth)
+        if not self.cpu:
+            return ops.point_cloud(scaled.contiguous(), sizes, inv_K, pose, color, color_offsets, scale, lo, hi, stride, edge,
+                                   mode, capacity, out)
+        import numpy as np
+        from .evaluate import export_points
+        planes = ops._planes(scaled, "points").numpy()
+        B = planes.shape[0]
+        hw = ops.target_sizes(sizes, B)
+        rows, _ = ops.target_rows(hw)
+        sc = scale.tolist() if torch.is_tensor(scale) else [scale] * B
+        parts = []
+        for b, (H, W) in enumerate(hw):
+            col = None
+            if color is not None and color.dtype == torch.uint8:
+                off = rows[b][0] * 3 if color_offsets is None else int(color_offsets[b])
+                col = color.reshape(-1)[off:off + H * W * 3].view(H, W, 3).numpy()
+            elif color is not None:
+                col = color[b].float().numpy()
+            parts.append(export_points(planes[b], (H, W), inv_K[b].numpy(), col, None if pose is None else pose[b].numpy(),
+                                       sc[b], lo, hi, stride, edge, mode, rows[b][0]))
+        if out is None:
+            out = ops.new_point_cloud(ops.candidate_count(hw, int(stride)) if capacity is None else int(capacity), B, "cpu",
+                                      color is not None)
+        cap = out.xyz.shape[0]
+        start, dropped = out.cursor.tolist()
+        total = sum(len(x[2]) for x in parts)
+        fit = min(total, cap - start)
+        out.xyz[start:start + fit] = torch.from_numpy(np.concatenate([x[0] for x in parts])[:fit])
+        out.index[start:start + fit] = torch.from_numpy(np.concatenate([x[2] for x in parts])[:fit])
+        if color is not None:
+            out.rgb[start:start + fit] = torch.from_numpy(np.concatenate([x[1] for x in parts])[:fit])
+        out.cursor[0], out.cursor[1] = start + fit, dropped + total - fit
+        out.counts.copy_(torch.tensor([len(x[2]) for x in parts]))
+        return out
+
+    def full_inv_K(self, K_norm, sizes):
+        """The loaders' normalised intrinsics (3x3 or 4x4, one matrix or B of them: kitti_dataset.py:26-29, row 0 in units of
+        the width, row 1 of the height) -> [B,4,4] fp32 inverse intrinsics at each frame's own size `sizes` ((H, W) or B
+        pairs), on the predictor's device: what `points` takes.  The inverse is taken in float64 on the host and rounded
+        once."""
+        import numpy as np
+        K = np.asarray(K_norm.cpu() if torch.is_tensor(K_norm) else K_norm, dtype=np.float64)
+        if K.ndim not in (2, 3) or K.shape[-2:] not in ((3, 3), (4, 4)):
+            raise PpeaKernelError(f"K_norm {K.shape}: 3x3 or 4x4 intrinsics, one matrix or a batch")
+        single = len(sizes) == 2 and not hasattr(sizes[0], "__len__")
+        B = K.shape[0] if K.ndim == 3 else 1 if single else len(sizes)
+        hw = ops.target_sizes(sizes, B)
+        inv = np.empty((B, 4, 4), dtype=np.float32)
+        for b, (H, W) in enumerate(hw):
+            full = np.eye(4)
+            k = K[b] if K.ndim == 3 else K
+            full[:k.shape[0], :k.shape[1]] = k
+            full[0] *= W
+            full[1] *= H
+            inv[b] = np.linalg.inv(full)
+        return torch.from_numpy(inv).to(self.device)
+
+
+class StreamMap:
+    """One fused point cloud of a `DepthStream`: the points of every pushed frame, at the network's size, in the frame of each
+    camera's first frame since its reset, appended to ONE shared `ops.PointCloud` of `capacity` points.
+
+    `world` [B,4,4] fp32 is the camera-to-world matrix of each camera's newest frame, identity at the start.  `add` multiplies
+    it from the right with the push's `pose[:, 0]` (the transform 0 -> -1: X_{t-1} = T X_t, so X_world = W_{t-1} T X_t) where
+    `present[:, 0]`, and sets it to the identity where the camera has just been reset.  It is a plain fp32 product chain with
+    no re-orthonormalisation: after n frames element ij is within n * 1e-6 * max(1, max_i sum_j |W_ij|) of the float64
+    product of the same fp32 poses (4 products and 3 sums of at most one ulp of the absolute-value sum per step).  Loop
+    closure, voxel fusion and scale alignment between clips are not done here."""
+
+    def __init__(self, stream, capacity, stride=4, edge=0.1, lo=1e-3, hi=80.0, scale=1.0):
+        self.s = stream
+        self.kw = dict(stride=stride, edge=edge, lo=lo, hi=hi, scale=scale)
+        d = stream.p.device
+        self.world = torch.eye(4, device=d).repeat(stream.B, 1, 1).contiguous()
+        self._cloud = ops.new_point_cloud(int(capacity), stream.B, d, True)
+
+    @torch.no_grad()
+    def add(self, out, color, inv_K):
+        """out: what `push` returned for `color` [B,3,H,W]; inv_K [B,4,4] at the network's size (full resolution, not the
+        matching scale).  Two kernels' worth of launches on the current stream, nothing read on the host: capturable."""
+        s = self.s
+        if s.p.cpu:
+            W, P = self.world.clone(), out["pose"][:, 0].float()
+            new = ((W[:, :, 0:1] * P[:, 0:1] + W[:, :, 1:2] * P[:, 1:2]) + W[:, :, 2:3] * P[:, 2:3]) + W[:, :, 3:4] * P[:, 3:4]
+            self.world.copy_(torch.where(out["present"][:, 0].bool()[:, None, None], new, torch.eye(4).expand_as(new)))
+        else:
+            ops.pose_accumulate(self.world, out["pose"], out["present"])
+        s.p.points(out["disp"], (s.H, s.W), inv_K, color=color, pose=self.world, out=self._cloud, **self.kw)
+        return self
+
+    def cloud(self):
+        """The shared `ops.PointCloud` (`.trim()` reads its fill once)."""
+        return self._cloud
+
+    def clear(self):
+        """Empties the buffer and puts every camera's `world` back to the identity."""
+        self._cloud.clear()
+        self.world.copy_(torch.eye(4, device=self.world.device).expand_as(self.world))
+        return self
+
+
 class DepthStream:
     """Video streaming on a `DepthPredictor`: `push` takes the NEXT frame of each of B cameras and matches it against the last
     F frames, whose stage-0 features, pose pairs and images it kept from the earlier pushes -- stem + stage 0 run on B items
@@ -599,6 +713,10 @@ class DepthStream:
         if what not in ("disp", "lowest_cost"):
             raise PpeaKernelError(f"render: what {what!r}, expected 'disp' or 'lowest_cost'")
         return self.p.render(out[what], size, **kw)
+
+    def map(self, capacity, stride=4, edge=0.1, lo=1e-3, hi=80.0, scale=1.0):
+        """A `StreamMap` of `capacity` points fed by this stream's pushes: `m.add(push(...), color, inv_K)`."""
+        return StreamMap(self, capacity, stride, edge, lo, hi, scale)
 
     def capture(self):
         """One torch.cuda.graph over static buffers for a whole push, state update included (single stream, no parallel

@@ -6,6 +6,7 @@ Reference call sites are cited per op (paths relative to /root/reference/ppeadep
 import ctypes as _ct
 import os
 import weakref
+from typing import NamedTuple as _NamedTuple, Optional
 
 import torch
 import torch.distributed as dist
@@ -949,6 +950,154 @@ def colorize(x, sizes, rng, lut, out=None):
     call("ppea_colorize_u8", xp, ptr(rng, _F32), ptr(lut, torch.uint8), ptr(table, torch.int64), ptr(o, torch.uint8), total, B,
          h, w, largest, stream_ptr())
     return o.view(B, *dense, 3) if dense is not None else (o.view(-1, 3), table)
+
+
+# ---------------------------------------------------------------------------------------------
+# Point clouds: 3D points from a predicted plane, the pose chain of a stream   (csrc/point_cloud.hip)
+# ---------------------------------------------------------------------------------------------
+_POINT_WS = {}      # (B, largest image, stride, device) -> workspace; built once, so that a captured call allocates nothing
+_COLOUR_OFFS = {}   # (sizes, device) -> [B] int64 byte offsets of back-to-back HWC frames
+
+
+class PointCloud(_NamedTuple):
+    """What `point_cloud` fills: xyz [capacity,3] fp32, rgb [capacity,3] uint8 or None, index [capacity] int64 (the flat
+    target pixel offset_b + v * W + u), cursor [2] int64 = (points held, points that did not fit), counts [B] int64 = kept
+    pixels per image of the last call, fitted or not.  All on the device; nothing of it has been read."""
+    xyz: torch.Tensor
+    rgb: Optional[torch.Tensor]
+    index: torch.Tensor
+    cursor: torch.Tensor
+    counts: torch.Tensor
+
+    def trim(self):
+        """-> (xyz [N,3], rgb [N,3] or None, index [N], dropped): views of the filled part and the number of points that
+        did not fit.  Reads `cursor` once (the only copy to the host)."""
+        n, dropped = self.cursor.tolist()
+        return self.xyz[:n], None if self.rgb is None else self.rgb[:n], self.index[:n], dropped
+
+    def clear(self):
+        """Empties the buffers (on the stream: capturable)."""
+        self.cursor.zero_()
+        return self
+
+
+def candidate_count(hw, stride):
+    """Pixels with u % stride == v % stride == 0 of the (H, W) pairs."""
+    return sum(((h - 1) // stride + 1) * ((w - 1) // stride + 1) for h, w in hw)
+
+
+def new_point_cloud(capacity, B, device, colour=True):
+    """An empty `PointCloud` for `capacity` points and calls of B images."""
+    return PointCloud(torch.empty(capacity, 3, device=device, dtype=_F32),
+                      torch.empty(capacity, 3, device=device, dtype=torch.uint8) if colour else None,
+                      torch.empty(capacity, device=device, dtype=torch.int64),
+                      torch.zeros(2, device=device, dtype=torch.int64), torch.zeros(B, device=device, dtype=torch.int64))
+
+
+def _matrices(m, B, what):
+    if tuple(m.shape) != (B, 4, 4):
+        raise _abi.PpeaKernelError(f"{what} {tuple(m.shape)}, expected {(B, 4, 4)}")
+    return ptr(m, _F32)
+
+
+@torch.no_grad()
+def point_cloud(pred, sizes, inv_K, cam_to_world=None, colour=None, colour_off=None, scale=1.0, lo=1e-3, hi=80.0, stride=1,
+                edge=0.0, mode="disp", capacity=None, out=None):
+    """pred [B,h,w] fp32 scaled disparity -> the 3D points of its depth at `sizes` ((H, W) or B pairs): d = the depth
+    `disp_export` computes before its clamp (sizes, scale, mode as there; bit-equal).  Candidates are the pixels with
+    u % stride == v % stride == 0; one is kept iff lo < d < hi and (edge <= 0 or |d_n - d| <= edge * d for its 4-neighbours
+    in the image).  Point = cam_to_world[b] @ (d * inv_K[b][:3,:3] @ (u, v, 1)), fp32; inv_K [B,4,4] at each image's TARGET
+    size, cam_to_world [B,4,4] or None (the camera frame).  colour: uint8 HWC frames at the target sizes in one buffer
+    (colour_off [B] int64 device byte offsets; None: back to back) or fp32 [B,3,H,W] in [0,1] (all sizes equal).
+    -> `PointCloud`: points in image order, raster order inside an image, deterministic.  capacity: None = the number of
+    candidates (nothing can be dropped).  out: a `PointCloud` to append to (its capacity holds).  Three launches, no host
+    read; the workspace is kept per (B, largest image, stride, device)."""
+    pred = _planes(pred, "point_cloud")
+    B, h, w = pred.shape
+    dev = pred.device
+    p = ptr(pred, _F32)
+    if mode not in EXPORT_MODES:
+        raise _abi.PpeaKernelError(f"point_cloud: mode {mode!r}, expected one of {sorted(EXPORT_MODES)}")
+    stride = int(stride)
+    if stride < 1:
+        raise _abi.PpeaKernelError(f"point_cloud: stride {stride}")
+    if torch.is_tensor(scale):
+        if tuple(scale.shape) != (B,):
+            raise _abi.PpeaKernelError(f"scale {tuple(scale.shape)} for a batch of {B}")
+        sc = scale
+    else:
+        key = (float(scale), B, dev)
+        if key not in _SCALES:
+            _SCALES[key] = torch.full((B,), float(scale), device=dev, dtype=_F32)
+        sc = _SCALES[key]
+    table, dense, total, largest = export_targets(sizes, B, dev)
+    hw = target_sizes(sizes, B)
+    kp = _matrices(inv_K, B, "inv_K")
+    mp = None if cam_to_world is None else _matrices(cam_to_world, B, "cam_to_world")
+    cmode, cp, op = 0, None, None
+    if colour is not None:
+        if colour.dtype == torch.uint8:
+            cmode = 1
+            if colour_off is None:
+                if colour.numel() != total * 3:
+                    raise _abi.PpeaKernelError(f"colour: {colour.numel()} bytes for {total} pixels")
+                key = (hw, dev)
+                if key not in _COLOUR_OFFS:
+                    _COLOUR_OFFS[key] = (table[:, 0] * 3).contiguous()
+                colour_off = _COLOUR_OFFS[key]
+            elif tuple(colour_off.shape) != (B,):
+                raise _abi.PpeaKernelError(f"colour_off {tuple(colour_off.shape)} for a batch of {B}")
+            cp, op = ptr(colour, torch.uint8), ptr(colour_off, torch.int64)
+        elif colour.dtype == _F32:
+            cmode = 2
+            if dense is None or tuple(colour.shape) != (B, 3, *dense):
+                raise _abi.PpeaKernelError(f"fp32 colour {tuple(colour.shape)} needs every target equal to its (H, W); "
+                                           f"targets {hw}")
+            cp = ptr(colour, _F32)
+        else:
+            raise _abi.PpeaKernelError(f"colour {colour.dtype}: uint8 HWC frames or fp32 [B,3,H,W]")
+    if out is None:
+        cap = candidate_count(hw, stride) if capacity is None else int(capacity)
+        if cap < 0:
+            raise _abi.PpeaKernelError(f"point_cloud: capacity {cap}")
+        out = new_point_cloud(cap, B, dev, cmode != 0)
+    else:
+        cap = out.xyz.shape[0]
+        if capacity is not None and int(capacity) != cap:
+            raise _abi.PpeaKernelError(f"point_cloud: capacity {capacity}, out holds {cap}")
+        if tuple(out.xyz.shape) != (cap, 3) or tuple(out.index.shape) != (cap,) or tuple(out.cursor.shape) != (2,) \
+                or tuple(out.counts.shape) != (B,) or (cmode != 0 and (out.rgb is None or tuple(out.rgb.shape) != (cap, 3))):
+            raise _abi.PpeaKernelError(f"point_cloud: out does not fit {cap} points of {B} images"
+                                       f"{' with colour' if cmode else ''}")
+    key = (B, largest, stride, dev)
+    if key not in _POINT_WS:
+        nbytes = _abi.lib.ppea_point_cloud_workspace_bytes(B, largest, stride)
+        if nbytes < 0:
+            _abi.check(int(nbytes), "ppea_point_cloud_workspace_bytes")
+        _POINT_WS[key] = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+    call("ppea_point_cloud_f32", p, ptr(sc, _F32), ptr(table, torch.int64), B, h, w, largest, float(lo), float(hi),
+         EXPORT_MODES[mode], stride, float(edge), kp, mp, cp, op, cmode, ptr(out.xyz, _F32),
+         ptr(out.rgb, torch.uint8) if cmode else None, ptr(out.index, torch.int64), cap, ptr(out.cursor, torch.int64),
+         ptr(out.counts, torch.int64), ptr(_POINT_WS[key], torch.uint8), stream_ptr())
+    return out
+
+
+@torch.no_grad()
+def pose_accumulate(world, pose, present):
+    """world [B,4,4] fp32, in place: world[b] @ pose[b,0] where present[b,0], the identity elsewhere.  pose [B,F,4,4] and
+    present [B,F] bool are a stream push's; pose[b,0] maps frame t to frame t-1, so `world` stays the camera-to-world matrix
+    of the newest frame, the clip's first frame being the world.  A plain fp32 product chain (fixed summation order, no
+    re-orthonormalisation).  One launch."""
+    B = world.shape[0]
+    if tuple(world.shape) != (B, 4, 4) or pose.dim() != 4 or tuple(pose.shape) != (B, pose.shape[1], 4, 4) \
+            or pose.shape[1] < 1 or tuple(present.shape) != tuple(pose.shape[:2]):
+        raise _abi.PpeaKernelError(f"pose_accumulate: world {tuple(world.shape)}, pose {tuple(pose.shape)}, present "
+                                   f"{tuple(present.shape)}")
+    if present.dtype == torch.bool:
+        present = present.view(torch.uint8)
+    call("ppea_pose_accumulate_f32", ptr(world, _F32), ptr(pose, _F32), ptr(present, torch.uint8), B, pose.shape[1],
+         stream_ptr())
+    return world
 
 
 # ---------------------------------------------------------------------------------------------

@@ -8,11 +8,13 @@ Each product can be switched on alone; file n belongs to line n of the split fil
   --benchmark   OUT/benchmark/<n>.png   the KITTI depth benchmark's 16-bit PNG of depth * 256 at 352x1216, --scale (5.4)
                                         (eval_depth_ori.py:318-333)
   --colour      OUT/colour/<n>.png      the disparity through --cmap at the frame's own size, range minimum .. --percentile
+  --ply         OUT/ply/<n>.ply         the frame's 3D points in the camera frame at its own size, coloured with the frame's
+                                        bytes (binary PLY; same scale and clamp as --depth_npy; --ply_stride, --ply_edge)
 --teacher predicts with the single-frame network instead of the multi-frame one.  Every other flag is a model option
 (`options.MonodepthOptions`: --height, --width, --adapter, --num_matching_frames, ...) and must describe the checkpoint.
 
 The frames are read by `datasets.KITTIRAWDataset` at their own sizes and resized by `DeviceInputPipeline(None, ...)`; the
-per-pixel work of every product is a HIP launch (`DepthPredictor.depth` / `.render`), one copy to the host per batch and
+per-pixel work of every product is a HIP launch (`DepthPredictor.depth` / `.render` / `.points`), one copy to the host per batch and
 product, and Pillow writes the files.
 """
 import argparse
@@ -37,6 +39,9 @@ def _parser():
     a("--colour", action="store_true")
     a("--cmap", default="plasma")
     a("--percentile", type=float, default=95.0)
+    a("--ply", action="store_true")
+    a("--ply_stride", type=int, default=1, help="every n-th row and column becomes a point")
+    a("--ply_edge", type=float, default=0.0, help="drop points whose depth differs from a neighbour's by more than this share")
     a("--png", action="store_true", help="the frames are .png files (default .jpg)")
     a("--device", default=None)
     a("--fp32", action="store_true", help="predict in fp32 (default bf16)")
@@ -70,8 +75,8 @@ def main(argv=None):
     options.apply_ddad(opt)
     if not opt.load_weights_folder:
         raise SystemExit("--load_weights_folder is required")
-    if not (args.depth_npy or args.benchmark or args.colour):
-        raise SystemExit("nothing to write: give --depth_npy, --benchmark and / or --colour")
+    if not (args.depth_npy or args.benchmark or args.colour or args.ply):
+        raise SystemExit("nothing to write: give --depth_npy, --benchmark, --colour and / or --ply")
     device = torch.device(args.device if args.device else ("cuda" if torch.cuda.is_available() else "cpu"))
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -84,7 +89,7 @@ def main(argv=None):
     data = datasets.KITTIRAWDataset(args.data_path, lines, ids, ".png" if args.png else ".jpg")
     pipe = DeviceInputPipeline(None, opt.height, opt.width, device, frame_idxs=tuple(ids), is_train=False)
     dirs = {k: os.path.join(args.out, k) for k, on in (("depth", args.depth_npy), ("benchmark", args.benchmark),
-                                                       ("colour", args.colour)) if on}
+                                                       ("colour", args.colour), ("ply", args.ply)) if on}
     for d in dirs.values():
         os.makedirs(d, exist_ok=True)
     tracker = trainer.depth_bin_tracker
@@ -93,6 +98,10 @@ def main(argv=None):
         B = frames.batch
         desc = frames.desc.view(len(ids), B, 4)
         sizes = [(int(h), int(w)) for h, w in desc[0, :, 1:3].tolist()]
+        if args.ply:
+            # the frames' bytes go to the device here instead of inside the pipeline (still the one copy): the points take
+            # their colour from them
+            frames.buf = frames.buf.to(device, non_blocking=True)
         inputs = pipe(frames)
         color0 = inputs[("color", 0, 0)]
         if args.teacher:
@@ -116,6 +125,18 @@ def main(argv=None):
             imgs = _images(p.render(disp, sizes, percentile=args.percentile, cmap=args.cmap), B)
             for n, m in zip(names, imgs):
                 save_png(os.path.join(dirs["colour"], n + ".png"), m)
+        if args.ply:
+            from . import vis
+            from .input_pipeline import KITTI_K
+            cloud = p.points(disp, sizes, p.full_inv_K(getattr(data, "K", KITTI_K), sizes), color=frames.buf,
+                             color_offsets=desc[0, :, 0].to(device, torch.int64).contiguous(),
+                             scale=opt.pred_depth_scale_factor, stride=args.ply_stride, edge=args.ply_edge)
+            # one copy of the batch's points (and one of the B counts that split them)
+            xyz, rgb, _, _ = (t.cpu().numpy() if torch.is_tensor(t) else t for t in cloud.trim())
+            ends = np.cumsum(cloud.counts.cpu().numpy())
+            for b, n in enumerate(names):
+                lo_, hi_ = int(ends[b - 1]) if b else 0, int(ends[b])
+                vis.write_ply(os.path.join(dirs["ply"], n + ".ply"), xyz[lo_:hi_], rgb[lo_:hi_])
     return 0
 
 

@@ -5,6 +5,8 @@ the GPU (ops.plane_range + ops.colorize), optionally at another size.  Both look
 shipped next to this file (`colormaps.json`, written by tools/gen_colormaps.py from matplotlib's listed colormaps), so the
 package does not need matplotlib at run time; the lookup is matplotlib's `Colormap.__call__(bytes=True)`:
 row floor(x * 256), x < 0 row 0, x >= 1 row 255, NaN the bytes (0, 0, 0).
+
+`write_ply` / `read_ply` keep a point cloud (`DepthPredictor.points`) as a binary little-endian PLY file.
 """
 import json
 import os
@@ -104,3 +106,59 @@ def colorize_device(value, size=None, vmin=None, vmax=None, percentile=100.0, cm
             if vmax is None else np.float32(vmax)
         imgs.append(colorize(p if (H, W) == (h, w) else resize_linear(p, W, H), lo, hi, cmap))
     return ops.host_export(imgs, sizes, out)
+
+
+def _ply_header(n, colour):
+    lines = ["ply", "format binary_little_endian 1.0", f"element vertex {n}", "property float x", "property float y",
+             "property float z"]
+    if colour:
+        lines += ["property uchar red", "property uchar green", "property uchar blue"]
+    return lines + ["end_header"]
+
+
+def _ply_dtype(colour):
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    return np.dtype(fields + ([("red", "u1"), ("green", "u1"), ("blue", "u1")] if colour else []))
+
+
+def write_ply(path, xyz, rgb=None):
+    """xyz [N,3] float32 (and rgb [N,3] uint8) -> a binary little-endian PLY file: `float x y z`, then `uchar red green
+    blue` when colour is given; 12 or 15 bytes per point.  N = 0 is a valid file.  Arrays or host tensors."""
+    xyz = np.asarray(xyz, dtype=np.float32)
+    if xyz.ndim != 2 or xyz.shape[1] != 3:
+        raise ValueError(f"xyz {xyz.shape}: expected [N,3]")
+    rec = np.empty(xyz.shape[0], dtype=_ply_dtype(rgb is not None))
+    rec["x"], rec["y"], rec["z"] = xyz[:, 0], xyz[:, 1], xyz[:, 2]
+    if rgb is not None:
+        rgb = np.asarray(rgb)
+        if rgb.dtype != np.uint8 or rgb.shape != xyz.shape:
+            raise ValueError(f"rgb {rgb.dtype} {rgb.shape} for xyz {xyz.shape}: expected uint8 of the same shape")
+        rec["red"], rec["green"], rec["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    with open(path, "wb") as f:
+        f.write(("\n".join(_ply_header(xyz.shape[0], rgb is not None)) + "\n").encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def read_ply(path):
+    """A file `write_ply` wrote -> (xyz [N,3] float32, rgb [N,3] uint8 or None)."""
+    with open(path, "rb") as f:
+        lines = []
+        while not lines or lines[-1] != "end_header":
+            line = f.readline()
+            if not line:
+                raise ValueError(f"{path}: no end_header")
+            lines.append(line.decode("ascii").rstrip("\n"))
+        payload = f.read()
+    if len(lines) < 3 or not lines[2].startswith("element vertex "):
+        raise ValueError(f"{path}: not a vertex-only PLY file")
+    n = int(lines[2].split()[2])
+    colour = len(lines) > 7
+    if lines != _ply_header(n, colour):
+        raise ValueError(f"{path}: a PLY layout write_ply does not write")
+    dt = _ply_dtype(colour)
+    if len(payload) != n * dt.itemsize:
+        raise ValueError(f"{path}: {len(payload)} payload bytes for {n} points of {dt.itemsize} bytes")
+    rec = np.frombuffer(payload, dtype=dt)
+    xyz = np.stack([rec["x"], rec["y"], rec["z"]], 1).astype(np.float32) if n else np.zeros((0, 3), np.float32)
+    rgb = (np.stack([rec["red"], rec["green"], rec["blue"]], 1) if n else np.zeros((0, 3), np.uint8)) if colour else None
+    return xyz, rgb
