@@ -56,21 +56,19 @@ def arm_of_plan(p, K, KS, mode):
 
 
 _BM_HN = {29: ((24, 4), (24, 5)), 27: ((12, 1), (12, 2), (12, 3)), 13: ((6, 1), (6, 2), (6, 3))}
-# every instantiation csrc/dwconv_mfma.hip builds: 75 row-band + 25 batch-major
+# every instantiation csrc/dwconv_mfma.hip builds: 74 row-band + 25 batch-major
 ALL_ARMS = frozenset(
     [rb(K, KS, m, s) for K in KS_ALL for KS in (0, 5) for m in (0, 1) for s in (2, 3, 5)]
     + [rb(K, 5, 0, s, BN=1) for K in KS_ALL for s in (2, 3, 5)]
     + [rb(K, 0, 0, s, BA=1) for K in KS_ALL for s in (2, 3, 5)]
-    + [rb(31, 5, 0, 5, WS=1), rb(31, 5, 0, 5, BN=1, WS=1), rb(31, 5, 1, 5, WS=1)]
+    + [rb(31, 5, 0, 5, WS=1), rb(31, 5, 0, 5, BN=1, WS=1)]
     + [bm(K, m, H, n, BN) for K, hn in _BM_HN.items() for H, n in hn for m, BN in ((0, 0), (0, 1), (1, 0))]
     + [bm(31, 1, 48, 2)])
-# built but never launched (found by the plan sweep of tests/test_dwconv_arms_cpu.py; the reasons are worked out there)
-UNREACHABLE = {
-    rb(31, 5, 1, 5, WS=1): "two staged inputs: 2 tiles x 78 rows x 288 B x 4 waves = 179 712 B > the 160 KB limit, so the band "
-                           "search settles on 32 and launch() refuses window sharing (it needs band == 48)",
-}
-# launch outcomes of the host plan that no shape of the sweep reaches
-UNREACHED_OUTCOMES = {"band": (16,), "gi": (8, 4)}
+# built but never launched: nothing (the kernel asserts that the data gradient has no window-sharing instantiation)
+UNREACHABLE = {}
+# launch outcomes of the host plan that no shape of the sweep reaches: none (the plans assert that their searches end
+# at band 32 and at groups of 12 images)
+UNREACHED_OUTCOMES = {"band": (), "gi": ()}
 
 
 def _r(name, shape, K, KS=5, mode=0, variant="plain", relu=False, arm=None, **claims):
@@ -161,13 +159,13 @@ WS_CASES = (
     _r("ws_ipw2", (1, 1024, 48, 104), 31, arm=rb(31, 5, 0, 5, WS=1), ipw=2, wpc=1),
     _r("ws_48x64_stats", (1, 2, 48, 64), 31, variant="stats", arm=rb(31, 5, 0, 5, WS=1)),
     _r("ws_96x80_stats", (2, 2, 96, 80), 31, variant="stats", arm=rb(31, 5, 0, 5, WS=1), bands=2),
-    # not window sharing: H % 48 != 0, and the data gradient (see UNREACHABLE)
+    # not window sharing: H % 48 != 0, and the data gradient (its band is 32: see the static_assert in the kernel)
     _r("ws_refused_h50", (1, 2, 50, 64), 31, arm=rb(31, 5, 0, 5), bands=2),
     _r("ws_refused_dgrad", (1, 2, 96, 64), 31, 5, 1, arm=rb(31, 5, 1, 5), band=32),
 )
 
 
-# batch-major: every (K, H, NTX) of launch_bm_w in both modes + the 48-row data gradient; N < gi, N % gi != 0, C % CPW != 0
+# batch-major: every (K, H, NTX) of choose_bm in both modes + the 48-row data gradient; N < gi, N % gi != 0, C % CPW != 0
 # (CPW = 4, 2, 1, 1 channels per workgroup at H = 6, 12, 24, 48), VEC 8 / 4, gi 16 / 12
 def _bm_cases():
     rows = []

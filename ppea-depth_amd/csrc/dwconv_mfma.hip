@@ -350,49 +350,11 @@ __device__ __forceinline__ void ds_read128_async(bf16x8& dst, uint32_t addr) {
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
 }
 
-// Software pipeline of one tile: the A fragments stream through a ring of RING registers, the read of
-// fragment I + DIST is issued right after MFMA I, and every wait names exactly how many younger reads may
-// still be in flight (LDS reads of one wave return in order; lgkmcnt is a 4-bit counter, so DIST <= 15).
-// Two accumulators alternate so that consecutive MFMAs never wait on each other's result.
+// The A fragments stream through a ring of RING registers, the read of fragment I + DIST is issued right after
+// MFMA I, and every wait names exactly how many younger reads may still be in flight (LDS reads of one wave
+// return in order; lgkmcnt is a 4-bit counter, so DIST <= 15).  Two accumulators alternate so that consecutive
+// MFMAs never wait on each other's result.
 constexpr int DIST = 12, RING = 13;
-
-template <int KK, int NS, int ROW0, int STRIDE_B, int I>
-__device__ __forceinline__ void issue_read(bf16x8 (&a)[RING], uint32_t abase) {
-    if constexpr (I < KK * NS) {
-        constexpr int ky = I / NS, sidx = I % NS;
-        ds_read128_async<(ky + ROW0) * STRIDE_B + sidx * 64>(a[I % RING], abase);
-    }
-}
-
-template <int KK, int NS, int ROW0, int STRIDE_B, int... Is>
-__device__ __forceinline__ void issue_first(bf16x8 (&a)[RING], uint32_t abase, std::integer_sequence<int, Is...>) {
-    (issue_read<KK, NS, ROW0, STRIDE_B, Is>(a, abase), ...);
-}
-
-template <int KK, int NS, int ROW0, int STRIDE_B, int I>
-__device__ __forceinline__ void mac_step(f32x4 (&acc)[2], bf16x8 (&a)[RING], uint32_t abase,
-                                         const bf16x8 (&bf)[KK][NS]) {
-    if constexpr (I < KK * NS) {
-        constexpr int TOTAL = KK * NS;
-        constexpr int younger = (TOTAL - 1 - I) < (DIST - 1) ? (TOTAL - 1 - I) : (DIST - 1);
-        asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(a[I % RING]) : "i"(younger));
-        acc[I & 1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[I % RING], bf[I / NS][I % NS], acc[I & 1], 0, 0, 0);
-        issue_read<KK, NS, ROW0, STRIDE_B, I + DIST>(a, abase);
-        mac_step<KK, NS, ROW0, STRIDE_B, I + 1>(acc, a, abase, bf);
-    }
-}
-
-// acc += sum over filter rows of A(rows, chunk) * B(ky, chunk) for one 16x16 tile.
-// `abase` = LDS byte address of (first input row of this lane's output row, first chunk column of
-// the tile) + 16 * (lane >> 4); ROW0 = extra row offset (small kernel inside the big halo).
-template <int KK, int NS, int ROW0, int STRIDE_B>
-__device__ __forceinline__ void tile_mac(f32x4& acc, uint32_t abase, const bf16x8 (&bf)[KK][NS]) {
-    bf16x8 a[RING];
-    f32x4 acc2[2] = {acc, {0.f, 0.f, 0.f, 0.f}};
-    issue_first<KK, NS, ROW0, STRIDE_B>(a, abase, std::make_integer_sequence<int, DIST>{});
-    mac_step<KK, NS, ROW0, STRIDE_B, 0>(acc2, a, abase, bf);
-    acc = acc2[0] + acc2[1];
-}
 
 // ---- cross-tile stream -----------------------------------------------------------------------------------
 // One tile = TOTAL = K*NS (+KS) steps, each one A read + one MFMA.  The read for step I + DIST is issued right
@@ -604,6 +566,9 @@ __global__ __launch_bounds__(64 * WAVES, 1) void dwconv_mfma_kernel(
     long total_waves, int tile_bytes, int region_bytes, float* __restrict__ stats, BnIn bn) {
     static_assert(!BN || MODE == 0, "the fused input BatchNorm is a forward feature");
     static_assert(!BA || (MODE == 0 && KS == 0 && !BN), "bias + activation: forward of the merged filter");
+    // window sharing needs a 48-row band; the data gradient of the pair stages two inputs: 2 tiles x (48 + 30) rows x
+    // 288 B x 4 waves = 179 712 B > the 160 KB of LDS, so its band is 32 on every shape
+    static_assert(!WS || MODE == 0, "window sharing: forward only");
     using GE = Geo<K>;
     using GS = Geo<(KS > 0 ? KS : 5)>;
     constexpr int STRIDE_B = Seg<K, NSEG>::STRIDE;
@@ -949,11 +914,6 @@ __device__ __forceinline__ void stage_bm(uint8_t* tile, const uint16_t* __restri
     }
 }
 
-template <int OFF>
-__device__ __forceinline__ void ds_read128_at(bf16x8& dst, uint32_t addr) {
-    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "i"(OFF));
-}
-
 // The rows of one wave: Y0 + RS * j, j < NY (RS = 1: a contiguous block; RS = number of waves: interleaved, which gives
 // every wave the same number of in-plane (y_in, y_out) pairs on planes taller than the filter's half width).
 template <int K, int KS, int MODE, int H, int NY, int Y0, int RS>
@@ -980,9 +940,9 @@ template <int K, int KS, int MODE, int H, int NY, int Y0, int RS, int YI>
 __device__ __forceinline__ void bm_issue(bf16x8 (&slot)[3], uint32_t ra_big, uint32_t ra_small) {
     using S = BmSched<K, KS, MODE, H, NY, Y0, RS>;
     if constexpr (YI < S::YHI) {
-        ds_read128_at<0>(slot[0], ra_big);
-        if constexpr (Geo<K>::NS == 2) ds_read128_at<64>(slot[1], ra_big);
-        if constexpr (S::small_at(YI) && !S::SHARE) ds_read128_at<0>(slot[2], ra_small);
+        ds_read128_async<0>(slot[0], ra_big);
+        if constexpr (Geo<K>::NS == 2) ds_read128_async<64>(slot[1], ra_big);
+        if constexpr (S::small_at(YI) && !S::SHARE) ds_read128_async<0>(slot[2], ra_small);
     }
 }
 
@@ -1198,28 +1158,65 @@ __global__ __launch_bounds__(256, 1) void dwconv_bm_kernel(
 }
 
 // ---- host plans ----------------------------------------------------------------------------------------------------------
-// Every host decision of a launch is made by ONE plain function per launcher (plan_bm, plan_rb: no device call); the launch
-// passes what it returns to the kernel, and ppea_dwconv_lk_plan reports it (`plan_out` below: do not launch, fill the
-// report).  Layout of the report: include/ppea_depth.h.
+// choose_lk() is the only place that decides: plain host arithmetic (no device call) from (K, KS, mode, variant, shape) to
+// an LkChoice -- the kernel family, its plan (plan_rb / plan_bm), the instantiation, and the one function that launches that
+// instantiation.  The entry points launch what it returns, ppea_dwconv_lk_stats_partials and ppea_dwconv_lk_plan report
+// it (layout of the report: include/ppea_depth.h).
 constexpr int LK_PLAN_INTS = 24;
 
-struct BmPlan { int gi, tile_bytes, tile1_bytes, ngroups, wgpc, cpw, partials; size_t lds; };
+inline BnIn no_bn() { return BnIn{nullptr, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; }
+// the BA kernels read their bias [C] and ReLU flag from the (otherwise unused) BnIn parameter
+inline BnIn bias_act_in(const float* bias, int relu) {
+    BnIn b = no_bn();
+    b.beta = bias;
+    b.P = relu ? 1 : 0;
+    return b;
+}
 
-// returns PPEA_ERR_UNSUPPORTED when the shape is not this variant's (the caller falls back to the row-band kernel)
+struct LkArgs {
+    const uint16_t *in0, *in1, *wb, *ws;     // MODE 0: x, -, packed big / small filter; MODE 1: dy_big, dy_small, flipped filters
+    uint16_t *o0, *o1;                       // MODE 0: y_big, y_small; MODE 1: dx, -
+    int N, C, H, W;
+    hipStream_t st;
+    float* stats;                            // forward: per-wave partial sums for the BatchNorm pair (see the kernel), or null
+    BnIn bn;                                 // no_bn(), the fused input BatchNorm, or bias_act_in(bias, relu)
+};
+
+struct BmPlan { int gi, tile_bytes, tile1_bytes, ngroups, wgpc, cpw, partials; size_t lds; };
+struct RbPlan { int band, G, tile_bytes, region, bands, segs, items_per_channel, wpc, ipw, fast; long total_waves; size_t lds; };
+
+enum { LK_PLAIN = 0, LK_STATS = 1, LK_BN = 2, LK_BIAS_ACT = 3 };       // `variant` of ppea_dwconv_lk_plan
+
+struct LkChoice {
+    int family;                              // 0: no MFMA kernel serves the shape, 1: row-band, 2: batch-major
+    RbPlan rb;                               // family 1: dwconv_mfma_kernel<K, KS, MODE, nseg, bn, ws, ba>
+    int nseg, ws, ba;
+    BmPlan bm;                               // family 2: dwconv_bm_kernel<K, KS, MODE, h, ny, ntx, rs, bn>
+    int h, ny, ntx, rs;
+    int bn;
+    int (*launch)(const LkArgs&, const LkChoice&);
+    int partials() const { return family == 1 ? rb.wpc : family == 2 ? bm.partials : 0; }
+};
+
+inline bool env_not_off(const char* name) {
+    const char* v = getenv(name);
+    return !(v != nullptr && v[0] == '0');
+}
+
+// false when the shape is not this variant's (choose_lk goes on to the row-band kernel)
 template <int K, int KS, int MODE, int H, int NY, int NTX>
-int plan_bm(int N, int C, int W, BmPlan& p) {
+bool plan_bm(int N, int C, int W, BmPlan& p) {
     using B = BmGeo<K, NTX>;
     using B1 = BmGeo<(KS > 0 ? KS : 5), NTX>;
     constexpr int SPLIT = H / NY, CPW = 4 / SPLIT;
     constexpr int NT_IN = (MODE == 1 && KS > 0) ? 2 : 1;
-    if ((long)N * C * H * W >= (1L << 31) || (long)N * C * H * W < 8) return PPEA_ERR_UNSUPPORTED;   // (masked pieces read the tensor's first 16 bytes)
-    p.gi = 0; p.tile_bytes = 0; p.tile1_bytes = 0;
-    for (int cand : {16, 12, 8, 4}) {                            // images per group: the largest whose tiles fit
+    if ((long)N * C * H * W >= (1L << 31) || (long)N * C * H * W < 8) return false;   // (masked pieces read the tensor's first 16 bytes)
+    static_assert(CPW * H * 12 * (B::STRIDE + (NT_IN == 2 ? B1::STRIDE : 0)) <= LDS_LIMIT, "the tiles of twelve images fit");
+    for (int cand : {16, 12}) {                                  // images per group: the largest whose tiles fit
         const int alloc = N < cand ? N : cand;
         const int tb = H * alloc * B::STRIDE, tb1 = NT_IN == 2 ? H * alloc * B1::STRIDE : 0;
         if (CPW * (tb + tb1) <= LDS_LIMIT) { p.gi = cand; p.tile_bytes = tb; p.tile1_bytes = tb1; break; }
     }
-    if (!p.gi) return PPEA_ERR_UNSUPPORTED;
     p.ngroups = (N + p.gi - 1) / p.gi;
     // column tiles per workgroup: whole planes on the small maps; on wide maps enough workgroups to fill the chip
     const int ntx_all = (W + 15) / 16;
@@ -1235,55 +1232,46 @@ int plan_bm(int N, int C, int W, BmPlan& p) {
     p.partials = SPLIT * p.ngroups * p.wgpc;
     p.lds = (size_t)CPW * (p.tile_bytes + p.tile1_bytes);
     if (p.lds < (size_t)4 * frag_scratch_bytes(K, KS)) p.lds = (size_t)4 * frag_scratch_bytes(K, KS);
-    return 0;
+    return true;
 }
 
 template <int K, int KS, int MODE, int H, int NY, int NTX, int RS, bool BN>
-int launch_bm(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0, uint16_t* o1,
-              int N, int C, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn, int* plan_out) {
+int launch_bm(const LkArgs& a, const LkChoice& ch) {
     constexpr int SPLIT = H / NY, CPW = 4 / SPLIT;
-    BmPlan p;
-    const int perr = plan_bm<K, KS, MODE, H, NY, NTX>(N, C, W, p);
-    if (perr != 0) return perr;
-    if (wpc_out != nullptr) { *wpc_out = p.partials; return 0; }
-    if (plan_out != nullptr) {
-        const int rep[LK_PLAN_INTS] = {2, MODE == 0 ? p.partials : 0, (int)p.lds, 0, 0, BN ? 1 : 0, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                       H, NY, NTX, RS, (W & 7) == 0 ? 8 : 4, p.gi, p.ngroups, p.wgpc, p.cpw};
-        for (int i = 0; i < LK_PLAN_INTS; ++i) plan_out[i] = rep[i];
-        return 0;
-    }
+    const BmPlan& p = ch.bm;
     auto kern = dwconv_bm_kernel<K, KS, MODE, H, NY, NTX, RS, BN>;
-    const BnIn bnv = bn != nullptr ? *bn : BnIn{nullptr, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         attr_done = true;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)(((C + CPW - 1) / CPW) * p.ngroups * p.wgpc)), dim3(256), p.lds, st, in0, in1, wb, ws,
-                       o0, o1, N, C, W, p.gi, p.ngroups, p.wgpc, p.cpw, p.tile_bytes, p.tile1_bytes, stats, bnv);
+    hipLaunchKernelGGL(kern, dim3((unsigned)(((a.C + CPW - 1) / CPW) * p.ngroups * p.wgpc)), dim3(256), p.lds, a.st, a.in0, a.in1,
+                       a.wb, a.ws, a.o0, a.o1, a.N, a.C, a.W, p.gi, p.ngroups, p.wgpc, p.cpw, p.tile_bytes, p.tile1_bytes,
+                       a.stats, a.bn);
     return launch_status();
 }
 
 template <int K, int KS, int MODE, int H, int NY, int NTX, int RS>
-int launch_bm_n(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0, uint16_t* o1,
-                int N, int C, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn, int* plan_out) {
+LkChoice choose_bm_n(bool bn, int N, int C, int W) {
+    LkChoice ch{};
+    if (!plan_bm<K, KS, MODE, H, NY, NTX>(N, C, W, ch.bm)) return ch;
+    ch.family = 2; ch.h = H; ch.ny = NY; ch.ntx = NTX; ch.rs = RS; ch.bn = bn ? 1 : 0;
+    ch.launch = launch_bm<K, KS, MODE, H, NY, NTX, RS, false>;
     if constexpr (MODE == 0) {
-        if (bn != nullptr) return launch_bm<K, KS, MODE, H, NY, NTX, RS, true>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, bn, plan_out);
+        if (bn) ch.launch = launch_bm<K, KS, MODE, H, NY, NTX, RS, true>;
     }
-    if (bn != nullptr) return PPEA_ERR_UNSUPPORTED;
-    return launch_bm<K, KS, MODE, H, NY, NTX, RS, false>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, nullptr, plan_out);
+    return ch;
 }
 
-// The plane sizes this variant is built for: RepLKNet stages 0-3 of 192-row frames (48 x W in segments, 24 x {64, 80},
-// 12 x {8..48}, 6 x {4..48}).
+// The plane sizes the batch-major variant is built for: RepLKNet stages 0-3 of 192-row frames (48 x W in segments,
+// 24 x {64, 80}, 12 x {8..48}, 6 x {4..48}).
 template <int K, int KS, int MODE>
-int launch_bm_w(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0, uint16_t* o1,
-                int N, int C, int H, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn, int* plan_out) {
-    static const bool on = !(getenv("PPEA_DW_BM") != nullptr && getenv("PPEA_DW_BM")[0] == '0');
-    if (!on || (W & 3) != 0) return PPEA_ERR_UNSUPPORTED;
+LkChoice choose_bm(bool bn, int N, int C, int H, int W) {
+    static const bool on = env_not_off("PPEA_DW_BM");
+    if (!on || (W & 3) != 0) return LkChoice{};
     const int ntx = (W + 15) / 16;
-#define PPEA_BM_NTX(H_, NTX_)                                                                                          \
-    if (H == H_ && ntx == NTX_) return launch_bm_n<K, KS, MODE, H_, 6, NTX_, 1>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, bn, plan_out);
+#define PPEA_BM_NTX(H_, NTX_) \
+    if (H == H_ && ntx == NTX_) return choose_bm_n<K, KS, MODE, H_, 6, NTX_, 1>(bn, N, C, W);
     if constexpr (KS == 5 && K == 29) { PPEA_BM_NTX(24, 4) PPEA_BM_NTX(24, 5) }
     if constexpr (KS == 5 && K == 27) { PPEA_BM_NTX(12, 1) PPEA_BM_NTX(12, 2) PPEA_BM_NTX(12, 3) }
     if constexpr (KS == 5 && K == 13) { PPEA_BM_NTX(6, 1) PPEA_BM_NTX(6, 2) PPEA_BM_NTX(6, 3) }
@@ -1295,25 +1283,27 @@ int launch_bm_w(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, co
         // measured 65-73 us here against 58 (tools/bench_dwconv.py) -- all 256 workgroups stage their 129 KB segment at the
         // same time with nothing to overlap it (one workgroup per CU, no registers left for a prefetch) and the epilogue's
         // 32-byte runs per image cost as much as on the small maps.  PPEA_DW_BM48=0 disables the variant.
-        static const bool on48 = !(getenv("PPEA_DW_BM48") != nullptr && getenv("PPEA_DW_BM48")[0] == '0');
+        static const bool on48 = env_not_off("PPEA_DW_BM48");
         const int groups16 = (N + 15) / 16;
         if (on48 && H == 48 && (W & 7) == 0 && 10 * N >= 7 * 16 * groups16)
-            return launch_bm_n<K, KS, MODE, 48, 12, 2, 4>(in0, in1, wb, ws, o0, o1, N, C, W, st, stats, wpc_out, bn, plan_out);
+            return choose_bm_n<K, KS, MODE, 48, 12, 2, 4>(bn, N, C, W);
     }
-    return PPEA_ERR_UNSUPPORTED;
+    return LkChoice{};
 }
 
-struct RbPlan { int band, G, tile_bytes, region, bands, segs, items_per_channel, wpc, ipw, fast; long total_waves; size_t lds; };
-
-template <int K, int KS, int MODE, int NSEG, bool WS>
-int plan_rb(int N, int C, int H, int W, RbPlan& p) {
+template <int K, int KS, int MODE, int NSEG>
+bool plan_rb(int N, int C, int H, int W, RbPlan& p) {
     constexpr int STRIDE_B = Seg<K, NSEG>::STRIDE;
     constexpr int NT_IN = (MODE == 1 && KS > 0) ? 2 : 1;
-    if ((long)N * C * H * W >= (1L << 31)) return PPEA_ERR_UNSUPPORTED;      // 32-bit element offsets
-    if ((long)N * C * H * W < 8) return PPEA_ERR_UNSUPPORTED;                // masked lanes read the first 16 bytes
+    if ((long)N * C * H * W >= (1L << 31)) return false;                     // 32-bit element offsets
+    if ((long)N * C * H * W < 8) return false;                               // masked lanes read the first 16 bytes
+    // a single plane's band of 32 rows always fits (142 848 B at K = 31, NSEG 5 with two inputs): the search ends at 32
+    constexpr int TB32 = ((32 + K - 1) * STRIDE_B + 15) & ~15;
+    static_assert(WAVES * (NT_IN * TB32 > frag_scratch_bytes(K, KS) ? NT_IN * TB32 : frag_scratch_bytes(K, KS)) <= LDS_LIMIT,
+                  "a 32-row band fits");
     // largest band / stacking whose per-wave region fits four times into the 160 KB of LDS
     int band = 0, G = 1, tile_bytes = 0, region = 0;
-    for (int cand : {48, 32, 16}) {
+    for (int cand : {48, 32}) {
         int g = (H < cand) ? (cand / H < N ? cand / H : N) : 1;
         if (g < 1) g = 1;
         for (; g >= 1; --g) {
@@ -1325,7 +1315,6 @@ int plan_rb(int N, int C, int H, int W, RbPlan& p) {
         }
         if (band) break;
     }
-    if (!band) return PPEA_ERR_UNSUPPORTED;
     p.band = band; p.G = G; p.tile_bytes = tile_bytes; p.region = region;
     p.bands = (G > 1) ? 1 : (H + band - 1) / band;
     p.segs = (W + 16 * NSEG - 1) / (16 * NSEG);
@@ -1341,115 +1330,102 @@ int plan_rb(int N, int C, int H, int W, RbPlan& p) {
     p.total_waves = (long)C * p.wpc;
     p.lds = (size_t)WAVES * region;
     p.fast = fast_staging<K, NSEG>(H, W, G, p.bands) ? 1 : 0;
-    if constexpr (WS) {
-        if (!(G == 1 && band == 48 && H % 48 == 0)) return PPEA_ERR_UNSUPPORTED;       // every item: one 48-row band
-    }
-    return 0;
+    return true;
 }
 
-// stats / wpc_out: forward only -- per-wave partial sums for the BatchNorm pair (see the kernel); wpc_out != nullptr:
-// do not launch, return the number of waves per channel (= partials per channel) the launch would use
-template <int K, int KS, int MODE, int NSEG, bool BN = false, bool WS = false, bool BA = false>
-int launch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0,
-           uint16_t* o1, int N, int C, int H, int W, hipStream_t st, float* stats = nullptr, int* wpc_out = nullptr,
-           const BnIn* bn = nullptr, int* plan_out = nullptr) {
-    RbPlan p;
-    const int perr = plan_rb<K, KS, MODE, NSEG, WS>(N, C, H, W, p);
-    if (perr != 0) return perr;
-    if (wpc_out != nullptr) { *wpc_out = p.wpc; return 0; }
-    if (plan_out != nullptr) {
-        const int rep[LK_PLAN_INTS] = {1, (MODE == 0 && !BA) ? p.wpc : 0, (int)p.lds, NSEG, WS ? 1 : 0, BN ? 1 : 0, BA ? 1 : 0,
-                                       p.band, p.G, p.bands, p.segs, p.items_per_channel, p.wpc, p.ipw, p.fast,
-                                       0, 0, 0, 0, 0, 0, 0, 0, 0};
-        for (int i = 0; i < LK_PLAN_INTS; ++i) plan_out[i] = rep[i];
-        return 0;
-    }
+template <int K, int KS, int MODE, int NSEG, bool BN, bool WS, bool BA>
+int launch_rb(const LkArgs& a, const LkChoice& ch) {
+    const RbPlan& p = ch.rb;
     auto kern = dwconv_mfma_kernel<K, KS, MODE, NSEG, BN, WS, BA>;
-    const BnIn bnv = bn != nullptr ? *bn : BnIn{nullptr, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     static bool attr_done = false;
     if (!attr_done) {
         (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         attr_done = true;
     }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((p.total_waves + WAVES - 1) / WAVES)), dim3(64 * WAVES), p.lds, st, in0,
-                       in1, wb, ws, o0, o1, N, C, H, W, p.G, p.band, p.bands, p.segs, p.items_per_channel, p.ipw, p.wpc,
-                       p.total_waves, p.tile_bytes, p.region, stats, bnv);
+    hipLaunchKernelGGL(kern, dim3((unsigned)((p.total_waves + WAVES - 1) / WAVES)), dim3(64 * WAVES), p.lds, a.st, a.in0,
+                       a.in1, a.wb, a.ws, a.o0, a.o1, a.N, a.C, a.H, a.W, p.G, p.band, p.bands, p.segs, p.items_per_channel,
+                       p.ipw, p.wpc, p.total_waves, p.tile_bytes, p.region, a.stats, a.bn);
     return launch_status();
 }
 
-// staged columns for a choice of NSEG (cost model: LDS staging traffic)
+// column tiles per staged segment: the choice with the fewest staged columns (cost model: LDS staging traffic)
 template <int K>
-inline long staged_cols(int W, int nseg) {
-    const long segs = (W + 16 * nseg - 1) / (16 * nseg);
-    return segs * (16 * (nseg - 1) + 32 * Geo<K>::NS);
+int pick_nseg(int W) {
+    auto staged_cols = [W](int nseg) {
+        const long segs = (W + 16 * nseg - 1) / (16 * nseg);
+        return segs * (16 * (nseg - 1) + 32 * Geo<K>::NS);
+    };
+    const long c5 = staged_cols(5), c3 = staged_cols(3), c2 = staged_cols(2);
+    return (c5 <= c3 && c5 <= c2) ? 5 : (c3 <= c2 ? 3 : 2);
+}
+
+template <int K, int KS, int MODE, int NSEG>
+LkChoice choose_rb(int variant, int N, int C, int H, int W) {
+    LkChoice ch{};
+    if (!plan_rb<K, KS, MODE, NSEG>(N, C, H, W, ch.rb)) return ch;
+    ch.family = 1; ch.nseg = NSEG;
+    ch.launch = launch_rb<K, KS, MODE, NSEG, false, false, false>;
+    if constexpr (MODE == 0 && KS == 5) {                        // fused input BatchNorm + ReLU (RepLKBlock forward)
+        if (variant == LK_BN) { ch.bn = 1; ch.launch = launch_rb<K, KS, MODE, NSEG, true, false, false>; }
+    }
+    if constexpr (MODE == 0 && KS == 0) {                        // merged filter + bias (+ ReLU)
+        if (variant == LK_BIAS_ACT) { ch.ba = 1; ch.launch = launch_rb<K, KS, MODE, NSEG, false, false, true>; }
+    }
+    if constexpr (K == 31 && KS == 5 && MODE == 0 && NSEG == 5) {
+        // window sharing between the three stacked tiles of a 48-row plane (stage 0 at 192 x 640), when every item is one
+        // 48-row band.  (ppea_dwconv_lk_stats_partials goes by the same plan: its wpc does not depend on the variant.)
+        static const bool ws_on = env_not_off("PPEA_DW_WS");
+        if (ws_on && ch.rb.G == 1 && ch.rb.band == 48 && H % 48 == 0) {
+            ch.ws = 1;
+            ch.launch = ch.bn ? launch_rb<K, KS, MODE, 5, true, true, false> : launch_rb<K, KS, MODE, 5, false, true, false>;
+        }
+    }
+    return ch;
 }
 
 template <int K, int KS, int MODE>
-int launch_k(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0,
-             uint16_t* o1, int N, int C, int H, int W, hipStream_t st, float* stats, int* wpc_out, const BnIn* bn, int* plan_out) {
-    {                                                            // small planes: the batch-major variant
-        const int err = launch_bm_w<K, KS, MODE>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
-        if (err != PPEA_ERR_UNSUPPORTED) return err;
-    }
+LkChoice choose_k(int variant, int N, int C, int H, int W) {
+    // the variants that have kernels: the fused BatchNorm is the pair's forward, bias + activation the merged filter's
+    if (variant == LK_BN && !(MODE == 0 && KS == 5)) return LkChoice{};
+    if (variant == LK_BIAS_ACT && !(MODE == 0 && KS == 0)) return LkChoice{};
+    if (variant != LK_BIAS_ACT) {
+        const LkChoice ch = choose_bm<K, KS, MODE>(variant == LK_BN, N, C, H, W);      // small planes: the batch-major variant
+        if (ch.family) return ch;
 #ifdef PPEA_BM_ONLY                                              // (compile-time experiments with the batch-major variant alone)
-    return PPEA_ERR_UNSUPPORTED;
+        return ch;
 #endif
-    const long c5 = staged_cols<K>(W, 5), c3 = staged_cols<K>(W, 3), c2 = staged_cols<K>(W, 2);
-    const int nseg = (c5 <= c3 && c5 <= c2) ? 5 : (c3 <= c2 ? 3 : 2);
-    if constexpr (K == 31 && KS == 5) {
-        // window sharing between the three stacked tiles of a 48-row plane (stage 0 at 192 x 640): launch() refuses the
-        // variant unless every item is one 48-row band, and the generic kernel takes over below
-        static const bool ws_on = !(getenv("PPEA_DW_WS") != nullptr && getenv("PPEA_DW_WS")[0] == '0');
-        if (ws_on && nseg == 5 && wpc_out == nullptr) {
-            int err;
-            if constexpr (MODE == 0) {
-                err = bn != nullptr ? launch<K, KS, MODE, 5, true, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, nullptr, bn, plan_out)
-                                    : launch<K, KS, MODE, 5, false, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, nullptr, nullptr, plan_out);
-            } else {
-                err = bn != nullptr ? PPEA_ERR_UNSUPPORTED
-                                    : launch<K, KS, MODE, 5, false, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, nullptr, nullptr, plan_out);
-            }
-            if (err != PPEA_ERR_UNSUPPORTED) return err;
-        }
     }
-    if constexpr (MODE == 0 && KS == 5) {
-        if (bn != nullptr) {                                     // fused input BatchNorm + ReLU (RepLKBlock forward)
-            if (nseg == 5) return launch<K, KS, MODE, 5, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
-            if (nseg == 3) return launch<K, KS, MODE, 3, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
-            return launch<K, KS, MODE, 2, true>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
-        }
+    switch (pick_nseg<K>(W)) {
+        case 5: return choose_rb<K, KS, MODE, 5>(variant, N, C, H, W);
+        case 3: return choose_rb<K, KS, MODE, 3>(variant, N, C, H, W);
+        default: return choose_rb<K, KS, MODE, 2>(variant, N, C, H, W);
     }
-    if (bn != nullptr) return PPEA_ERR_UNSUPPORTED;
-    if (nseg == 5) return launch<K, KS, MODE, 5>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, nullptr, plan_out);
-    if (nseg == 3) return launch<K, KS, MODE, 3>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, nullptr, plan_out);
-    return launch<K, KS, MODE, 2>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, nullptr, plan_out);
 }
 
-// Merged filter + bias (+ ReLU), forward: the general kernel with the column-segment choice of launch_k.
-template <int K>
-int launch_bias_act(const uint16_t* x, const uint16_t* wb, uint16_t* y, const float* bias, int relu, int N, int C, int H,
-                    int W, hipStream_t st, int* plan_out = nullptr) {
-    const long c5 = staged_cols<K>(W, 5), c3 = staged_cols<K>(W, 3), c2 = staged_cols<K>(W, 2);
-    const int nseg = (c5 <= c3 && c5 <= c2) ? 5 : (c3 <= c2 ? 3 : 2);
-    const BnIn ba{nullptr, relu ? 1 : 0, 0.f, 0.f, 0.f, nullptr, bias, nullptr, nullptr, nullptr, nullptr};
-    if (nseg == 5) return launch<K, 0, 0, 5, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba, plan_out);
-    if (nseg == 3) return launch<K, 0, 0, 3, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba, plan_out);
-    return launch<K, 0, 0, 2, false, false, true>(x, nullptr, wb, nullptr, y, nullptr, N, C, H, W, st, nullptr, nullptr, &ba, plan_out);
-}
-
-template <int MODE>
-int dispatch(const uint16_t* in0, const uint16_t* in1, const uint16_t* wb, const uint16_t* ws, uint16_t* o0,
-             uint16_t* o1, int N, int C, int H, int W, int K, int KS, hipStream_t st, float* stats = nullptr,
-             int* wpc_out = nullptr, const BnIn* bn = nullptr, int* plan_out = nullptr) {
-#define PPEA_CASE(K_)                                                                             \
-    case K_:                                                                                      \
-        return KS == 5 ? launch_k<K_, 5, MODE>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out)   \
-                       : launch_k<K_, 0, MODE>(in0, in1, wb, ws, o0, o1, N, C, H, W, st, stats, wpc_out, bn, plan_out);
+// f(std::integral_constant<int, K>) for the filter sizes that have kernels
+template <typename F>
+LkChoice with_k(int K, F&& f) {
     switch (K) {
-        PPEA_CASE(31) PPEA_CASE(29) PPEA_CASE(27) PPEA_CASE(13)
-        default: return PPEA_ERR_UNSUPPORTED;
+        case 31: return f(std::integral_constant<int, 31>{});
+        case 29: return f(std::integral_constant<int, 29>{});
+        case 27: return f(std::integral_constant<int, 27>{});
+        case 13: return f(std::integral_constant<int, 13>{});
+        default: return LkChoice{};
     }
-#undef PPEA_CASE
+}
+
+// mode 0: forward, 1: data gradient; variant: LK_PLAIN .. LK_BIAS_ACT (LK_STATS chooses what LK_PLAIN chooses)
+LkChoice choose_lk(int K, int KS, int mode, int variant, int N, int C, int H, int W) {
+    return with_k(K, [&](auto k) {
+        constexpr int K_ = decltype(k)::value;
+        if (mode == 0) return KS == 5 ? choose_k<K_, 5, 0>(variant, N, C, H, W) : choose_k<K_, 0, 0>(variant, N, C, H, W);
+        return KS == 5 ? choose_k<K_, 5, 1>(variant, N, C, H, W) : choose_k<K_, 0, 1>(variant, N, C, H, W);
+    });
+}
+
+int launch_lk(int K, int KS, int mode, int variant, const LkArgs& a) {
+    const LkChoice ch = choose_lk(K, KS, mode, variant, a.N, a.C, a.H, a.W);
+    return ch.family ? ch.launch(a, ch) : PPEA_ERR_UNSUPPORTED;
 }
 
 }  // namespace
@@ -1482,8 +1458,8 @@ int ppea_dwconv_lk_fwd_bf16p(const uint16_t* x, const void* packed_big, const vo
     if (N == 0) return 0;
     if (packed_small == nullptr || y_small == nullptr) KS = 0;
     if (KS != 0 && KS != 5) return PPEA_ERR_UNSUPPORTED;
-    return dispatch<0>(x, nullptr, (const uint16_t*)packed_big, (const uint16_t*)packed_small, y_big, y_small, N, C,
-                       H, W, K, KS, (hipStream_t)stream);
+    return launch_lk(K, KS, 0, LK_PLAIN, {x, nullptr, (const uint16_t*)packed_big, (const uint16_t*)packed_small, y_big, y_small,
+                                          N, C, H, W, (hipStream_t)stream, nullptr, no_bn()});
 }
 
 // Inference: y = act(DW_k(x; merged filter) + bias[c]), relu != 0: ReLU -- an eval-mode ReparamLargeKernelConv + ReLU in one
@@ -1493,15 +1469,8 @@ int ppea_dwconv_lk_fwd_bias_act_bf16p(const uint16_t* x, const void* packed, con
                                       int C, int H, int W, int K, void* stream) {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0) return PPEA_ERR_UNSUPPORTED;
     if (x == nullptr || packed == nullptr || bias == nullptr || y == nullptr) return PPEA_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const uint16_t* wb = (const uint16_t*)packed;
-    switch (K) {
-        case 31: return launch_bias_act<31>(x, wb, y, bias, relu, N, C, H, W, st);
-        case 29: return launch_bias_act<29>(x, wb, y, bias, relu, N, C, H, W, st);
-        case 27: return launch_bias_act<27>(x, wb, y, bias, relu, N, C, H, W, st);
-        case 13: return launch_bias_act<13>(x, wb, y, bias, relu, N, C, H, W, st);
-        default: return PPEA_ERR_UNSUPPORTED;
-    }
+    return launch_lk(K, 0, 0, LK_BIAS_ACT, {x, nullptr, (const uint16_t*)packed, nullptr, y, nullptr, N, C, H, W,
+                                            (hipStream_t)stream, nullptr, bias_act_in(bias, relu)});
 }
 
 // Forward as above plus the statistics of the two BatchNorms that follow (rka.py:232-239): stats [2][C][P][2] fp32 =
@@ -1509,9 +1478,7 @@ int ppea_dwconv_lk_fwd_bias_act_bf16p(const uint16_t* x, const void* packed, con
 // P = ppea_dwconv_lk_stats_partials(N, C, H, W, K, KS); reduce each half with ppea_bn_finalize_sums_f32.
 int ppea_dwconv_lk_stats_partials(int N, int C, int H, int W, int K, int KS) {
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (KS != 0 && KS != 5)) return 0;
-    int wpc = 0;
-    const int err = dispatch<0>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, C, H, W, K, KS, nullptr, nullptr, &wpc);
-    return err == 0 ? wpc : 0;
+    return choose_lk(K, KS, 0, LK_STATS, N, C, H, W).partials();
 }
 int ppea_dwconv_lk_fwd_stats_bf16p(const uint16_t* x, const void* packed_big, const void* packed_small, uint16_t* y_big,
                                    uint16_t* y_small, float* stats, int N, int C, int H, int W, int K, int KS,
@@ -1519,8 +1486,8 @@ int ppea_dwconv_lk_fwd_stats_bf16p(const uint16_t* x, const void* packed_big, co
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || stats == nullptr) return PPEA_ERR_UNSUPPORTED;
     if (packed_small == nullptr || y_small == nullptr) KS = 0;
     if (KS != 0 && KS != 5) return PPEA_ERR_UNSUPPORTED;
-    return dispatch<0>(x, nullptr, (const uint16_t*)packed_big, (const uint16_t*)packed_small, y_big, y_small, N, C,
-                       H, W, K, KS, (hipStream_t)stream, stats, nullptr);
+    return launch_lk(K, KS, 0, LK_STATS, {x, nullptr, (const uint16_t*)packed_big, (const uint16_t*)packed_small, y_big, y_small,
+                                          N, C, H, W, (hipStream_t)stream, stats, no_bn()});
 }
 
 // Forward with the BatchNorm (+ ReLU) of the INPUT fused into the staging pass (RepLKBlock: pw1 conv_bn_relu -> large
@@ -1537,8 +1504,8 @@ int ppea_dwconv_lk_fwd_bn_bf16p(const uint16_t* x, const void* packed_big, const
     if (sums == nullptr || P <= 0 || count <= 0 || gamma == nullptr || beta == nullptr || mean == nullptr || invstd == nullptr)
         return PPEA_ERR_ARG;
     const BnIn bn{sums, P, (float)count, eps, momentum, gamma, beta, running_mean, running_var, mean, invstd};
-    return dispatch<0>(x, nullptr, (const uint16_t*)packed_big, (const uint16_t*)packed_small, y_big, y_small, N, C,
-                       H, W, K, KS, (hipStream_t)stream, nullptr, nullptr, &bn);
+    return launch_lk(K, KS, 0, LK_BN, {x, nullptr, (const uint16_t*)packed_big, (const uint16_t*)packed_small, y_big, y_small,
+                                       N, C, H, W, (hipStream_t)stream, nullptr, bn});
 }
 
 int ppea_dwconv_lk_bwd_data_bf16p(const uint16_t* dy_big, const uint16_t* dy_small, const void* packed_big_flip,
@@ -1548,12 +1515,12 @@ int ppea_dwconv_lk_bwd_data_bf16p(const uint16_t* dy_big, const uint16_t* dy_sma
     if (N == 0) return 0;
     if (packed_small_flip == nullptr || dy_small == nullptr) KS = 0;
     if (KS != 0 && KS != 5) return PPEA_ERR_UNSUPPORTED;
-    return dispatch<1>(dy_big, dy_small, (const uint16_t*)packed_big_flip, (const uint16_t*)packed_small_flip, dx,
-                       nullptr, N, C, H, W, K, KS, (hipStream_t)stream);
+    return launch_lk(K, KS, 1, LK_PLAIN, {dy_big, dy_small, (const uint16_t*)packed_big_flip, (const uint16_t*)packed_small_flip,
+                                          dx, nullptr, N, C, H, W, (hipStream_t)stream, nullptr, no_bn()});
 }
 
 // Host only (no device call, no stream): the kernel and the launch geometry the entry points above go by for this shape,
-// answered by the launchers themselves (see plan_rb / plan_bm).  mode 0: forward, 1: data gradient; variant 0: plain,
+// answered by choose_lk itself.  mode 0: forward, 1: data gradient; variant 0: plain,
 // 1: with statistics, 2: fused input BatchNorm, 3: bias + activation.  plan [24] as laid out in include/ppea_depth.h;
 // plan[0] == 0: no MFMA kernel serves the shape (the entry point returns PPEA_ERR_UNSUPPORTED).
 int ppea_dwconv_lk_plan(int N, int C, int H, int W, int K, int KS, int mode, int variant, int* plan) {
@@ -1562,26 +1529,17 @@ int ppea_dwconv_lk_plan(int N, int C, int H, int W, int K, int KS, int mode, int
     if (N <= 0 || C <= 0 || H <= 0 || W <= 0 || (KS != 0 && KS != 5)) return 0;
     if (mode == 1 && variant != 0) return 0;
     if ((variant == 2 && KS != 5) || (variant == 3 && KS != 0)) return 0;
-    int err;
-    if (variant == 3) {
-        switch (K) {
-            case 31: err = launch_bias_act<31>(nullptr, nullptr, nullptr, nullptr, 0, N, C, H, W, nullptr, plan); break;
-            case 29: err = launch_bias_act<29>(nullptr, nullptr, nullptr, nullptr, 0, N, C, H, W, nullptr, plan); break;
-            case 27: err = launch_bias_act<27>(nullptr, nullptr, nullptr, nullptr, 0, N, C, H, W, nullptr, plan); break;
-            case 13: err = launch_bias_act<13>(nullptr, nullptr, nullptr, nullptr, 0, N, C, H, W, nullptr, plan); break;
-            default: err = PPEA_ERR_UNSUPPORTED;
-        }
-    } else {
-        const BnIn bn{nullptr, 0, 0.f, 0.f, 0.f, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // routes only
-        const BnIn* bnp = variant == 2 ? &bn : nullptr;
-        err = mode == 0 ? dispatch<0>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, C, H, W, K, KS, nullptr, nullptr, nullptr, bnp, plan)
-                        : dispatch<1>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, C, H, W, K, KS, nullptr, nullptr, nullptr, bnp, plan);
-    }
-    if (err == PPEA_ERR_UNSUPPORTED) {
-        for (int i = 0; i < LK_PLAN_INTS; ++i) plan[i] = 0;
-        return 0;
-    }
-    return err;
+    const LkChoice ch = choose_lk(K, KS, mode, variant, N, C, H, W);
+    const RbPlan& r = ch.rb;
+    const BmPlan& b = ch.bm;
+    const int rep[3][LK_PLAN_INTS] = {
+        {0},
+        {1, (mode == 0 && !ch.ba) ? r.wpc : 0, (int)r.lds, ch.nseg, ch.ws, ch.bn, ch.ba, r.band, r.G, r.bands, r.segs,
+         r.items_per_channel, r.wpc, r.ipw, r.fast, 0, 0, 0, 0, 0, 0, 0, 0, 0},
+        {2, mode == 0 ? b.partials : 0, (int)b.lds, 0, 0, ch.bn, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+         ch.h, ch.ny, ch.ntx, ch.rs, (W & 7) == 0 ? 8 : 4, b.gi, b.ngroups, b.wgpc, b.cpw}};
+    for (int i = 0; i < LK_PLAN_INTS; ++i) plan[i] = rep[ch.family][i];
+    return 0;
 }
 
 // Test support, host only: ppea_dwconv_lk_plan over the grid N 1..Nmax x C in Cs[nC] x H 1..Hmax x W 1..Wmax, folded.
